@@ -6,14 +6,18 @@ A *step* is one pass of the hot path over one token (batch 1): for each of the 3
     ->  FFN down (W2 11008->4096)
 then lm_head (4096->32000) — 6 607 077 376 weights, 3 716 481 024 algorithmic bytes, all through the
 device-resident C ABI of libns_hip.so (include/ns_bestla.h part 3), captured once in a HIP graph and replayed.
-Inputs are resident in HBM when the timed region starts.  Weights are synthetic (seeded torch.randn, quantized and
+Every layer reads the token's seeded input vector (the chain has no norms; see Chain.__init__) and writes its own
+output row.  Inputs are resident in HBM when the timed region starts.  Weights are synthetic (seeded torch.randn, quantized and
 packed ON THE GPU by the product quantizer into reference-format blobs, then loaded like any reference blob).
 
 N > 1: 1-D tensor parallel exactly as the reference shards Llama (models/model_utils/model_files.h:145-190):
 wq/wk/wv/w1/w3 split on N, wo/w2 split on K + one fp32 all-reduce each (RCCL), lm_head replicated; one process per
 GPU under torch.distributed.  Total work is fixed -> "scaling": "strong".
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline` objects.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times exactly --steps steps and reports them
+(`ms_per_step`, `value` = tokens/s); --full adds five more timed batches (`value` = their median), the `roofline` and
+`cpu_baseline` objects and the other legs (parity, whole token, prefill, int8 semantics, config 4 / 5, reference route).
+--dump-outputs DIR writes the last timed step's logits (DIR/logits.npy) and every layer's output (DIR/hidden.npy), float32.
 """
 import argparse
 import ctypes as C
@@ -54,6 +58,13 @@ def parse():
     ap.add_argument("--full-token-only", action="store_true", help="diagnostics: print the whole-token leg alone and exit")
     ap.add_argument("--no-reference-route", action="store_true", help="skip the leg that runs the reference's unchanged model_eval on the device route")
     ap.add_argument("--reference-route-only", action="store_true", help="diagnostics: print the reference_route leg alone and exit")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: five more timed batches (value = their median), parity "
+                         "against the oracle, roofline, whole token / prefill / int8 / config 4-5 legs, CPU baseline, "
+                         "reference route, all-reduce latency (TP)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (rank 0's logits and every layer's "
+                         "output) as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -79,7 +90,7 @@ class Chain:
             seed = 1000 + il * 8
             lw = {}
             kh = keep_host_layer and il < self.KEEP_HOST_LAYERS
-            # norm-preserving synthetic init keeps activations O(1) through the chain (random data, no zeros)
+            # norm-preserving synthetic init: one layer maps an O(1) input to an O(1) output (random data, no zeros)
             lw["q"] = self._make(self.dl, d, seed + 0, d ** -0.5, kh)
             lw["k"] = self._make(self.dl, d, seed + 1, d ** -0.5, kh)
             lw["v"] = self._make(self.dl, d, seed + 2, d ** -0.5, kh)
@@ -104,7 +115,11 @@ class Chain:
         dev = "cuda"
         g = torch.Generator(device=dev).manual_seed(7)
         self.x0 = torch.randn((1, d), generator=g, device=dev, dtype=torch.float32)
-        self.x = torch.empty_like(self.x0)
+        # every layer reads the token's input x0 and writes its own row of `hidden`.  The chain has no norms, and without
+        # them the gated FFN squares the activations' scale layer after layer: fed from one layer to the next, the fp16
+        # shadows overflowed partway through the 32 layers and every logit came out NaN.  Launches, shapes and bytes are the same.
+        self.hidden = torch.empty((n_layers, 1, d), device=dev, dtype=torch.float32)
+        self.x = self.hidden[n_layers - 1]
         self.qkv = torch.empty((3, 1, self.dl), device=dev, dtype=torch.float32)
         self.attn = torch.empty((1, d), device=dev, dtype=torch.float32)
         self.t2 = torch.empty((1, self.ffl), device=dev, dtype=torch.float32)
@@ -147,7 +162,9 @@ class Chain:
         tp_ = self.world > 1  # after an all-reduce the fp16 shadow of the summed vector is stale: fall back to fp32 A
         items = []
         x_in, x_in_h = self.x0, self.x0h
-        for lw in self.layers:
+        for il, lw in enumerate(self.layers):
+            x_out = self.hidden[il]
+
             def attn_block(lw=lw, x_in=x_in, x_in_h=x_in_h):
                 st = self.st
                 pkg.check(L.ns_hip_fusion_qkv_forward_h(x_in.data_ptr(), p(x_in_h) if x_in_h is not None else None,
@@ -162,16 +179,18 @@ class Chain:
             if tp_:
                 items.append(("reduce", self.attn))  # ne_all_reduce after attn-out (llama.cpp:590-593)
 
-            def ffn_block(lw=lw):
+            def ffn_block(lw=lw, x_out=x_out):
                 st = self.st
                 pkg.check(L.ns_hip_fusion_ffn3_forward_h(self.attn.data_ptr(), None if tp_ else p(self.attnh),
                                                          lw["w1"].h, lw["w2"].h, lw["w3"].h, None, self.t2.data_ptr(),
-                                                         p(self.t2h), self.x.data_ptr(), None if tp_ else p(self.xh), 1,
+                                                         p(self.t2h), x_out.data_ptr(), None if tp_ else p(self.xh), 1,
                                                          pkg.EPI_SILU, st))
             items.append(("gemm", ffn_block))
             if tp_:
-                items.append(("reduce", self.x))  # ne_all_reduce after FFN (llama.cpp:690-694)
-            x_in, x_in_h = self.x, (None if tp_ else self.xh)
+                items.append(("reduce", x_out))  # ne_all_reduce after FFN (llama.cpp:690-694)
+            # (layers >= 1 read x0 like layer 0; under TP as fp32 A, the path they took before)
+            x_in, x_in_h = self.x0, (None if tp_ else self.x0h)
+        x_in, x_in_h = self.x, (None if tp_ else self.xh)
 
         def head_block(x_in=x_in, x_in_h=x_in_h):
             st = self.st
@@ -207,7 +226,7 @@ class Chain:
         p = lambda t: t.data_ptr() if H else None
         out = []
         x_in, x_in_h = self.x0, self.x0h
-        for lw in self.layers:
+        for il, lw in enumerate(self.layers):
             out.append((lambda lw=lw, x_in=x_in, x_in_h=x_in_h: pkg.check(L.ns_hip_fusion_qkv_forward_h(
                 x_in.data_ptr(), p(x_in_h), lw["q"].h, lw["k"].h, lw["v"].h, self.qkv.data_ptr(), p(self.qkvh), 1, d,
                 self.dl, self.st)), [lw["q"], lw["k"], lw["v"]]))
@@ -217,10 +236,10 @@ class Chain:
             out.append((lambda lw=lw: pkg.check(L.ns_hip_fusion_ffn3_gateup_h(
                 self.attn.data_ptr(), p(self.attnh), lw["w1"].h, lw["w3"].h, None, self.t2.data_ptr(), p(self.t2h), 1,
                 pkg.EPI_SILU, self.st)), [lw["w1"], lw["w3"]]))
-            out.append((lambda lw=lw: pkg.check(L.ns_hip_f32f32_forward_h(
-                self.t2.data_ptr(), p(self.t2h), lw["w2"].h, self.x.data_ptr(), p(self.xh), 1, self.ffl, d,
+            out.append((lambda lw=lw, x_out=self.hidden[il]: pkg.check(L.ns_hip_f32f32_forward_h(
+                self.t2.data_ptr(), p(self.t2h), lw["w2"].h, x_out.data_ptr(), p(self.xh), 1, self.ffl, d,
                 pkg.EPI_NONE, None, 0, self.st)), [lw["w2"]]))
-            x_in, x_in_h = self.x, self.xh
+        x_in, x_in_h = self.x, self.xh
         out.append((lambda x_in=x_in, x_in_h=x_in_h: pkg.check(L.ns_hip_f32f32_forward_h(
             x_in.data_ptr(), p(x_in_h), self.head.h, self.logits.data_ptr(), None, 1, d, self.V, pkg.EPI_NONE, None, 0,
             self.st)), [self.head]))
@@ -375,7 +394,8 @@ def main():
     # which lets two ranks share one GPU; such a line is marked INVALID below)
     use_native = (world > 1 and os.environ.get("NS_TP_NATIVE", "1") != "0" and
                   (backend == "nccl" or bool(os.environ.get("NS_TP_RCCL_LIB"))) and pctx.enable_native())
-    chain = Chain(pkg, args.layers, rank, world, keep_host_layer=(rank == 0 and world == 1 and not args.no_cpu_baseline))
+    chain = Chain(pkg, args.layers, rank, world,
+                  keep_host_layer=(args.full and rank == 0 and world == 1 and not args.no_cpu_baseline))
     # the chain object itself carries the captured stream handle; under graph capture torch switches the current
     # stream, so the stream pointer handed to the C ABI must be re-read inside the capture.
     class Step:
@@ -429,7 +449,8 @@ def main():
             pctx.disable_p2p()  # collective; reduce_add is RCCL from here on
         failed, err = 0, None
         try:
-            wall_ms, ev_ms = time_graph(step, args.steps, args.warmup, use_graph, world, extra_batches=5 if world == 1 else 0)
+            wall_ms, ev_ms = time_graph(step, args.steps, args.warmup, use_graph, world,
+                                        extra_batches=5 if (world == 1 and args.full) else 0)
         except Exception as e:
             failed, err = 1, e
             try:
@@ -452,7 +473,13 @@ def main():
         sys.stderr.write("launch mode %r (%s all-reduce) failed (%s); trying the next one\n" %
                          (use_graph, "peer-memory" if with_p2p else "RCCL",
                           str(err).splitlines()[0] if err else "on another rank"))
-    comm = all_reduce_latency(chain, world, pctx.p2p_enabled() or backend == "nccl") if world > 1 else None  # collective
+    if args.dump_outputs and rank == 0:
+        # the last timed step's result (every step recomputes it from the same seeded input; lm_head is replicated under TP)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "logits.npy"), chain.logits.detach().cpu().numpy().astype(np.float32))
+        np.save(os.path.join(args.dump_outputs, "hidden.npy"), chain.hidden.detach().cpu().numpy().astype(np.float32))
+    comm = (all_reduce_latency(chain, world, pctx.p2p_enabled() or backend == "nccl")
+            if (world > 1 and args.full) else None)  # collective
     t = torch.tensor([wall_ms], device="cuda", dtype=torch.float64)
     if world > 1:
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
@@ -521,12 +548,13 @@ def main():
             worst = max(par.values())
             if not worst <= 1e-3:
                 out["config"]["INVALID"] = "GPU chain disagrees with the oracle (rel-L2 %.3g > 1e-3)" % worst
-        out["roofline"] = roofline(chain, pkg)
+        if args.full:
+            out["roofline"] = roofline(chain, pkg)
         # (stable keys: null at one GPU)
         out["config"]["all_reduce_us"] = comm["us"] if (world > 1 and comm is not None) else None
         out["config"]["all_reduces_per_step"] = comm["per_step"] if (world > 1 and comm is not None) else (None if world > 1 else 0)
         out["config"]["comm_fraction"] = round(comm["us"] * comm["per_step"] / (ms_per_step * 1e3), 4) if (world > 1 and comm is not None) else None
-        if world == 1:
+        if world == 1 and args.full:
             # the whole token (attention over a 2048-position fp16 kv-cache, norms, RoPE, residuals) on the same weights
             ft, lg = full_token(chain, pkg, 2048, fused=True)
             fu, lgu = full_token(chain, pkg, 2048, fused=False, iters=10)
@@ -546,9 +574,9 @@ def main():
                 out["config"]["config5_rank_ms"] = sec["config5"]["ms_per_step"]
                 out["config"]["config4"] = sec["config4"]
                 out["config"]["config5"] = sec["config5"]
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(chain, args.layers)
-        if world == 1 and not args.no_reference_route:
+        if world == 1 and args.full and not args.no_reference_route:
             # (last: the chain's weights are released first — the leg's worker processes load their own model)
             del chain
             torch.cuda.empty_cache()

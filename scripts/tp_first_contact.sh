@@ -52,7 +52,7 @@ if [ "${NS_FC_SKIP_BENCH:-0}" != "1" ]; then
   for n in 1 2 4 8; do
     if [ "$NGPU" -lt "$n" ]; then echo "(c) bench --gpus $n: SKIP (needs $n GPUs)"; continue; fi
     if [ "$n" -eq 1 ]; then python bench.py --gpus 1 --steps 20 --warmup 5 --chain-only > "$OUT/bench_1.json" 2> "$OUT/bench_1.err"
-    else run_ranks "$n" $((29640 + n)) bench.py --gpus "$n" --steps 20 --warmup 5 > "$OUT/bench_$n.json" 2> "$OUT/bench_$n.err"; fi
+    else run_ranks "$n" $((29640 + n)) bench.py --gpus "$n" --steps 20 --warmup 5 --full > "$OUT/bench_$n.json" 2> "$OUT/bench_$n.err"; fi
     python - "$OUT/bench_$n.json" "$n" <<'P' || rc=1
 import json, sys
 try:
