@@ -692,12 +692,16 @@ static void touch_destination_while_queue_runs(void* dst, size_t size, hipStream
   helper.join();
   (void)hipGetLastError();
 }
-void bestla_device_memcpy(void* dstptr, const void* srcptr, size_t size, void* queue) {
+static void device_memcpy_impl(void* dstptr, const void* srcptr, size_t size, void* queue, bool wait_first) {
   (void)ns_hip_lazy_flush();
   // what the route holds back (its window) goes out first; a copy FROM device memory reads a tensor behind the window's last op
   const bool from_dev = srcptr && in_device_pool(srcptr);
   (void)ns::route_sync_point(queue, from_dev ? srcptr : nullptr, from_dev ? size : 0);
   if (!dstptr || !srcptr || !size) return;
+  if (wait_first && from_dev) {
+    (void)hipStreamSynchronize(static_cast<hipStream_t>(queue));
+    (void)ns::route_after_sync(queue);
+  }
   if (from_dev && !in_device_pool(dstptr)) touch_destination_while_queue_runs(dstptr, size, static_cast<hipStream_t>(queue));
   // (replayed tokens run on the plan's activations: the embeddings go there as well, the logits come from there — ns_route.cpp)
   void* twin = ns::route_twin_dst(dstptr, queue);
@@ -717,6 +721,11 @@ void bestla_device_memcpy(void* dstptr, const void* srcptr, size_t size, void* q
     ns::route_note_input(dstptr, size, queue);     // an evaluation's input: kept so that the evaluation can be issued again
   }
 }
+// The exported copy WITHOUT a wait of its own (ne_bestla.h:92): a caller that fetches results with it and bestla_device_sync gets no second chance behind
+// the wait — an evaluation that has to be run again (fp16 overflow, ns_route.h) must have been by the time its results are read.  A copy FROM device memory
+// therefore waits for the queue and lets the route look at the flag first; towards the device nothing changes.  (bestla_device_memcpy_sync, the reference's
+// only form, keeps its order: copy, deferred wait, copy again if need be.)
+void bestla_device_memcpy(void* dstptr, const void* srcptr, size_t size, void* queue) { device_memcpy_impl(dstptr, srcptr, size, queue, true); }
 static bool device_sync_impl(void* queue) {
   (void)ns_hip_lazy_flush();
   ns::route_time_mark(queue, 0);
@@ -729,13 +738,13 @@ void bestla_device_sync(void* queue) { (void)device_sync_impl(queue); }
 void bestla_device_memcpy_sync(void* dstptr, const void* srcptr, size_t size, void* queue) {
   static const bool timing = getenv("NS_ROUTE_TIMING") != nullptr;
   const auto t0 = std::chrono::steady_clock::now();
-  bestla_device_memcpy(dstptr, srcptr, size, queue);
+  device_memcpy_impl(dstptr, srcptr, size, queue, false);
   const bool again = device_sync_impl(queue);
   if (timing && size >= (size_t(8) << 20))
     fprintf(stderr, "route timing: bestla_device_memcpy_sync of %.1f MB took %.2f ms\n", size / 1e6,
             std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() / 1e3);
   if (again) {  // the evaluation this copy reads from was run again (fp16 overflow, ns_route.h): its results are fetched again
-    bestla_device_memcpy(dstptr, srcptr, size, queue);
+    device_memcpy_impl(dstptr, srcptr, size, queue, false);
     (void)hipStreamSynchronize(static_cast<hipStream_t>(queue));
     (void)ns::route_after_sync(queue);
   }
@@ -831,6 +840,7 @@ void bestla_device_load_storage(void* hoststor, void* devstor, void* deviceptr, 
   g_stats[4] += uint64_t(now_us() - t0);
   g_stats[5] = g_pending.size();
   g_have_pending.store(1);
+  ns::route_note_copy(queue);  // (uploads and re-layout kernels are on the queue: the next bestla_device_sync waits for them, it is not left to a later copy)
 }
 
 void ns_hip_device_load_stats(uint64_t out[6]) {

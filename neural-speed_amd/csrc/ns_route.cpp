@@ -163,7 +163,9 @@ struct Route {
   char* stash_mem = nullptr;
   size_t stash_cap = 0, stash_used = 0;
   bool stash_complete = true;  // false: an input of the evaluation could not be kept (it cannot be issued again from its start)
-  bool stash_stale = false;    // the stash belongs to an evaluation that has ended: the next input copy starts it over
+  bool stash_stale = false;    // the stash belongs to an evaluation that has ended: the next input copy starts it over — NOTHING ELSE (round 7)
+  bool stash_ended = false;    // ... and that evaluation is the one that ended LAST (it brought its inputs through the queue): it can be run again from them
+  bool tainted = false;        // device memory was freed while this evaluation's trace was open: the trace makes no plan and is not kept
   bool tm_prev_pending = false;
   int copies_pending = 0;      // copies issued on the queue since it was last waited for (a wait with none pending can be left to the next copy: route_defer_sync)
   long long win_t0 = 0, win_ops = 0, win_launches = 0, win_issue_us = 0;  // NS_ROUTE_TIMING: the last window that went out
@@ -310,8 +312,11 @@ RouteOp expected(const PlanOp& po, long long k) {
 
 // The evaluation's inputs are put back where the graph asked for them (Stash): segments of a plan run on the PLAN's activations, and a
 // token's own tensors sit only act_delta * k above those — inside memory the segments have written.
-int restore_inputs() {
-  if (R.stash_stale) return 0;  // (this evaluation brought no input through the queue)
+// `ended`: the evaluation has ended (route_after_sync runs it again) — its stash is stale by then, which only says that the NEXT input copy starts it over;
+// whether it holds that evaluation's inputs is stash_ended.  Round 6 asked stash_stale in both places and restored nothing behind an evaluation's end: a
+// REPLAYED token that was run again (fp16 overflow) read an input the plan's segments had written over.
+int restore_inputs(bool ended = false) {
+  if (ended ? !R.stash_ended : R.stash_stale) return 0;  // (this evaluation brought no input through the queue)
   for (const Stash& si : R.stash)
     if (hipMemcpyAsync(si.dst, R.stash_mem + si.off, si.bytes, hipMemcpyDeviceToDevice, R.st) != hipSuccess) {
       set_error("device route: restoring an evaluation's input failed");
@@ -1205,7 +1210,7 @@ constexpr size_t kWindowMax = 16384;  // ops; a window this long goes out withou
 // an evaluation that ended is evaluated AGAIN from its first launch, plainly (no plan, the fp32 kernels): R.cur holds its ops, the stash its inputs
 int reevaluate() {
   if (!R.stash_complete || R.cur.empty()) return -1;
-  if (restore_inputs() != 0) return -1;
+  if (restore_inputs(true) != 0) return -1;
   R.launched = 0;
   return flush_window(nullptr, 0);
 }
@@ -1312,6 +1317,7 @@ int route_sync_point(void* stream, const void* src, size_t bytes) {
       R.cur.clear();
       R.last_replayed = true;
       R.tm_replayed = true;
+      R.stash_ended = !R.stash_stale;
       R.stash_stale = R.tm_prev_pending = true;
       if (R.bails_in_a_row && R.kdone >= 8) R.bails_in_a_row = 0;
       if (R.ev_pending) {
@@ -1327,13 +1333,15 @@ int route_sync_point(void* stream, const void* src, size_t bytes) {
     if (flush_window(src, bytes) != 0) rc = -1;
     // the evaluation ends here (its trace is complete): a plan is made from two consecutive agreeing ones
     stat(1);
-    if (!R.have_plan && rc == 0 && enabled()) {
+    if (!R.have_plan && rc == 0 && enabled() && !R.tainted) {
       if (R.plan_pause > 0 && R.cur.size() == R.prev.size()) R.plan_pause--;
       else if (R.plan_pause == 0) (void)make_plan();
     }
     R.prev.swap(R.cur);
     R.cur.clear();
+    if (R.tainted) R.prev.clear(), R.tainted = false;  // (a free inside the evaluation: its ops may name memory that is gone)
     R.launched = 0;
+    R.stash_ended = !R.stash_stale;
     R.stash_stale = R.tm_prev_pending = true;
   }
   return rc;
@@ -1444,8 +1452,15 @@ void route_note_input(void* dst, size_t bytes, void* stream) {
   if (t_in_exec || !r || !dst || !bytes) return;
   t_R = r;
   if (!R.cur.empty() || R.pos != 0) return;  // (cannot happen: a copy is a synchronisation point, which ends the trace)
-  if (R.stash_stale) R.stash.clear(), R.stash_used = 0, R.stash_complete = true, R.stash_stale = false;
-  if (bytes > (size_t(64) << 20)) return;  // (a model part being uploaded, not an evaluation's input: nothing an evaluation writes over)
+  if (R.stash_stale) R.stash.clear(), R.stash_used = 0, R.stash_complete = true, R.stash_stale = R.stash_ended = false;
+  constexpr size_t kStashMax = size_t(64) << 20;
+  if (bytes > kStashMax) return;  // (a model part being uploaded, not an evaluation's input: nothing an evaluation writes over)
+  // The stash keeps what arrives directly IN FRONT of an evaluation.  Copies that together pass the largest single input it keeps are a load as well (the
+  // reference's loader copies tensor by tensor, model_files.h:1523; a session's caches): what is kept so far is let go and the stash starts over with this
+  // copy — an evaluation writes over its activations, which the copies directly in front of it fill, not over weights or cache rows it does not rewrite with
+  // the same values.  (Round 6 kept everything since the process began in a buffer that doubled, gave up once that asked for more than 512 MB and left a
+  // first evaluation that overflowed with its inf / nan.)
+  if (((R.stash_used + 255) & ~size_t(255)) + bytes > kStashMax) R.stash.clear(), R.stash_used = 0, R.stash_complete = true;
   const size_t need = ((R.stash_used + 255) & ~size_t(255)) + bytes;
   if (need > R.stash_cap) {  // grows; what this evaluation has kept so far moves along
     char* bigger = nullptr;
@@ -1469,14 +1484,23 @@ void route_note_input(void* dst, size_t bytes, void* stream) {
   R.stash.push_back(Stash{dst, bytes, off});
   R.stash_used = off + bytes;
 }
-void route_invalidate() {  // device memory is being freed: no captured launch, no recorded op may outlive it
+// device memory is being freed: no captured launch, no recorded op may outlive it — and none may be LOST (round 7: round 6 cleared the window with its ops
+// not launched yet, and dropped the plan under a token whose first segments had run on the plan's activations).  What has been handed over goes out first:
+// a token under verification falls back (it is issued again at the addresses it asked for, as when it deviates), the window is flushed.  The open trace
+// stays — the evaluation goes on behind the free and ends as one evaluation — but makes no plan and is not kept for the next one.
+void route_invalidate() {
   if (t_in_exec) return;
   Route* keep = t_R;
   for (Route* r : g_routes) {
     t_R = r;
+    if (R.have_plan && R.pos > 0) (void)bail_out();
+    if (!R.cur.empty()) {
+      (void)flush_window(nullptr, 0);
+      R.tainted = true;
+    }
     drop_plan();
-    R.cur.clear(), R.prev.clear();
-    R.launched = 0;
+    R.prev.clear();
+    R.stash_ended = false;  // (`prev` is gone: nothing to run again)
   }
   t_R = keep;
 }

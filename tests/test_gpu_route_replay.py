@@ -32,6 +32,7 @@ def _api(L):
     L.bestla_device_load_storage.argtypes = [vp, vp, vp, vp]
     L.bestla_device_f32f32_forward.argtypes = [vp, vp, vp, i, i, i, i, i, vp, vp]
     L.bestla_device_memcpy_sync.argtypes = [vp, vp, sz, vp]
+    L.bestla_device_memcpy.argtypes = [vp, vp, sz, vp]
     L.bestla_device_sync.argtypes = [vp]
     L.ns_hip_device_storage_release.argtypes = [vp]
     L.ns_hip_lazy_rms_norm.argtypes = [i, i, C.c_float, vp, vp, vp]
@@ -248,9 +249,14 @@ def test_two_device_contexts_alternating_tokens_keep_separate_plans(L, pkg, nso)
 NL = 2  # decoder layers of the second stream
 
 
-def _run_layers(L, nso, blobs, gam, xs, replay, nctx=NCTX, pos0=0, cache0=None, hkv=HEADS, poke=None):
+def _run_layers(L, nso, blobs, gam, xs, replay, nctx=NCTX, pos0=0, cache0=None, hkv=HEADS, poke=None, fetch="memcpy_sync", hook=None, preload_mb=0):
     """NL decoder layers WITH the attention node and the model's last norm + output projection: the shape in which the plan carries RMS norms
-    across launches (ns_route.cpp link_norms).  Positions pos0, pos0 + 1, ... of caches made for nctx positions (cache0: their initial contents).  Returns (outputs per token, K caches, V caches, route statistics)."""
+    across launches (ns_route.cpp link_norms).  Positions pos0, pos0 + 1, ... of caches made for nctx positions (cache0: their initial contents).  Returns (outputs per token, K caches, V caches, route statistics).
+    fetch: how a token's output is fetched — "memcpy_sync" (the reference's form) or "memcpy+sync" (bestla_device_memcpy, then bestla_device_sync).
+    hook = (token, where, fn): fn(L, q) is called at that token — "mid": between the two layers' ops, "end": after the last forward and in front of the token's
+    bestla_device_sync.  preload_mb: in front of the first token that many MB go into a 60 MB device buffer by bestla_device_memcpy_sync, 60 MB at a time (a
+    loader's copies)."""
+    assert fetch in ("memcpy_sync", "memcpy+sync") and (hook is None or hook[1] in ("mid", "end"))
     _api(L)
     vp, i = C.c_void_p, C.c_int
     L.ns_hip_mha_f32_device_layout.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, C.c_float, i, vp]
@@ -277,6 +283,12 @@ def _run_layers(L, nso, blobs, gam, xs, replay, nctx=NCTX, pos0=0, cache0=None, 
         kcs.append(kc), vcs.append(vc)
     dg = L.bestla_device_malloc(D * f4, q)
     L.bestla_device_memcpy_sync(dg, nso.ptr(gam), gam.nbytes, q)
+    if preload_mb:
+        piece = np.full(60 << 20, 7, np.uint8)
+        dload = L.bestla_device_malloc(piece.nbytes, q)
+        slices.append(dload)
+        for done in range(0, preload_mb << 20, piece.nbytes):
+            L.bestla_device_memcpy_sync(dload, nso.ptr(piece), min(piece.nbytes, (preload_mb << 20) - done), q)
     outs = []
     vec = lambda n: (_ll(n, 1, 1, 1), _ll(4, 4 * n, 4 * n, 4 * n))
     ne, nb = vec(D)
@@ -326,13 +338,21 @@ def _run_layers(L, nso, blobs, gam, xs, replay, nctx=NCTX, pos0=0, cache0=None, 
             L.bestla_device_f32f32_forward(pp, nso.ptr(stors["w2"]), pt2, 1, D, FF, FF, D, None, q)
             assert L.ns_hip_binary_nd_f32(0, pt2, pr, po, ne, nb, ne, nb, nb, q) == 0
             px = po
+            if hook is not None and hook[:2] == (tok, "mid") and il == 0:
+                hook[2](L, q)
         pfn, pfh, plog = alloc(D), alloc(D), alloc(FF)
         assert L.ns_hip_lazy_rms_norm(1, D, 1e-5, px, pfn, q) == 0
         assert L.ns_hip_lazy_mul(pfn, dg, pfh, ne, nb, ne, nb, nb, q) == 0
         L.bestla_device_f32f32_forward(pfh, nso.ptr(stors["w1"]), plog, 1, FF, D, D, FF, None, q)  # (the gate matrix stands in for an output projection)
+        if hook is not None and hook[:2] == (tok, "end"):
+            hook[2](L, q)
         L.bestla_device_sync(q)
         out = np.zeros(FF, np.float32)
-        L.bestla_device_memcpy_sync(nso.ptr(out), plog, out.nbytes, q)
+        if fetch == "memcpy_sync":
+            L.bestla_device_memcpy_sync(nso.ptr(out), plog, out.nbytes, q)
+        else:
+            L.bestla_device_memcpy(nso.ptr(out), plog, out.nbytes, q)
+            L.bestla_device_sync(q)
         outs.append(out)
     caches = []
     for c in kcs + vcs:
