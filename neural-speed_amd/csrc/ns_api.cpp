@@ -341,14 +341,25 @@ struct DevBuf {
 // |scale| to [2^5, 2^6).  |code - zp| <= 383, so scaled weights stay below 2^15 (no overflow however large the
 // original weights are), and only groups more than 2^-19 below the largest one drop under fp16's normal range — bits
 // far beneath the 1e-3 budget relative to the output.  Powers of two change no rounding inside the normal range.
-void set_gemm_scale_range(ns_weight* w, uint32_t smax_bits) {
+// fp8 weights: the fp16 operand is code value * scale, and a code value is up to 480 (E4M3: 2^-7 .. 1.875 * 2^8) or 57344 (E5M2:
+// 2^-15 .. 1.75 * 2^15; exponent field 31 is refused at load) — the largest |scale| goes to [2^6, 2^7) (480 * 2^7 = 61440) or to
+// [2^-1, 1), both below fp16's 65504.  `low_scales` (launch_scale_spread with gemm_f8_scale_drop below): some group's scale would
+// leave fp16's normal range under that factor — the weight then stays on the first-generation GEMM (ns_weight::g2_ok).
+int gemm_f8_scale_top(uint32_t qtype) { return qtype == DT_F8_E5M2 ? 0 : 7; }
+// fp32 scales: every scale * g2_pre stays a NORMAL fp16 number (>= 2^-14: the product code * scale is then rounded once, 2^-12
+// relative, like the integer formats').  E8M0 scales are powers of two, exact as fp16 subnormals as well: down to 2^-20, where a
+// group's largest code (>= 2^8) still lies 12 bits above fp16's subnormal step of 2^-24.
+int gemm_f8_scale_drop(uint32_t qtype, uint32_t src_scale_dt) { return gemm_f8_scale_top(qtype) + (src_scale_dt == DT_F8_E8M0 ? 20 : 14); }
+void set_gemm_scale_range(ns_weight* w, uint32_t smax_bits, bool low_scales = false) {
   w->g2_pre = w->g2_post = 1.f;
+  w->g2_ok = !(w->kind == WK_F8 && low_scales);
   float smax;
   memcpy(&smax, &smax_bits, 4);
   if (!(smax > 0.f)) return;
   int e;
   frexpf(smax, &e);           // smax = f * 2^e, f in [0.5, 1)
-  int shift = 6 - e;          // smax * 2^shift in [2^5, 2^6)
+  int shift = (w->kind == WK_F8 ? gemm_f8_scale_top(w->qtype) : 6) - e;  // smax * 2^shift in [2^5, 2^6) (fp8: see above)
+  if (shift > 100 || shift < -100) w->g2_ok = w->kind != WK_F8;  // (fp8 has no headroom for a clamped factor)
   if (shift > 100) shift = 100;
   if (shift < -100) shift = -100;
   w->g2_pre = ldexpf(1.f, shift);
@@ -444,11 +455,12 @@ ns_weight* weight_from_device_sections(const BlobView& v_in, const uint8_t* dq, 
   if (ok) {
     ra.flags = dinfo.p + 1;
     ok = hip_ok(launch_repack(ra, w, st), "repack") && (add_native_planes(ra, w, st), true) &&
-         hip_ok(launch_scale_absmax(ds, v.s_bytes / (dt_bits(v.scale_dt) / 8), v.scale_dt, dinfo.p, st), "scale range") &&
+         hip_ok(launch_scale_absmax(ds, v.s_bytes / (dt_bits(v.scale_dt) / 8), v.scale_dt, dinfo.p, st, v.cstep, int(v.n)), "scale range") &&
+         (w->kind != WK_F8 || hip_ok(launch_scale_spread(ds, v.s_bytes / (dt_bits(v.scale_dt) / 8), v.scale_dt, gemm_f8_scale_drop(w->qtype, v.scale_dt), dinfo.p, st, v.cstep, int(v.n)), "scale spread")) &&
          hip_ok(hipMemcpyAsync(info, dinfo.p, 8, hipMemcpyDeviceToHost, st), "load info D2H") &&
          hip_ok(hipStreamSynchronize(st), "sync after repack");
   }
-  if (ok && info[1]) {
+  if (ok && (info[1] & 1)) {
     set_error("F8_E5M2 blob holds codes with exponent field 31 (beyond the reference quantizer's max_norm and fp16)");
     ok = false;
   }
@@ -456,7 +468,7 @@ ns_weight* weight_from_device_sections(const BlobView& v_in, const uint8_t* dq, 
     ns_hip_weight_free(w);
     return nullptr;
   }
-  set_gemm_scale_range(w, info[0]);
+  set_gemm_scale_range(w, info[0], (info[1] & 2) != 0);
   return w;
 }
 
@@ -609,8 +621,8 @@ int forward_impl(const float* dA, const ns_weight* w, float* dC, int m, int lda,
   if (!dA || !dC) {
     // fp16-only activations (the producer wrote its shadow only) and / or an fp16-only output (the consumer is this library's next
     // GEMM): the tiled kernel multiplies fp16 activations as they are and can leave the fp32 store out (round 5)
-    if (w->shuf || ref_int8_for(w) || link || w->kind == WK_F8) {
-      set_error("forward: fp16-only activations / outputs need a weight the tiled kernel takes as is (no act-order shuffle, no int8-reference mode, no fp8)");
+    if (w->shuf || ref_int8_for(w) || link || !gemm3_takes(w)) {
+      set_error("forward: fp16-only activations / outputs need a weight the tiled kernel takes as is (no act-order shuffle, no int8-reference mode; fp8 with the g3_f8 switch on and group scales within its range rule)");
       return -1;
     }
     SmallMArgs a{};
@@ -687,13 +699,14 @@ int forward_impl(const float* dA, const ns_weight* w, float* dC, int m, int lda,
   //   32000 x 4096 (lm_head)   8 rows 39.8 -> 32.1, 16 rows 53.4 -> 32.6   (4 rows: 28.9 vs 32.1, stays)
   //   11008 x 4096             16 rows 17.2 -> 16.7, 17 rows 33.0 -> 17.5, 64 rows 44.8 -> 20.8
   //   4096 x 11008             16 rows 24.1 -> 19.7 (12 rows level),  4096 x 4096: 33 rows 15.8 -> 13.4 (below: level or behind)
-  // fp8 weights stay on the old rule (first-generation GEMM only).  NS_TILED_MIN_M: diagnostics (A-B runs).
+  // fp8 weights keep the old rule up to 64 rows (streaming / first-generation kernels) and take the tiled kernel from 65 (launch_gemm2
+  // refuses them below, docs/kernels/gemm3.md).  NS_TILED_MIN_M: diagnostics (A-B runs).
   static const int tiled_env = getenv("NS_TILED_MIN_M") ? atoi(getenv("NS_TILED_MIN_M")) : 0;
   // Up to 16 rows every call stays on the streaming kernels all the same: their accumulation is exact in fp32 (3e-5 from the
   // fp64 product of the fp16-rounded activations, tests/test_gpu_fullsize.py), the tiled kernel rounds scaled weights to fp16
   // (2e-4), and a decode step's numerics should not depend on the shape of the matrix.
   const int tiled_from = tiled_env > 0 ? tiled_env : tiled_from_rows(w);
-  const bool wide_tiled = m >= tiled_from && w->kind != WK_F8 && !getenv("NS_SMALLM_MAX");
+  const bool wide_tiled = m >= tiled_from && (w->kind != WK_F8 || (m > 64 && gemm3_takes(w))) && !getenv("NS_SMALLM_MAX");
   const bool small = !wide_tiled && (m <= 16 || (m <= small_max && (staging <= 140e6 || getenv("NS_SMALLM_MAX") != nullptr)));
   // fp32 activations, several rows, many column tiles: one conversion pass to fp16 (about 2 us) halves what every
   // workgroup of the streaming kernel stages (14336 x 4096 at 16 rows: 39 -> 24 us; at 8 rows: 25 -> 18 us)
@@ -748,7 +761,8 @@ int qkv_rope_route_forward_m(const float* dA, const void* dA16, const ns_weight*
   if (!have_device()) return -1;
   const ns_weight* ws[3] = {wq, wk, wv};
   if (!wq || !wk || !wv || !dA || !cq || !ck || !cv || !rope || m <= 16) return -2;
-  bool one = !ref_int8_for(wq) && wq->kind != WK_F8;
+  // (fp8 weights from 65 rows: the separate launches the caller keeps below that are the ones that served such a window before)
+  bool one = !ref_int8_for(wq) && (wq->kind != WK_F8 || (m > 64 && gemm3_takes(wq) && gemm3_takes(wk) && gemm3_takes(wv)));
   for (int i = 0; i < 3; i++)
     one &= ws[i]->k == wq->k && ws[i]->kind == wq->kind && ws[i]->blocksize == wq->blocksize && ws[i]->scale_dt == wq->scale_dt && ws[i]->asym == wq->asym &&
            ws[i]->qtype == wq->qtype && !ws[i]->shuf && !ws[i]->load_failed;
@@ -947,7 +961,8 @@ ns_weight* ns_hip_weight_load_async(const void* host_blob, void* dst, uint64_t d
   uint32_t* dinfo = g_staging.info + 2 * (g_staging.next++ % kInfoRing);
   ra.flags = dinfo + 1;
   bool ok = hip_ok(hipMemsetAsync(dinfo, 0, 8, st), "memset") && hip_ok(launch_repack(ra, w, st), "repack") &&
-            (add_native_planes(ra, w, st), true) && hip_ok(launch_scale_absmax(ds, v.s_bytes / (dt_bits(v.scale_dt) / 8), v.scale_dt, dinfo, st), "scale range") &&
+            (add_native_planes(ra, w, st), true) && hip_ok(launch_scale_absmax(ds, v.s_bytes / (dt_bits(v.scale_dt) / 8), v.scale_dt, dinfo, st, v.cstep, int(v.n)), "scale range") &&
+            (w->kind != WK_F8 || hip_ok(launch_scale_spread(ds, v.s_bytes / (dt_bits(v.scale_dt) / 8), v.scale_dt, gemm_f8_scale_drop(w->qtype, v.scale_dt), dinfo, st, v.cstep, int(v.n)), "scale spread")) &&
             hip_ok(hipMemcpyAsync(pinned_info, dinfo, 8, hipMemcpyDeviceToHost, st), "load info D2H");
   if (ok && v.shuf_bytes)
     ok = hip_ok(hipMalloc((void**)&w->shuf, v.shuf_bytes), "hipMalloc(shuffle)") &&
@@ -964,12 +979,12 @@ int ns_hip_weight_finish_load(ns_weight* w, const uint32_t* info) {
   if (!w || !info) return -1;
   if (!w->load_pending) return 0;  // loaded synchronously (double-quantised scales): nothing to finish
   w->load_pending = false;
-  if (info[1]) {
+  if (info[1] & 1) {  // (bit 1: an fp8 weight whose scale spread keeps it off the tiled GEMM — set_gemm_scale_range)
     w->load_failed = true;
     set_error("F8_E5M2 blob holds codes with exponent field 31 (beyond the reference quantizer's max_norm and fp16)");
     return -1;
   }
-  set_gemm_scale_range(w, info[0]);
+  set_gemm_scale_range(w, info[0], (info[1] & 2) != 0);
   return 0;
 }
 
@@ -1162,6 +1177,10 @@ int ns_hip_set_tuning(const char* key, int value) {
     set_gemm3_wide(value);
     return 0;
   }
+  if (key && !strcmp(key, "g3_f8")) {  // fp8 weights on the tiled prefill GEMM (1, default) or as before it took them (0); -1: NS_G3_F8 / default
+    set_gemm3_f8(value);
+    return 0;
+  }
   if (key && !strcmp(key, "g3_bm")) {
     set_gemm3_bm(value);
     return 0;
@@ -1308,7 +1327,7 @@ int ns_hip_fusion_qkv_rope_forward_x(const float* dA, const void* dA16, const ns
   }
   const ns_weight* ws[3] = {wq, wk, wv};
   if (m > 16) {  // prefill size (round 5): the tiled GEMM's fused-QKV launch carries the epilogue; k / v optionally to the cache only
-    bool one = !ref_int8_for(wq) && !link && wq->kind != WK_F8;
+    bool one = !ref_int8_for(wq) && !link && gemm3_takes(wq) && gemm3_takes(wk) && gemm3_takes(wv);
     for (int i = 0; i < 3; i++)
       one &= ws[i]->k == wq->k && ws[i]->kind == wq->kind && ws[i]->blocksize == wq->blocksize && ws[i]->scale_dt == wq->scale_dt &&
              ws[i]->asym == wq->asym && ws[i]->qtype == wq->qtype && !ws[i]->shuf && !ws[i]->load_failed;
@@ -1323,7 +1342,7 @@ int ns_hip_fusion_qkv_rope_forward_x(const float* dA, const void* dA16, const ns
       if (e != hipErrorNotSupported) return hip_ok(e, "qkv+rope GEMM launch") ? 0 : -1;
     }
     if (getenv("NS_ROPE_GEMM_DEBUG")) fprintf(stderr, "qkv+rope at prefill size refused: one format %d, m %d, k %d, n %d %d %d, head_size %d, ldc %d\n", int(one), m, wq->k, wq->n, wk->n, wv->n, rope->head_size, ldc);
-    set_error("qkv+rope at prefill size: needs three weights of one integer / f4 format, plain whole-head RoPE, head_size a multiple of 4, matrix widths multiples of 128, 16-byte aligned outputs and no norm link");
+    set_error("qkv+rope at prefill size: needs three weights of one format the tiled kernel takes (integer, f4, or fp8 with the g3_f8 switch on), plain whole-head RoPE, head_size a multiple of 4, matrix widths multiples of 128, 16-byte aligned outputs and no norm link");
     return -1;
   }
   bool same = !ref_int8_for(wq) && m <= 16 && dA16;
@@ -1456,7 +1475,9 @@ int ns_hip_fusion_ffn3_gateup_x(const float* dA, const void* dA16, const ns_weig
   // GEMM size (round 5): ONE launch of the tiled kernel on gate / up tile pairs — act(A W1) * (A W3) is formed in registers, so
   // neither tmp1 nor an fp32 tmp2 has to exist (each is written only if the caller hands a pointer: the reference's graph treats
   // both as scratch, ne_layers.c:2573-2576); before, W1 wrote tmp1 (fp32), W3 read it back and wrote tmp2 (fp32 + fp16)
-  if (same && !ref8 && !link && seq > 16 && (seq > 64 || seq >= tiled_from_rows(w1)) && w1->kind != WK_F8 && (dTmp2 || dTmp2_16) &&
+  // (fp8 weights: from 65 rows; from 17 like the rest only where nothing else serves the call — fp16-only activations)
+  const bool f8_rows = w1->kind != WK_F8 || (gemm3_takes(w1) && gemm3_takes(w3) && (seq > 64 || !dA));
+  if (same && !ref8 && !link && seq > 16 && (seq > 64 || seq >= tiled_from_rows(w1)) && f8_rows && (dTmp2 || dTmp2_16) &&
       smallm_supported(w1, seq)) {
     SmallMArgs a{};
     a.a = dA, a.a16 = dA16, a.lda = fin, a.m = seq, a.ldc = fmid, a.nseg = 2;
@@ -1548,7 +1569,7 @@ int ns_hip_fusion_ffn3_forward_h(const float* dA, const void* dA16, const ns_wei
   const int fmid = w1->n;
   // GEMM size, no fp32 tmp2 asked for: the intermediate exists as fp16 only (the down projection multiplies fp16 activations anyway);
   // it lives in the caller's dTmp2_16 or in per-stream scratch
-  if (!dTmp2 && seq > 16 && !w2->shuf && !ref_int8_for(w2) && w2->kind != WK_F8 && fmid % 64 == 0) {
+  if (!dTmp2 && seq > 16 && !w2->shuf && !ref_int8_for(w2) && (w2->kind != WK_F8 || (gemm3_takes(w2) && (seq > 64 || !dA))) && fmid % 64 == 0) {
     void* t16 = dTmp2_16 ? dTmp2_16 : stream_scratch(st, size_t(seq) * fmid * 2, 8);
     if (t16 && ns_hip_fusion_ffn3_gateup_h(dA, dA16, w1, w3, dTmp1, nullptr, t16, seq, act, stream) == 0) {
       SmallMArgs a{};

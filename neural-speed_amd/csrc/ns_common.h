@@ -120,6 +120,9 @@ struct ns_weight {
   // gemm2 (ns_gemm.hip) rounds `scale * g2_pre` to fp16 and multiplies its accumulators by g2_post = 1 / g2_pre: a
   // power of two chosen at load time from the largest |scale| so that dequantised weights stay in fp16's normal range
   float g2_pre = 1.f, g2_post = 1.f;
+  // fp8 weights (a code spans 2^-7 .. 480 or 2^-15 .. 57344 before its scale): false when no power of two keeps the largest scaled code
+  // finite in fp16 and the smallest groups' largest codes above fp16's subnormals at once — such a weight stays on the first-generation GEMM
+  bool g2_ok = true;
   // activation shuffle of GPTQ act-order blobs (ShuffleIndices, bestla_storage.h:704): int[k] on the device, own
   // allocation; the forward gathers A'[j] = A[shuf[j]] before the GEMM (prologue_a.h:322-330).  null = none.
   int* shuf = nullptr;
@@ -143,7 +146,11 @@ hipError_t launch_repack(const RepackArgs& a, ns_weight* w, hipStream_t st);
 hipError_t launch_dq8_expand(const uint8_t* codes, const float* dq, const float* lut, float* out, int rows, int cstep, int n, int dq_blocksize,
                              uint32_t dq_last, hipStream_t st);
 // max |scale| over a reference scale section (finite values only), as fp32 bits, atomically max-ed into *out_bits
-hipError_t launch_scale_absmax(const void* scales, size_t count, uint32_t scale_dt, uint32_t* out_bits, hipStream_t st);
+// (cstep > 0: the section is rows of cstep entries, the first n of each are the weight's columns — the padding behind them is skipped)
+hipError_t launch_scale_absmax(const void* scales, size_t count, uint32_t scale_dt, uint32_t* out_bits, hipStream_t st, int cstep = 0, int n = 0);
+// fp8 weights (F32 / F8_E8M0 scale sections), after launch_scale_absmax on the same stream: ORs 2 into info[1] when a non-zero scale lies
+// below 2^(e - drop), info[0] = the largest |scale| = f * 2^e with f in [0.5, 1)
+hipError_t launch_scale_spread(const void* scales, size_t count, uint32_t scale_dt, int drop, uint32_t* info, hipStream_t st, int cstep = 0, int n = 0);
 
 struct GemmSeg {
   const ns_weight* w;
@@ -237,6 +244,11 @@ void set_i8_tile(int tile);     // ns_i8ref.hip: workgroup tile of i8mfma2_kerne
 void set_i8_mfma_gen(int gen);  // ns_i8ref.hip: 2 = i8mfma2_kernel for nibble containers (default), 1 = i8mfma_kernel everywhere
 void set_gemm3_min_m(int m);  // ns_gemm.hip: rows from which gemm3_kernel is used (0 = default)
 void set_gemm3_wide(int on);  // ns_gemm.hip: 1 the cross-wave output epilogue of gemm3_kernel's 1 x 4 wave tiles, 0 (default) the per-wave one, -1 = environment / default
+void set_gemm3_f8(int on);  // ns_gemm.hip: 1 (default) fp8 weights take gemm3_kernel at prompt size, 0 they stay on the first-generation kernel, -1 = NS_G3_F8 / default
+bool gemm3_f8_on();
+// may this weight's prompt-size GEMMs run on the tiled kernel (ns_gemm.hip)?  Every integer / f4 weight; fp8 ones while "g3_f8" is on and the
+// load found range factors for them (ns_weight::g2_ok)
+bool gemm3_takes(const ns_weight* w);
 void set_gemm3_bm(int bm);  // ns_gemm.hip: force gemm3_kernel's row-tile height (tests / A-B runs); 0 = automatic  // ns_attn.hip: context-split rule of the decode attention kernel
 void set_decode_waves(int nw);  // 0 = by shape
 int decode_waves(int grid, int ks, bool dual);  // waves per workgroup of a decode launch (both kernel generations)

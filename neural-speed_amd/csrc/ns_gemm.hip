@@ -77,6 +77,7 @@ struct Gemm2Params {
                       // to fp16 and the accumulators by spost on the way out, so that weights with very small or very
                       // large magnitudes stay inside fp16's normal range (1, 1 for ordinary LLM weights)
   F4Lut lut;
+  F8Consts f8;  // gemm3_kernel, fp8 codes: the encoding's two conversion constants (cvt_f8x8, ns_dev.h) — E4M3 and E5M2 share one instantiation
   // gemm3_kernel, fused QKV (ip_fusion_qkv.cpp:84-86 at GEMM size): up to three matrices of one K and one format side by
   // side along the column blocks; nseg <= 1: the single matrix above
   int nseg;
@@ -355,11 +356,15 @@ __global__ __launch_bounds__(256, (BM == 256 ? 2 : 3)) void gemm3_kernel(const G
   constexpr int NIW = SQ ? 4 : 2;               // column tiles (16 wide) per wave
   constexpr int APW = BM / 32;                   // A DMA pieces (8 rows each) per wave and chunk
   constexpr int kStage = BM * kG3KC * 2;         // bytes of one A stage
-  constexpr bool B8 = KIND == WK_INT8;          // 8-bit codes: a record is 64 deep, two per 128-deep superstep
+  constexpr bool B8 = kind_is_8bit(KIND);       // 8-bit codes (int8, fp8): a record is 64 deep, two per 128-deep superstep
   constexpr int NJ = B8 ? 2 : 4;                // 32-deep slices per record
   constexpr int RPS = B8 ? 2 : 1;               // records per superstep (128 deep = chunks 2u, 2u + 1)
   constexpr int SBYTES = SPS * (SK == SK_F32 ? 4 : 2);
   constexpr bool M32 = kG3M32;
+  static_assert(KIND != WK_F8 || (SK == SK_F32 && !ASYM && !M32 && !TALL), "fp8 weights: fp32 device scales, no zero points, the 16x16x32 loop");
+  // VALU instructions the scheduler is asked to place behind each MFMA of a slice (interleave): the next slice's dequantisation is about
+  // 18 VALU per B fragment for int8 / int4 codes and 34 for fp8 ones (cvt_f8x8: 7 per code pair + the packed multiply), for MI MFMAs
+  constexpr int VPM = KIND == WK_F8 ? 4 : 2;
   constexpr int MB = MI / 2, NP = NIW / 2;       // 32-row / 32-column fragments of the wave tile (M32)
   using Corr = CorrRaw<SPS, SK, ASYM>;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -381,6 +386,8 @@ __global__ __launch_bounds__(256, (BM == 256 ? 2 : 3)) void gemm3_kernel(const G
   _Float16* const c16_out = p.nseg > 1 ? p.seg_c16[sg] : p.c16;
   // the weight's fp16-range factors (scales are multiplied by spre before the fp16 product, results by spost): per matrix in a fused launch
   const float spre_ = p.nseg > 1 ? p.seg_spre[sg] : p.spre, spost_ = p.nseg > 1 ? p.seg_spost[sg] : p.spost;
+  // gate/up pairs: the up matrix (column tile ni = 1 of the wave) has range factors of its own
+  const float spre_up = DUAL ? p.seg_spre[1] : spre_, spost_up = DUAL ? p.seg_spost[1] : spost_;
   const int tile0 = DUAL ? bnl * 4 + w : bnl * kG3Tiles + wn * NIW, row0 = bm * BM;  // DUAL: the tile of BOTH matrices (output columns 16 tile0 ..)
 
   const Rsrc rq = p.nseg > 1 ? make_rsrc(p.seg_codes[sg], p.seg_codes_bytes[sg]) : make_rsrc(p.codes, p.codes_bytes);
@@ -601,10 +608,14 @@ __global__ __launch_bounds__(256, (BM == 256 ? 2 : 3)) void gemm3_kernel(const G
       } else if constexpr (KIND == WK_INT8) {
         const _Float16 zo = (_Float16)(-1152.f - zp[js]);
         v = cvt_i8x8(b.q[ni][4 * h + 2 * jj], b.q[ni][4 * h + 2 * jj + 1], half2_t{zo, zo});
+      } else if constexpr (KIND == WK_F8) {
+        // exact bit-level conversion of the reference's encoding (no zero, no subnormals, no NaN: NOT the hardware's OCP fp8); E5M2's
+        // exponent-field-0 codes become fp16 subnormals, which the packed multiply below and the MFMA both keep (fp16 denormals are on)
+        v = cvt_f8x8(b.q[ni][4 * h + 2 * jj], b.q[ni][4 * h + 2 * jj + 1], p.f8);
       } else {
         v = cvt_f4x8(b.q[ni][js], p.lut);
       }
-      const _Float16 sh = (_Float16)(sc[js] * spre_);
+      const _Float16 sh = (_Float16)(sc[js] * (DUAL && ni ? spre_up : spre_));
       bf[ni] = v * half8_t{sh, sh, sh, sh, sh, sh, sh, sh};
     }
   };
@@ -780,12 +791,12 @@ __global__ __launch_bounds__(256, (BM == 256 ? 2 : 3)) void gemm3_kernel(const G
       mma(af, bf0, T_{}, 0, 1, [&](int mi) {
         if (mi < APW) issue_a_piece(c0 + 1, 1, mi);
       });
-      interleave(std::integral_constant<int, 2>{}, T_{}, T_{});
+      interleave(std::integral_constant<int, VPM>{}, T_{}, T_{});
       __builtin_amdgcn_sched_barrier(0);
       // slice 1 multiplies while slice 2's B fragments are prepared (its A image is behind the next barrier)
       dequant(breg, std::integral_constant<int, 2>{}, bf0);
       mma(af, bf1, F_{}, 0, 0, nothing);
-      interleave(std::integral_constant<int, 2>{}, F_{}, F_{});
+      interleave(std::integral_constant<int, VPM>{}, F_{}, F_{});
       __builtin_amdgcn_sched_barrier(0);
       // ---- chunk 2u + 1 (A stage 1) ----
       if (more1) {
@@ -797,7 +808,7 @@ __global__ __launch_bounds__(256, (BM == 256 ? 2 : 3)) void gemm3_kernel(const G
         mma(af, bf0, T_{}, 1, 1, [&](int mi) {
           if (mi < APW) issue_a_piece(c0 + 2, 0, mi);
         });
-        interleave(std::integral_constant<int, 2>{}, T_{}, T_{});
+        interleave(std::integral_constant<int, VPM>{}, T_{}, T_{});
         __builtin_amdgcn_sched_barrier(0);
         mma(af, bf1, F_{}, 0, 0, nothing);
       }
@@ -872,7 +883,7 @@ __global__ __launch_bounds__(256, (BM == 256 ? 2 : 3)) void gemm3_kernel(const G
           for (int ni = 0; ni < NIW; ni++)
 #pragma unroll
             for (int r = 0; r < 4; r++)
-              parkw[(mi * 16 + 4 * g + r) * WROW + w * PC + ni * 16 + nn] = acc[4 * hh + mi][ni][r] * spost_;
+              parkw[(mi * 16 + 4 * g + r) * WROW + w * PC + ni * 16 + nn] = acc[4 * hh + mi][ni][r] * (DUAL && ni ? spost_up : spost_);
         __syncthreads();
         if (p.diag == 1) continue;
         const int rb = row0 + hh * 64 + w * 16;  // this wave's 16 rows of the half
@@ -1512,7 +1523,7 @@ static hipError_t launch_gemm2_k(const Gemm2Params& p, bool asym, dim3 grid, siz
 template <int KIND, int SPS, int SK, int BM, bool TALL = false, bool DUAL = false>
 static hipError_t launch_gemm3_k(const Gemm2Params& p, bool asym, dim3 grid, hipStream_t st) {
   // A stages + the B stage of this format: records, scale rows, zero-point rows of 8 column tiles for one superstep
-  constexpr int rps = KIND == WK_INT8 ? 2 : 1;
+  constexpr int rps = kind_is_8bit(KIND) ? 2 : 1;
   constexpr int sbytes = SPS * (SK == SK_F32 ? 4 : 2);
   // (the epilogue parks 64 rows x (wave columns + 4) floats per wave over the stage memory: the 64-row tile's stages alone are
   // smaller than that)
@@ -1534,7 +1545,7 @@ static hipError_t launch_gemm3_k(const Gemm2Params& p, bool asym, dim3 grid, hip
     }
     return e;
   };
-  if constexpr (KIND == WK_F4) {
+  if constexpr (KIND == WK_F4 || KIND == WK_F8) {
     (void)asym;
     return go(gemm3_kernel<KIND, SPS, SK, false, BM, TALL, DUAL>);
   } else {
@@ -1614,6 +1625,18 @@ static hipError_t launch_gemm3_s(const Gemm2Params& p, uint32_t scale_dt, bool a
   return launch_gemm3_k<KIND, SPS, SK_BF16, 256>(p, asym, grid, st);
 }
 
+// fp8 weights: device scales are always fp32 (E8M0 is expanded at load), no zero points — five instantiations per SPS
+template <int SPS>
+static hipError_t launch_gemm3_f8(const Gemm2Params& p, dim3 grid, hipStream_t st) {
+  if (p.dual) {
+    if (p.bm3 == 64) return launch_gemm3_k<WK_F8, SPS, SK_F32, 64, false, true>(p, false, grid, st);
+    return launch_gemm3_k<WK_F8, SPS, SK_F32, 128, false, true>(p, false, grid, st);
+  }
+  if (p.bm3 == 64) return launch_gemm3_k<WK_F8, SPS, SK_F32, 64>(p, false, grid, st);
+  if (p.bm3 == 128) return launch_gemm3_k<WK_F8, SPS, SK_F32, 128>(p, false, grid, st);
+  return launch_gemm3_k<WK_F8, SPS, SK_F32, 256>(p, false, grid, st);
+}
+
 template <int KIND, int SPS>
 static hipError_t launch_gemm2_s(const Gemm2Params& p, uint32_t scale_dt, bool asym, dim3 grid, size_t lds,
                                  hipStream_t st) {
@@ -1631,6 +1654,14 @@ static int gemm3_min_m() {
   const int v = g_g3_min_m.load();
   return v > 0 ? v : kG3MinM;
 }
+static std::atomic<int> g_g3_f8{-1};  // ns_hip_set_tuning("g3_f8", 0 / 1): -1 = NS_G3_F8 or the default (1)
+void set_gemm3_f8(int on) { g_g3_f8.store(on < 0 ? -1 : (on != 0)); }
+bool gemm3_f8_on() {
+  static const int env = getenv("NS_G3_F8") ? atoi(getenv("NS_G3_F8")) : 1;
+  const int v = g_g3_f8.load();
+  return (v >= 0 ? v : env) != 0;
+}
+bool gemm3_takes(const ns_weight* w) { return w && (w->kind != WK_F8 || (gemm3_f8_on() && w->g2_ok && w->scale_dt == DT_F32 && !w->asym && w->sps <= 2)); }
 void set_gemm3_bm(int bm) { g_g3_bm.store(bm == 64 || bm == 128 || bm == 256 || bm == 257 || bm == 258 ? bm : 0); }  // 257: 256-row tile, tall wave tiles; 258: the automatic choice without them (A-B runs)
 
 // hipErrorNotSupported = use the first-generation kernel (scratch allocation failed, sizes beyond 32-bit offsets ...)
@@ -1638,11 +1669,22 @@ hipError_t launch_gemm2(const SmallMArgs& a, hipStream_t st) {
   static const bool off = getenv("NS_GEMM_V1") != nullptr;  // diagnostics
   if (off) return hipErrorNotSupported;
   const ns_weight* w0 = a.seg[0].w;
-  // fp8 weights span 2^-15 .. 2^15 per code before their scale: they stay on the first-generation kernel, which
-  // applies the group scale to the fp32 MFMA result
-  if (w0->kind == WK_F8) return hipErrorNotSupported;
+  // fp8 weights span 2^-15 .. 2^15 per code before their scale: gemm3_kernel takes them when the load found a power of two that keeps
+  // every scaled code inside fp16 (ns_api.cpp set_gemm_scale_range) and the "g3_f8" switch is on; otherwise, and for the NS_GEMM3=0 / 2
+  // kernels, they stay on the first-generation kernel, which applies the group scale to the fp32 MFMA result.  Rows: a plain call (fp32
+  // activations in, fp32 result out, one matrix) of up to 64 rows stays on the kernels that served it before — the streaming kernel's
+  // and gen 1's exact-scale numerics, 3e-5 — and the forms only this kernel has (fp16-only operands, fused launches) start at 17
+  const bool f8 = w0->kind == WK_F8;
+  if (f8) {
+    static const int g3_mode_f8 = getenv("NS_GEMM3") ? atoi(getenv("NS_GEMM3")) : 1;
+    for (int i = 0; i < a.nseg; i++)
+      if (!a.seg[i].w || a.seg[i].w->kind != WK_F8 || !gemm3_takes(a.seg[i].w)) return hipErrorNotSupported;
+    const bool plain = a.nseg == 1 && !a.dual && !a.rope && a.a && a.seg[0].c;
+    if (g3_mode_f8 != 1 || kG3M32 || a.m < 17 || (plain && a.m <= 64)) return hipErrorNotSupported;
+  }
   Gemm2Params p;
   memset(&p, 0, sizeof(p));
+  if (f8) p.f8 = f8_consts(w0->qtype);
   p.m = a.m;
   p.k = w0->k;
   p.n = w0->n;
@@ -1698,12 +1740,13 @@ hipError_t launch_gemm2(const SmallMArgs& a, hipStream_t st) {
     if (a.nseg != 2 || !w || a.m < gemm3_min_m() || (p.lda16 & 7) != 0 || g3_off_env || a.d || kG3M32) return hipErrorNotSupported;
     if (w->k != w0->k || w->n != w0->n || w->kind != w0->kind || w->sps != w0->sps || w->scale_dt != w0->scale_dt || w->asym != w0->asym ||
         w->ksteps != w0->ksteps || w->qstride != w0->qstride || w->sstride != w0->sstride || w->zstride != w0->zstride ||
-        w->srows != w0->srows || w->g2_pre != w0->g2_pre || w->g2_post != w0->g2_post || w->qtype != w0->qtype ||
+        w->srows != w0->srows || w->qtype != w0->qtype ||
         w->codes_bytes != w0->codes_bytes || w->scales_bytes != w0->scales_bytes || w->zps_bytes != w0->zps_bytes)
       return hipErrorNotSupported;
     if (!p.c && !p.c16) return hipErrorInvalidValue;
     p.dual = 1;
     p.codes2 = w->codes, p.scales2 = w->scales, p.zps2 = w->zps;
+    p.seg_spre[1] = w->g2_pre, p.seg_spost[1] = w->g2_post;  // (the two matrices' largest scales need not share a binade)
     p.c2 = a.c2;
     p.nbn = (w0->ntiles + 3) / 4;
     p.cpx = (p.nbn + 7) / 8;
@@ -1723,6 +1766,9 @@ hipError_t launch_gemm2(const SmallMArgs& a, hipStream_t st) {
       case WK_INT8:
         if (w0->sps == 2) return launch_gemm3_s<WK_INT8, 2>(p, w0->scale_dt, w0->asym, grid3, st, false);
         return launch_gemm3_s<WK_INT8, 1>(p, w0->scale_dt, w0->asym, grid3, st, false);
+      case WK_F8:
+        if (w0->sps == 2) return launch_gemm3_f8<2>(p, grid3, st);
+        return launch_gemm3_f8<1>(p, grid3, st);
       default:
         switch (w0->sps) {
           case 4: return launch_gemm3_s<WK_F4, 4>(p, w0->scale_dt, w0->asym, grid3, st, false);
@@ -1790,7 +1836,7 @@ hipError_t launch_gemm2(const SmallMArgs& a, hipStream_t st) {
     // in a layer's sequence of GEMMs, steady state, choosing them by that rule gained nothing (986 vs 993 TFLOPS,
     // profiles/r03w_prefill_ab.txt) — not selected automatically
     p.tall3 = bm_env == 257 && w0->kind == WK_INT4;
-    p.bm3 = p.tall3 ? 256 : bm_env == 64 || bm_env == 128 || bm_env == 256 ? bm_env : a.m <= 64 ? 64 : (tall_tiles >= 1024 && w0->kind != WK_INT8 ? 256 : 128);  // 8-bit codes: the tall tile's LDS
+    p.bm3 = p.tall3 ? 256 : bm_env == 64 || bm_env == 128 || bm_env == 256 ? bm_env : a.m <= 64 ? 64 : (tall_tiles >= 1024 && !kind_is_8bit(w0->kind) ? 256 : 128);  // 8-bit codes: the tall tile's LDS
                                                                                             // footprint (81 KiB) leaves one workgroup per CU
     // outputs: the per-wave epilogue by default; the cross-wave one (ns_hip_set_tuning("g3_wide", 1) / NS_G3_WIDE=1) measured 2-8 % SLOWER
     // with both outputs on the 7B shapes at 2048 rows (profiles/r05b_gemm3_epilogue_ab.txt: 4096^2 100.4 vs 92.9 us, 11008 x 4096 208.2 vs
@@ -1835,12 +1881,15 @@ hipError_t launch_gemm2(const SmallMArgs& a, hipStream_t st) {
     } else if (w0->kind == WK_INT8) {
       if (w0->sps == 2) return launch_gemm3_s<WK_INT8, 2>(p, w0->scale_dt, w0->asym, grid3, st, deep);
       return launch_gemm3_s<WK_INT8, 1>(p, w0->scale_dt, w0->asym, grid3, st, deep);
+    } else if (f8) {
+      if (w0->sps == 2) return launch_gemm3_f8<2>(p, grid3, st);
+      return launch_gemm3_f8<1>(p, grid3, st);
     } else {
       NS_G3DISPATCH(WK_F4)
     }
 #undef NS_G3DISPATCH
   }
-  if (p.rope_on) return hipErrorNotSupported;  // (the RoPE epilogue is gemm3_kernel's)
+  if (p.rope_on || f8) return hipErrorNotSupported;  // (the RoPE epilogue and the fp8 conversion are gemm3_kernel's)
   const int nbm = (a.m + kG2BM - 1) / kG2BM;
   // few output tiles (M up to a few hundred rows): split K so that the launch still fills the chip
   p.ksplit = 1;

@@ -223,10 +223,13 @@ hipError_t launch_repack(const RepackArgs& a, ns_weight* w, hipStream_t st) {
   return hipGetLastError();
 }
 
-// largest finite |scale| of a reference scale section; positive fp32 bit patterns order like unsigned integers
-__global__ void scale_absmax_kernel(const uint8_t* __restrict__ s, size_t count, uint32_t scale_dt, uint32_t* out) {
+// largest finite |scale| of a reference scale section; positive fp32 bit patterns order like unsigned integers.  cstep > 0: rows of
+// cstep entries of which the first n are columns of the weight — the padding behind them is skipped (its zero BYTES are zero scales
+// in the float types but 2^0 as a shared exponent)
+__global__ void scale_absmax_kernel(const uint8_t* __restrict__ s, size_t count, uint32_t scale_dt, uint32_t* out, int cstep, int n) {
   uint32_t best = 0;
   for (size_t i = size_t(blockIdx.x) * blockDim.x + threadIdx.x; i < count; i += size_t(gridDim.x) * blockDim.x) {
+    if (cstep > 0 && int(i % size_t(cstep)) >= n) continue;
     uint32_t bits;
     if (scale_dt == DT_F8_E8M0) {
       bits = e8m0_bits(reinterpret_cast<const int8_t*>(s)[i]);
@@ -246,11 +249,34 @@ __global__ void scale_absmax_kernel(const uint8_t* __restrict__ s, size_t count,
   }
   if ((threadIdx.x & 63) == 0 && best) atomicMax(out, best);
 }
-hipError_t launch_scale_absmax(const void* scales, size_t count, uint32_t scale_dt, uint32_t* out_bits, hipStream_t st) {
+hipError_t launch_scale_absmax(const void* scales, size_t count, uint32_t scale_dt, uint32_t* out_bits, hipStream_t st, int cstep, int n) {
   if (!count) return hipSuccess;
   const unsigned blocks = unsigned(std::min<size_t>((count + 255) / 256, 1024));
   hipLaunchKernelGGL(scale_absmax_kernel, dim3(blocks), dim3(256), 0, st, static_cast<const uint8_t*>(scales), count,
-                     scale_dt, out_bits);
+                     scale_dt, out_bits, cstep, n);
+  return hipGetLastError();
+}
+
+// fp8 weights on the tiled GEMM (ns_gemm.hip): does any non-zero finite |scale| lie below 2^(e - drop), smax = f * 2^e with f in [0.5, 1)?
+// `info[0]` = the largest |scale| (scale_absmax_kernel, earlier on the same stream); bit 1 of info[1] is set when one does.
+__global__ void scale_spread_kernel(const uint8_t* __restrict__ s, size_t count, uint32_t scale_dt, int drop, uint32_t* info, int cstep, int n) {
+  const int e = int((info[0] >> 23) & 0xffu) - 126;
+  const int biased = e - drop + 127;
+  if (biased <= 0) return;  // the bound is below fp32's normal range
+  const uint32_t thr = uint32_t(biased) << 23;
+  bool low = false;
+  for (size_t i = size_t(blockIdx.x) * blockDim.x + threadIdx.x; i < count; i += size_t(gridDim.x) * blockDim.x) {
+    if (cstep > 0 && int(i % size_t(cstep)) >= n) continue;
+    uint32_t bits = scale_dt == DT_F8_E8M0 ? e8m0_bits(reinterpret_cast<const int8_t*>(s)[i]) : reinterpret_cast<const uint32_t*>(s)[i];
+    bits &= 0x7fffffffu;
+    low |= bits != 0 && bits < thr;
+  }
+  if (__any(low) && (threadIdx.x & 63) == 0) atomicOr(info + 1, 2u);
+}
+hipError_t launch_scale_spread(const void* scales, size_t count, uint32_t scale_dt, int drop, uint32_t* info, hipStream_t st, int cstep, int n) {
+  if (!count) return hipSuccess;
+  const unsigned blocks = unsigned(std::min<size_t>((count + 255) / 256, 1024));
+  hipLaunchKernelGGL(scale_spread_kernel, dim3(blocks), dim3(256), 0, st, static_cast<const uint8_t*>(scales), count, scale_dt, drop, info, cstep, n);
   return hipGetLastError();
 }
 

@@ -55,6 +55,7 @@ struct MoeParams {
   const float* d;
   int ldd;
   float lut[16];  // 4-bit float types: code -> value
+  int f8_e5m2;    // fp8 codes: 1 = E5M2, 0 = E4M3
 };
 
 // ---- prefill size (round 5): the token rows grouped by expert, ONE tiled GEMM per expert over its rows ----------------------------
@@ -99,9 +100,17 @@ __global__ void moe_scatter_epilogue_kernel(const float* __restrict__ cg, const 
   c[size_t(t) * ldc + col] = v;
 }
 
-template <int KIND>  // WK_INT4, WK_INT8 or WK_F4
+// the reference's fp8 value of a code (f8_to_fp32, kernel_ref.h:984-1002): +-2^(e - bias) * (1 + m / 2^mbits) for EVERY code
+__device__ __forceinline__ float moe_f8_value(uint32_t code, int e5m2) {
+  const int mbits = e5m2 ? 2 : 3, bias = e5m2 ? 15 : 7;
+  const int e = int((code & 0x7fu) >> mbits), m = int(code & ((1u << mbits) - 1u));
+  const float v = ldexpf(1.f + float(m) / float(1 << mbits), e - bias);
+  return (code & 0x80u) ? -v : v;
+}
+
+template <int KIND>  // WK_INT4, WK_INT8, WK_F4 or WK_F8
 __global__ __launch_bounds__(kMoeThreads) void moe_gemv_kernel(const MoeParams p) {
-  constexpr int NJ = KIND == WK_INT8 ? 2 : 4;
+  constexpr int NJ = kind_is_8bit(KIND) ? 2 : 4;
   extern __shared__ __attribute__((aligned(16))) unsigned char moe_smem[];
   __shared__ float red[kMoeWaves][16];
   __shared__ float lut_s[16];
@@ -166,6 +175,9 @@ __global__ __launch_bounds__(kMoeThreads) void moe_gemv_kernel(const MoeParams p
         if constexpr (KIND == WK_INT8) {
           const uint32_t word = i < 4 ? xw[2 * j] : xw[2 * j + 1];
           wv = float(int(int8_t((word >> (8 * (i & 3))) & 255u))) - zb;
+        } else if constexpr (KIND == WK_F8) {
+          const uint32_t word = i < 4 ? xw[2 * j] : xw[2 * j + 1];
+          wv = moe_f8_value((word >> (8 * (i & 3))) & 255u, p.f8_e5m2);
         } else {
           const uint32_t code = (xw[j] >> (((i & 1) << 4) + ((i >> 1) << 2))) & 15u;  // nibble i at bit {0,16,4,20,...}
           if constexpr (KIND == WK_F4)
@@ -237,7 +249,13 @@ static int mul_mat_id_grouped(const float* dA, const int32_t* dIds, int ids_stri
                               int ldc, int epilogue, const float* dD, int ldd, hipStream_t st) {
   const ns_weight* w0 = g->experts[0];
   const int n_as = int(g->experts.size()), n = w0->n, k = w0->k;
-  if (w0->kind == WK_F8 || w0->shuf || (k % 64) != 0) return 1;
+  // fp8 experts: from 65 token rows, while the tiled kernel takes them ("g3_f8", the load's range rule) — every expert of the group
+  if (w0->shuf || (k % 64) != 0) return 1;
+  if (w0->kind == WK_F8) {
+    if (m <= 64) return 1;
+    for (const ns_weight* w : g->experts)
+      if (!gemm3_takes(w)) return 1;
+  }
   const int kpad = k;
   // scratch: ids column + permutation + validity (3 m ints), gathered fp16 rows [m + 1][k], raw products [m + 1][n] (one padding row: a
   // single-row group is launched with two rows — the tiled kernel's minimum — and its second row belongs to the NEXT group, launched later)
@@ -256,6 +274,9 @@ static int mul_mat_id_grouped(const float* dA, const int32_t* dIds, int ids_stri
   std::vector<int> count(n_as + 1, 0), off(n_as + 2, 0);
   for (int t = 0; t < m; t++) count[col[t] >= 0 && col[t] < n_as ? col[t] : n_as]++;
   for (int e = 0; e <= n_as; e++) off[e + 1] = off[e] + count[e];
+  if (w0->kind == WK_F8)  // (the tiled kernel takes fp8 weights from 17 rows: an expert with fewer keeps the call on the per-row kernels)
+    for (int e = 0; e < n_as; e++)
+      if (count[e] > 0 && count[e] < 17) return 1;
   std::vector<int> fill(off.begin(), off.end() - 1);
   for (int t = 0; t < m; t++) {
     const int e = col[t] >= 0 && col[t] < n_as ? col[t] : n_as;
@@ -330,8 +351,8 @@ ns_expert_group* ns_hip_expert_group_create(const ns_weight* const* experts, int
     }
     host[i] = {reinterpret_cast<const uint8_t*>(w->codes), static_cast<const uint8_t*>(w->scales), w->zps};
   }
-  if (w0->kind != WK_INT4 && w0->kind != WK_INT8 && w0->kind != WK_F4) {
-    set_error("expert group: S1..S8 and the 4-bit float types are supported (fp8 experts are not)");
+  if (w0->kind != WK_INT4 && w0->kind != WK_INT8 && w0->kind != WK_F4 && w0->kind != WK_F8) {
+    set_error("expert group: S1..S8, the 4-bit float types and fp8 are supported");
     return nullptr;
   }
   ns_expert_group* g = new ns_expert_group;
@@ -381,6 +402,7 @@ int ns_hip_mul_mat_id(const float* dA, const int32_t* dIds, int ids_stride, int 
   p.a = dA, p.lda = lda, p.c = dC, p.ldc = ldc;
   p.epilogue = epilogue, p.d = dD, p.ldd = ldd;
   for (int i = 0; i < 16; i++) p.lut[i] = w->lutf[i];
+  p.f8_e5m2 = w->qtype == DT_F8_E5M2 ? 1 : 0;
   const size_t lds = size_t(w->ksteps) * w->kstep_len * 2;
   if (lds > 60 * 1024) {
     set_error("mul_mat_id: K beyond 30720 is not supported by this first version");
@@ -402,7 +424,7 @@ int ns_hip_mul_mat_id(const float* dA, const int32_t* dIds, int ids_stride, int 
   // codes, the expert's base pointer picked from the table on the device — instead of this file's VALU loop (Mixtral shapes,
   // one token, 8 x {14336 x 4096, 4096 x 14336} int4: 169 us per MoE FFN layer with the loop, profiles/r04s_moe_mixtral_m1.json)
   static const int moe_gemv_rows = getenv("NS_MOE_GEMV_ROWS") ? atoi(getenv("NS_MOE_GEMV_ROWS")) : 8;
-  if (m <= moe_gemv_rows && w->single_span) {
+  if (m <= moe_gemv_rows && w->single_span && w->kind != WK_F8) {  // (fp8 experts: the loop below)
     bool all = true;
     for (int t = 0; t < m && all; t++) {
       MoeRoute route{g->table, dIds + size_t(t) * ids_stride + id, int(g->experts.size())};
@@ -424,6 +446,8 @@ int ns_hip_mul_mat_id(const float* dA, const int32_t* dIds, int ids_stride, int 
   const dim3 grid(w->ntiles, m), block(kMoeThreads);
   if (w->kind == WK_INT8)
     hipLaunchKernelGGL(moe_gemv_kernel<WK_INT8>, grid, block, lds, st, p);
+  else if (w->kind == WK_F8)
+    hipLaunchKernelGGL(moe_gemv_kernel<WK_F8>, grid, block, lds, st, p);
   else if (w->kind == WK_F4)
     hipLaunchKernelGGL(moe_gemv_kernel<WK_F4>, grid, block, lds, st, p);
   else

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Per-shape prefill GEMM throughput: Llama-2-7B shapes at M rows, int4 g32 (and int8 g32) weights, each shape timed
-alone.  Usage: scripts/gemm_shapes_bench.py [M] [int8]"""
+"""Per-shape prefill GEMM throughput: Llama-2-7B shapes at M rows, int4 g32 (int8 g32, or fp8 = E4M3 g32 with E8M0
+scales) weights, each shape timed alone.  Usage: scripts/gemm_shapes_bench.py [M] [int8 | fp8]"""
 import ctypes as C, json, os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -8,14 +8,15 @@ import __graft_entry__ as ge
 pkg = ge.load_package(); L = pkg.lib()
 torch.cuda.set_device(0)
 m = int(sys.argv[1]) if len(sys.argv) > 1 else 2048
-qt = pkg.S8 if (len(sys.argv) > 2 and sys.argv[2] == "int8") else pkg.S4
+fmt = sys.argv[2] if len(sys.argv) > 2 and sys.argv[2] in ("int8", "fp8") else "int4"
+qt, sdt, comp = {"int4": (pkg.S4, pkg.BF16, pkg.COMP_INT8), "int8": (pkg.S8, pkg.BF16, pkg.COMP_INT8), "fp8": (pkg.F8_E4M3, pkg.F8_E8M0, pkg.COMP_F32)}[fmt]
 st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
 res = {}
 for n, k in [(4096, 4096), (11008, 4096), (4096, 11008), (32000, 4096)]:
     w = torch.randn((n, k), device="cuda") * k ** -0.5
-    size = L.ns_BTLAGemmPackBSize(n, k, 32, qt, pkg.BF16, False, pkg.COMP_INT8, None)
+    size = L.ns_BTLAGemmPackBSize(n, k, 32, qt, sdt, False, comp, None)
     blob = torch.zeros(size, dtype=torch.uint8, device="cuda")
-    pkg.check(L.ns_hip_quant_pack_device(blob.data_ptr(), w.data_ptr(), n, k, k, 32, qt, pkg.BF16, False, pkg.COMP_INT8, True, st))
+    pkg.check(L.ns_hip_quant_pack_device(blob.data_ptr(), w.data_ptr(), n, k, k, 32, qt, sdt, False, comp, True, st))
     wt = pkg.Weight.from_device_blob(blob.data_ptr(), size, st)
     torch.cuda.synchronize()
     a = torch.randn((m, k), device="cuda"); a16 = a.half()
@@ -46,4 +47,4 @@ for n, k in [(4096, 4096), (11008, 4096), (4096, 11008), (32000, 4096)]:
     res["%dx%d" % (n, k)] = {"us": round(ms * 1e3, 1), "tflops": round(2.0 * m * n * k / ms / 1e9, 1),
                               "graph_us": round(gms * 1e3, 1), "graph_tflops": round(2.0 * m * n * k / gms / 1e9, 1)}
     del w, blob, a, a16, c, c16
-print(json.dumps({"m": m, "weights": "int8" if qt == pkg.S8 else "int4", "shapes": res}))
+print(json.dumps({"m": m, "weights": fmt, "shapes": res}))
