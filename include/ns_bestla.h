@@ -234,6 +234,10 @@ int ns_hip_get_compute_mode(void);
  *   "gv_nw"           waves per 16-column tile of the decode kernels (2 / 4 / 8 / 16), 0 = by shape (default); the
  *                     partial sums of a tile are added in wave order, so this selects the summation order
  *   "g3_min_m"        rows from which the tiled prefill GEMM is used inside its envelope (0 = default)
+ *   "moe_gemv_rows"   ns_hip_mul_mat_id: token rows up to which a call takes one decode-kernel launch per row (0 = default: NS_MOE_GEMV_ROWS
+ *                     in the environment, else 8; negative = never)
+ *   "moe_grouped_rows" ns_hip_mul_mat_id: token rows from which a call outside a capture groups its rows by expert on the host, one tiled
+ *                     GEMM per expert (0 = default: NS_MOE_GROUPED_ROWS in the environment, else 32; negative = never)
  * Returns 0, or -1 for an unknown key. */
 int ns_hip_set_tuning(const char* key, int value);
 /* Loads the code objects of the hot kernels (tiled GEMM, decode GEMV, attention, the operators between them) for the current device now instead of at the
@@ -609,16 +613,22 @@ int ns_hip_attn_set_head_partition(int global_head_num, int head_offset);
  * part-1 surface.  Here the ids stay on the device (they are the router's top-k output), so a decode step with experts
  * can be captured in one HIP graph:
  *     dC[t][:] = epi( dA[t][:] . W[ dIds[t * ids_stride + id] ],  dD[t][:] )        t = 0 .. m-1
- * An expert group is n_as weights of identical shape and format (S1..S8, NF4 / FP4); an id outside [0, n_as) — the
- * reference asserts — produces a zero product for that row.  fp16-activation numerics like every default forward.
+ * An expert group is n_as weights of identical shape and format (S1..S8, NF4 / FP4, FP8 E4M3 / E5M2); an id outside [0, n_as) —
+ * the reference asserts — produces a zero product for that row: dC[t] = epi(0, dD[t]) on every path (NS_EPI_ADD leaves dD[t],
+ * NS_EPI_ADD_GELU gelu(dD[t]), the others zero).  fp16-activation numerics like every default forward.
  * The `ffn_id_*` nodes (ne_layers.c:8053-8170) are three such calls (gate with NS_EPI_SILU, up with NS_EPI_MUL and
  * dD = gate output, down).
+ * A call is served by row count: up to "moe_gemv_rows" rows one decode-kernel launch per row, from "moe_grouped_rows" rows (outside a
+ * stream capture) the rows grouped by expert and one tiled GEMM per expert, otherwise — and wherever those two refuse — a per-row
+ * loop kernel (docs/kernels/other.md).  ns_hip_moe_stats (process-wide sums): calls served by [0] the grouped path, [1] the decode
+ * kernel, [2] the loop kernel; [3] grouped attempts that were not taken (the call then counts under [1] or [2] as well).
  * ---------------------------------------------------------------------------------------------- */
 typedef struct ns_expert_group ns_expert_group;
 ns_expert_group* ns_hip_expert_group_create(const ns_weight* const* experts, int n_as);
 void ns_hip_expert_group_free(ns_expert_group* g);
 int ns_hip_mul_mat_id(const float* dA, const int32_t* dIds, int ids_stride, int id, const ns_expert_group* g, float* dC,
                       int m, int lda, int ldc, int epilogue, const float* dD, int ldd, void* stream);
+void ns_hip_moe_stats(uint64_t out[4]);
 
 /* ----------------------------------------------------------------------------------------------
  * Part 5 — tensor-parallel all-reduce over peer-mapped HBM.  The decode-sized fast path of

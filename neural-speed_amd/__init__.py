@@ -170,6 +170,8 @@ def lib():
         L.ns_hip_expert_group_free.restype = None
         L.ns_hip_expert_group_free.argtypes = [vp]
         L.ns_hip_mul_mat_id.argtypes = [vp, vp, i, i, vp, vp, i, i, i, i, vp, i, vp]
+        L.ns_hip_moe_stats.restype = None
+        L.ns_hip_moe_stats.argtypes = [vp]
         L.ns_hip_p2p_create.restype = vp
         L.ns_hip_p2p_create.argtypes = [i, i, sz, vp]
         L.ns_hip_p2p_connect.argtypes = [vp, vp]

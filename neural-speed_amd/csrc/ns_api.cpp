@@ -1157,6 +1157,10 @@ int ns_hip_set_tuning(const char* key, int value) {
                      !strcmp(key, "gvs_table") ? 4 : 5, value);
     return 0;
   }
+  if (key && (!strcmp(key, "moe_gemv_rows") || !strcmp(key, "moe_grouped_rows"))) {  // row thresholds of ns_hip_mul_mat_id's paths; 0 = default, < 0 = off
+    set_moe_tuning(!strcmp(key, "moe_gemv_rows") ? 0 : 1, value);
+    return 0;
+  }
   if (key && !strcmp(key, "g3_min_m")) {
     set_gemm3_min_m(value);
     return 0;

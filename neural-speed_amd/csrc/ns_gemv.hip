@@ -115,7 +115,7 @@ struct GemvParams {
   const uint8_t* i8_corr;
   uint32_t i8_span, i8_nblk, i8_bshift;
   // expert-indexed launch (XV = 4, ns_hip_mul_mat_id at decode size): the weight base is table[*moe_id].codes — every expert of a
-  // group has the same shape and layout, so the offsets above hold for all of them; an id outside [0, moe_n) zeroes the row
+  // group has the same shape and layout, so the offsets above hold for all of them; an id outside [0, moe_n) gives epi(0, d)
   const MoeExpertRow* moe_table;
   const int32_t* moe_id;
   int moe_n;
@@ -262,12 +262,22 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
     tl = T - (sg == 0 ? 0u : (sg == 1 ? p.tb1 : p.tb2));
   } else if constexpr (MOE) {
     const int e = *p.moe_id;  // wave-uniform: scalar loads
-    if (e < 0 || e >= p.moe_n) {  // an out-of-range id zeroes its row (the reference would assert)
+    if (e < 0 || e >= p.moe_n) {  // an out-of-range id: a zero PRODUCT for the row (the reference would assert), through the epilogue of section 6
       const KArgs cz = late_args();
       const int colz = int(T) * 16 + nn;
       if (w == 0 && g == 0 && colz < cz->mat[0].n) {
-        cz->mat[0].c[colz] = 0.f;
-        if (cz->mat[0].c16) cz->mat[0].c16[colz] = (_Float16)0.f;
+        float v = 0.f;
+        const float dv = cz->d ? cz->d[colz] : 0.f;
+        switch (cz->epilogue) {
+          case 1: v = v + dv; break;
+          case 2: v = v * dv; break;
+          case 3: v = epi_gelu(v + dv); break;
+          case 4: v = epi_gelu(v); break;
+          case 5: v = epi_silu(v); break;
+          default: break;
+        }
+        cz->mat[0].c[colz] = v;
+        if (cz->mat[0].c16) cz->mat[0].c16[colz] = (_Float16)v;
       }
       return;
     }

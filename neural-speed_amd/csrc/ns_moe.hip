@@ -16,6 +16,7 @@
 // streaming loop with four records in flight per wave, not tuned like smallm_kernel.
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -244,6 +245,13 @@ struct ns_expert_group {
 using namespace ns;
 
 namespace ns {
+// row thresholds of ns_hip_mul_mat_id's three paths (ns_hip_set_tuning "moe_gemv_rows" / "moe_grouped_rows"): 0 = the environment variable
+// if set, else the built-in value; negative = that path is off
+static std::atomic<int> g_moe_gemv_rows{0}, g_moe_grouped_rows{0};
+void set_moe_tuning(int what, int value) { (what == 0 ? g_moe_gemv_rows : g_moe_grouped_rows).store(value); }
+// calls served by [0] the grouped path, [1] the decode kernel, [2] the loop kernel; [3] grouped attempts that returned "not taken" (ns_hip_moe_stats)
+static std::atomic<uint64_t> g_moe_stats[4];
+
 // 0 = done, -1 = error (set_error), 1 = not taken (the caller's per-row path serves the call)
 static int mul_mat_id_grouped(const float* dA, const int32_t* dIds, int ids_stride, int id, const ns_expert_group* g, float* dC, int m, int lda,
                               int ldc, int epilogue, const float* dD, int ldd, hipStream_t st) {
@@ -410,20 +418,26 @@ int ns_hip_mul_mat_id(const float* dA, const int32_t* dIds, int ids_stride, int 
   }
   hipStream_t st = (hipStream_t)stream;
   // prefill-sized calls: rows grouped by expert, one tiled GEMM per expert (see moe_gather_rows_kernel)
-  static const int grouped_from = getenv("NS_MOE_GROUPED_ROWS") ? atoi(getenv("NS_MOE_GROUPED_ROWS")) : 32;
+  static const int grouped_env = getenv("NS_MOE_GROUPED_ROWS") ? atoi(getenv("NS_MOE_GROUPED_ROWS")) : 32;
+  const int grouped_set = g_moe_grouped_rows.load();
+  const int grouped_from = grouped_set ? grouped_set : grouped_env;
   if (m >= grouped_from && grouped_from > 0) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     const bool capturing = hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
     (void)hipGetLastError();
     if (!capturing) {
       const int rc = mul_mat_id_grouped(dA, dIds, ids_stride, id, g, dC, m, lda, ldc, epilogue, dD, ldd, st);
+      if (rc == 0) g_moe_stats[0]++;
       if (rc <= 0) return rc;  // 0 done, -1 failed; 1: outside the tiled kernel's envelope — the per-row kernels below
+      g_moe_stats[3]++;
     }
   }
   // decode-sized calls: one launch of the decode kernel (ns_gemv.hip, XV = 4) per token row — LDS-DMA rings, MFMA on the raw
   // codes, the expert's base pointer picked from the table on the device — instead of this file's VALU loop (Mixtral shapes,
   // one token, 8 x {14336 x 4096, 4096 x 14336} int4: 169 us per MoE FFN layer with the loop, profiles/r04s_moe_mixtral_m1.json)
-  static const int moe_gemv_rows = getenv("NS_MOE_GEMV_ROWS") ? atoi(getenv("NS_MOE_GEMV_ROWS")) : 8;
+  static const int gemv_env = getenv("NS_MOE_GEMV_ROWS") ? atoi(getenv("NS_MOE_GEMV_ROWS")) : 8;
+  const int gemv_set = g_moe_gemv_rows.load();
+  const int moe_gemv_rows = gemv_set ? gemv_set : gemv_env;
   if (m <= moe_gemv_rows && w->single_span && w->kind != WK_F8) {  // (fp8 experts: the loop below)
     bool all = true;
     for (int t = 0; t < m && all; t++) {
@@ -441,7 +455,10 @@ int ns_hip_mul_mat_id(const float* dA, const int32_t* dIds, int ids_stride, int 
         return -1;
       }
     }
-    if (all) return 0;
+    if (all) {
+      g_moe_stats[1]++;
+      return 0;
+    }
   }
   const dim3 grid(w->ntiles, m), block(kMoeThreads);
   if (w->kind == WK_INT8)
@@ -457,7 +474,12 @@ int ns_hip_mul_mat_id(const float* dA, const int32_t* dIds, int ids_stride, int 
     set_error(std::string("mul_mat_id launch: ") + hipGetErrorString(e));
     return -1;
   }
+  g_moe_stats[2]++;
   return 0;
+}
+
+void ns_hip_moe_stats(uint64_t out[4]) {
+  for (int i = 0; i < 4; i++) out[i] = g_moe_stats[i].load();
 }
 
 }  // extern "C"
