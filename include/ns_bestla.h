@@ -350,7 +350,20 @@ int ns_hip_fusion_ffn3_gateup_x(const float* dA, const void* dA16, const ns_weig
  * positions n_past, n_past + 1, ...; fp16 shadow of A required.  The angles do not depend on the layer: cos_sin is the
  * table ns_hip_rope_cos_sin fills ONCE per token ([m][head_size / 2] pairs (cos, sin) * attn_factor, theta built by the
  * reference's sequential fp32 products), shared by every layer's launch.  Same arithmetic as ns_hip_rope_qkv_append
- * (bitwise).  m > 16 (round 5): the tiled GEMM carries the epilogue (see NS_QKV_ROPE_KV_CACHE_ONLY below); no norm link there. */
+ * (bitwise).  m > 16 (round 5): the tiled GEMM carries the epilogue (see NS_QKV_ROPE_KV_CACHE_ONLY below); no norm link there.
+ * NeoX pairs (mode 2: falcon, gptneox, qwen, gemma, phi, phi3, stablelm, baichuan, grok graphs): mode == 2 TOGETHER WITH the flag
+ * NS_QKV_ROPE_NEOX rotates the pairs (e, e + head_size / 2) over the whole head (n_dims == head_size, no YaRN); cos_sin is then the
+ * table of ns_hip_rope_cos_sin_mode(mode 2) - the flag is the caller's statement that it is: the NeoX branch applies freq_scale
+ * twice, a mode-0 table is silently wrong for it as soon as freq_scale != 1.  mode == 2 without the flag is refused as before
+ * (callers fall back to ns_hip_fusion_qkv_forward_x + ns_hip_rope_qkv_append), and so is the flag with any other mode.
+ *   m <= 16: head_size a multiple of 32; a workgroup of the decode kernel streams BOTH 16-column tiles of a pair (gemv_kernel's
+ *   GV_MSEGP mode), with the wave count of the two-launch form's QKV launch: bit-equal to ns_hip_fusion_qkv_forward_x with the same
+ *   norm link + ns_hip_rope_qkv_append(mode 2).  Exception: where the doubled rings do not fit LDS beside the staged rows (many
+ *   rows of a large K) the wave count is halved further and the result differs in fp32 summation order only.
+ *   m > 16: head_size 32, 64 or 128 (a head inside one 128-column block of the tiled GEMM; the partner column is read out of the
+ *   tile parked in LDS); other head sizes are refused - keep ns_hip_fusion_qkv_forward_h + ns_hip_rope_qkv_append for those.
+ *   Bit-equal to that two-launch form.  NS_QKV_ROPE_KV_CACHE_ONLY combines with it.
+ * Not in the epilogue: partial rotary (n_dims < head_size), YaRN / long-rope / GLM, and the replayed device route (llama, mode 0). */
 typedef struct ns_qkv_rope {
   void* kcache16;
   void* vcache16;
@@ -363,8 +376,14 @@ typedef struct ns_qkv_rope {
 /* Round 5: the same epilogue at PREFILL size (m > 16: the tiled GEMM, fused QKV as column segments; head_size a multiple of 4, matrix widths
  * multiples of 128, cos_sin rows for all m positions).  k and v then need not exist as fp32 tensors at all - the attention reads the cache: */
 #define NS_QKV_ROPE_KV_CACHE_ONLY 1 /* m > 16 only: k (rotated) and v go to the fp16 cache alone, dC[1] / dC[2] are not written */
+#define NS_QKV_ROPE_NEOX 2          /* with mode == 2: NeoX pairs (e, e + head_size / 2); cos_sin was filled by ns_hip_rope_cos_sin_mode(mode 2) */
 int ns_hip_rope_cos_sin(int m, int n_past, int n_dims, float freq_base, float freq_scale, float attn_factor,
                         float* dCosSin, void* stream);
+/* The table for RoPE mode `mode`: 0 = what ns_hip_rope_cos_sin writes; 2 (NeoX) = [m][n_dims / 2] (cos, sin) * attn_factor with the
+ * NeoX branch's angle arithmetic (ne_layers.c: theta_base = (n_past + i) * freq_scale, the sequential theta_scale products, then
+ * theta = freq_scale * theta_base - the reference's own double application).  Other modes: -1. */
+int ns_hip_rope_cos_sin_mode(int m, int n_past, int n_dims, int mode, float freq_base, float freq_scale, float attn_factor,
+                             float* dCosSin, void* stream);
 int ns_hip_fusion_qkv_rope_forward_x(const float* dA, const void* dA16, const ns_weight* wq, const ns_weight* wk,
                                      const ns_weight* wv, float* dC, int m, int lda, int ldc, const ns_norm_link* link,
                                      const ns_qkv_rope* rope, void* stream);

@@ -34,6 +34,8 @@ EPI_NONE, EPI_ADD, EPI_MUL, EPI_ADD_GELU, EPI_GELU, EPI_SILU = range(6)
 CORE_AUTO = -1
 # ne_attn_flags_t (neural_speed/core/ne_layers.h:65-72)
 ATTN_CAUSAL, ATTN_ALIBI8, ATTN_PREFER_FP32, ATTN_TANH30 = 1, 2, 4, 8
+# ns_qkv_rope::flags
+QKV_ROPE_KV_CACHE_ONLY, QKV_ROPE_NEOX = 1, 2
 
 
 class NormLink(C.Structure):
@@ -210,6 +212,7 @@ def lib():
         L.ns_hip_fusion_ffn3_gateup_x.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, vp, vp]
         L.ns_hip_norm_prep.argtypes = [i, i, vp, i, vp, vp, vp, i, vp]
         L.ns_hip_rope_cos_sin.argtypes = [i, i, i, f, f, f, vp, vp]
+        L.ns_hip_rope_cos_sin_mode.argtypes = [i, i, i, i, f, f, f, vp, vp]
         L.ns_hip_fusion_qkv_rope_forward_x.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, vp, vp, vp]
         L.ns_hip_fusion_ffn3_forward_h.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, vp]
         L.ns_hip_fusion_ffn3_gateup.argtypes = [vp, vp, vp, vp, vp, i, i, vp]

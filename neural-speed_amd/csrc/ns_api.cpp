@@ -730,6 +730,10 @@ int qkv_rope_route_forward(const float* dA, const void* dA16, const ns_weight* w
     set_error("route qkv+rope: prompt-sized calls go through qkv_rope_route_forward_m");
     return -1;
   }
+  if (rope && ((rope->flags & NS_QKV_ROPE_NEOX) || rope->mode != 0)) {
+    set_error("route qkv+rope: the replayed route is llama's, RoPE mode 0");
+    return -1;
+  }
   if (!wq || !wk || !wv || !dA16 || !cq || !ck || !cv || !rope) {
     set_error("route qkv+rope: null argument");
     return -1;
@@ -1313,6 +1317,23 @@ int ns_hip_rope_cos_sin(int m, int n_past, int n_dims, float freq_base, float fr
                 "rope table launch") ? 0 : -1;
 }
 
+int ns_hip_rope_cos_sin_mode(int m, int n_past, int n_dims, int mode, float freq_base, float freq_scale, float attn_factor,
+                             float* dCosSin, void* stream) {
+  // (the arguments are checked before the device is looked for: a refusal touches no device)
+  if (mode != 0 && mode != 2) {
+    set_error("rope_cos_sin_mode: the table exists for modes 0 (adjacent pairs) and 2 (NeoX)");
+    return -1;
+  }
+  if (m < 0 || n_past < 0 || n_dims < 2 || (n_dims & 1) || !dCosSin) {
+    set_error("rope_cos_sin_mode: invalid argument (n_dims even and >= 2)");
+    return -1;
+  }
+  if (mode == 0) return ns_hip_rope_cos_sin(m, n_past, n_dims, freq_base, freq_scale, attn_factor, dCosSin, stream);
+  if (!have_device()) return -1;
+  return hip_ok(launch_rope_cos_sin(m, n_past, n_dims, freq_base, freq_scale, attn_factor, dCosSin, (hipStream_t)stream, true),
+                "rope table launch") ? 0 : -1;
+}
+
 int ns_hip_fusion_qkv_rope_forward_x(const float* dA, const void* dA16, const ns_weight* wq, const ns_weight* wk,
                                      const ns_weight* wv, float* dC, int m, int lda, int ldc, const ns_norm_link* link,
                                      const ns_qkv_rope* rope, void* stream) {
@@ -1325,9 +1346,27 @@ int ns_hip_fusion_qkv_rope_forward_x(const float* dA, const void* dA16, const ns
     set_error("qkv+rope: the producer side of a norm link needs a single-matrix forward");
     return -1;
   }
-  if (rope->flags & ~NS_QKV_ROPE_KV_CACHE_ONLY) {  // (`flags` is the struct's newest field — a caller built against the older header passes what lay behind it)
+  if (rope->flags & ~(NS_QKV_ROPE_KV_CACHE_ONLY | NS_QKV_ROPE_NEOX)) {  // (`flags` is the struct's newest field — a caller built against the older header passes what lay behind it)
     set_error("qkv+rope: unknown bits in ns_qkv_rope::flags (zero the struct before filling it: the field was added in round 5)");
     return -1;
+  }
+  const bool neox = (rope->flags & NS_QKV_ROPE_NEOX) != 0;
+  if (neox != (rope->mode == 2)) {
+    // mode 2 without the flag: the unchanged contract (callers keep ns_hip_fusion_qkv_forward_x + ns_hip_rope_qkv_append); the flag says the table is mode 2's
+    set_error(neox ? "qkv+rope: NS_QKV_ROPE_NEOX goes with mode 2 only"
+                   : "qkv+rope: mode 2 (NeoX) needs NS_QKV_ROPE_NEOX in flags and the table of ns_hip_rope_cos_sin_mode(mode 2); other modes than 0 / 2 have no epilogue");
+    return -1;
+  }
+  if (neox) {
+    if (rope->n_dims != rope->head_size || rope->head_size < 32) {
+      set_error("qkv+rope (NeoX): whole-head rotation only (n_dims == head_size)");
+      return -1;
+    }
+    if (m <= 16 ? (rope->head_size % 32) != 0 : (rope->head_size != 32 && rope->head_size != 64 && rope->head_size != 128)) {
+      set_error(m <= 16 ? "qkv+rope (NeoX) at decode size: head_size must be a multiple of 32 (a workgroup streams both 16-column tiles of a pair)"
+                        : "qkv+rope (NeoX) at prefill size: head_size 32, 64 or 128 (a head inside one 128-column block); use ns_hip_fusion_qkv_forward_h + ns_hip_rope_qkv_append for this head size");
+      return -1;
+    }
   }
   const ns_weight* ws[3] = {wq, wk, wv};
   if (m > 16) {  // prefill size (round 5): the tiled GEMM's fused-QKV launch carries the epilogue; k / v optionally to the cache only

@@ -352,7 +352,7 @@ hipError_t launch_rope(const float* src, float* dst, int batch, int seq, int hea
 hipError_t launch_rope_glm(const float* src, float* dst, int batch, int seq, int heads, int head_size, int n_past, int n_dims,
                            bool skip, float freq_base, int prompt_size, const int* n_padding, hipStream_t st);
 hipError_t launch_rope_cos_sin(int m, int n_past, int n_dims, float freq_base, float freq_scale, float attn_factor,
-                               float* out, hipStream_t st);  // (n_past follows g_affine inside a route capture)
+                               float* out, hipStream_t st, bool neox = false);  // (n_past follows g_affine inside a route capture; neox: the mode-2 angles)
 // ns_api.cpp: the fused QKV + RoPE + cache-write launch of a replayed token: weights by ROLE, each result at its own tensor
 int qkv_rope_route_forward_m(const float* dA, const void* dA16, const ns_weight* wq, const ns_weight* wk, const ns_weight* wv, float* cq, float* ck, float* cv, int m,
                              int lda, int ldc, const ns_qkv_rope* rope, hipStream_t st);  // a window's prompt-sized form (-2: shape not taken)

@@ -66,7 +66,7 @@ struct Gemm2Params {
   // gemm3_kernel, fused QKV with RoPE(q, k) + kv-cache append as its epilogue (round 5; ns_qkv_rope at prefill size): segment 0 = q (rotated, fp32),
   // 1 = k (rotated -> fp16 cache [+ fp32]), 2 = v (-> fp16 cache [+ fp32]); cos / sin pairs per (row, pair) from the caller's table
   float seg_spre[3], seg_spost[3];  // fused QKV: each matrix's own factors (round 5: real models' q / k / v scales differ in range)
-  int rope_on, rope_hs, rope_npast;
+  int rope_on, rope_hs, rope_npast;  // rope_on: 1 = mode 0 (adjacent pairs), 2 = NeoX pairs (e, e + rope_hs / 2)
   const float2* rope_tab;
   _Float16 *rope_kc, *rope_vc;
   long long rope_csl, rope_chead;
@@ -960,6 +960,10 @@ __global__ __launch_bounds__(256, (BM == 256 ? 2 : 3)) void gemm3_kernel(const G
           for (int r = 0; r < 4; r++) park[(mi * 16 + 4 * g + r) * kRowF + ni * 16 + nn] = acc[4 * hh + mi][ni][r] * spost_;
     }
     // (LDS operations of one wave complete in order: no barrier between its own writes and reads)
+    // NeoX RoPE (rope_on == 2): a lane's partner columns, head_size / 2 further on or back, were parked by another lane and for
+    // head sizes 64 / 128 by another wave — workgroup barriers around the park, outside everything that depends on the row
+    const bool neox = p.rope_on == 2;
+    if (neox) __syncthreads();
     const int rbase = row0 + wm * 128 + hh * 64;
     if (p.diag == 1) continue;
     if (vec4) {
@@ -974,7 +978,24 @@ __global__ __launch_bounds__(256, (BM == 256 ? 2 : 3)) void gemm3_kernel(const G
         if (p.rope_on) {  // fused QKV + RoPE + cache append: rope_qkv_append_tab_kernel's arithmetic on the four columns (two adjacent pairs) of this lane
           typedef _Float16 half4r_t __attribute__((ext_vector_type(4)));
           const int hd = col / p.rope_hs, dcol = col - hd * p.rope_hs;
-          if (sg < 2) {
+          if (neox) {
+            // pairs (e, e + head_size / 2), head_size 32 / 64 / 128: the head lies inside this 128-column block, the partner four columns in
+            // the same parked row of wave (partner column / wave columns) — rope_qkv_append_tab_kernel's NeoX branch, products and sums rounded one by one
+            if (sg < 2) {
+#pragma clang fp contract(off)
+              const int half = p.rope_hs >> 1, e = dcol & (half - 1);
+              const int wc = (wn * kCols + (l % kLpr) * 4) ^ half;  // the partner's column in the workgroup tile
+              const float* pw = reinterpret_cast<const float*>(smem) + (w - wn + wc / kCols) * (64 * kRowF) + rl * kRowF + (wc % kCols);
+              const float4 o = *reinterpret_cast<const float4*>(pw);
+              const float2* tp = p.rope_tab + (size_t(row) * size_t(half) + size_t(e));
+              const float4 c01 = *reinterpret_cast<const float4*>(tp), c23 = *reinterpret_cast<const float4*>(tp + 2);
+              const bool lo = dcol < half;  // this lane holds x0 (and writes y0 = x0 c - x1 s) or x1 (y1 = x0 s + x1 c)
+              const float4 xa = lo ? v : o, xb = lo ? o : v;
+              const float a0 = xa.x * (lo ? c01.x : c01.y), a1 = xa.y * (lo ? c01.z : c01.w), a2 = xa.z * (lo ? c23.x : c23.y), a3 = xa.w * (lo ? c23.z : c23.w);
+              const float b0 = xb.x * (lo ? c01.y : c01.x), b1 = xb.y * (lo ? c01.w : c01.z), b2 = xb.z * (lo ? c23.y : c23.x), b3 = xb.w * (lo ? c23.w : c23.z);
+              v.x = lo ? a0 - b0 : a0 + b0, v.y = lo ? a1 - b1 : a1 + b1, v.z = lo ? a2 - b2 : a2 + b2, v.w = lo ? a3 - b3 : a3 + b3;
+            }
+          } else if (sg < 2) {
 #pragma clang fp contract(off)  // (rope_kernel's products and sums are rounded one by one: ns_quant.hip is built with -ffp-contract=off, this file is not)
             const float4 cs = *reinterpret_cast<const float4*>(p.rope_tab + (size_t(row) * size_t(p.rope_hs >> 1) + size_t(dcol >> 1)));
             const float x0 = v.x, x1 = v.y, x2 = v.z, x3 = v.w;
@@ -1015,6 +1036,7 @@ __global__ __launch_bounds__(256, (BM == 256 ? 2 : 3)) void gemm3_kernel(const G
         if (c16_out) c16_out[size_t(row) * p.ldc + col] = (_Float16)v;
       }
     }
+    if (neox && hh + 1 < MI / 4) __syncthreads();  // every wave has read its partners before the next half is parked
   }
 }
 
@@ -1801,7 +1823,8 @@ hipError_t launch_gemm2(const SmallMArgs& a, hipStream_t st) {
     p.nbn = bn0;
     if (a.rope) {  // RoPE + kv-cache append in the epilogue: plain whole-head RoPE, whole 128-column blocks per matrix, 16-byte fp32 / 8-byte cache stores
       const ns_qkv_rope& r = *a.rope;
-      const bool ok = a.nseg == 3 && r.mode == 0 && r.n_dims == r.head_size && r.head_size >= 4 && (r.head_size & 3) == 0 && r.kcache16 && r.vcache16 && r.cos_sin &&
+      const bool neox = (r.flags & NS_QKV_ROPE_NEOX) != 0;  // NeoX pairs: the head inside one 128-column block (32 / 64 / 128)
+      const bool ok = a.nseg == 3 && r.mode == (neox ? 2 : 0) && (!neox || (r.head_size >= 32 && 128 % r.head_size == 0)) && r.n_dims == r.head_size && r.head_size >= 4 && (r.head_size & 3) == 0 && r.kcache16 && r.vcache16 && r.cos_sin &&
                       r.n_past >= 0 && a.seg[0].w->n == r.heads * r.head_size && a.seg[1].w->n == r.heads_kv * r.head_size &&
                       a.seg[2].w->n == r.heads_kv * r.head_size && a.seg[0].w->n % 128 == 0 && a.seg[1].w->n % 128 == 0 && (a.ldc & 3) == 0 &&
                       (r.cache_step_sl & 3) == 0 && (r.cache_step_head & 3) == 0 && (reinterpret_cast<uintptr_t>(r.kcache16) & 7) == 0 &&
@@ -1810,7 +1833,7 @@ hipError_t launch_gemm2(const SmallMArgs& a, hipStream_t st) {
                       (!a.seg[2].c || (reinterpret_cast<uintptr_t>(a.seg[2].c) & 15) == 0) && !a.seg[0].c16 && !a.seg[1].c16 && !a.seg[2].c16 &&
                       a.epilogue == NS_EPI_NONE && !kG3M32;
       if (!ok) return hipErrorNotSupported;
-      p.rope_on = 1, p.rope_hs = r.head_size, p.rope_npast = r.n_past;
+      p.rope_on = neox ? 2 : 1, p.rope_hs = r.head_size, p.rope_npast = r.n_past;
       p.rope_tab = reinterpret_cast<const float2*>(r.cos_sin);
       p.rope_kc = static_cast<_Float16*>(r.kcache16), p.rope_vc = static_cast<_Float16*>(r.vcache16);
       p.rope_csl = r.cache_step_sl, p.rope_chead = r.cache_step_head;

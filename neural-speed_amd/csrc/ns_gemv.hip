@@ -67,8 +67,9 @@ struct GemvMat {
 };
 static_assert(sizeof(GemvMat) == 40, "GemvMat is addressed by index in the kernel-argument segment");
 
-// RoPE of q and k + kv-cache append as the epilogue of a fused QKV launch (ns_qkv_rope): adjacent-pair mode only, so
-// a pair always lies inside one 16-column tile
+// RoPE of q and k + kv-cache append as the epilogue of a fused QKV launch (ns_qkv_rope).  Adjacent pairs (mode 0) always lie
+// inside one 16-column tile (GV_MSEG).  NeoX pairs (e, e + head_size / 2) lie head_size / 32 tiles apart: a workgroup of the
+// pair mode (GV_MSEGP) streams both tiles, so no value is handed between workgroups
 struct GemvRope {
   _Float16* kc;
   _Float16* vc;
@@ -122,6 +123,9 @@ struct GemvParams {
   // native bit-plane records (PL = true: ns_weight::native): the format's bit width and the lanes of a record request
   // (record bytes / 16; the record's planes are contiguous, so a k-step is still ONE request)
   uint32_t pl_bits, pl_lanes;
+  // segment pairs (GV_MSEGP): 16-column tiles per half head (head_size / 32) — workgroup u of a matrix owns tiles
+  // t0 = head * 2 pair_tiles + j and t0 + pair_tiles (head = u / pair_tiles, j = u % pair_tiles); tb1 / tb2 count workgroups there
+  uint32_t pair_tiles;
   // ---- cold: read late, through the kernel-argument pointer (keeps them out of the streaming loop's SGPRs) ----
   GemvMat mat[3];
   float* c2;
@@ -170,9 +174,25 @@ __device__ __forceinline__ void wait_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-enum GemvMode { GV_PLAIN = 0, GV_DUAL = 1, GV_MSEG = 2 };
+// one NeoX pair: y0 = x0 c - x1 s, y1 = x0 s + x1 c with separately rounded products (no contraction into FMAs: the separate
+// operator's translation unit is built with -ffp-contract=off, this one is not)
+__device__ __forceinline__ void neox_rotate(float x0, float x1, float c, float s, float* y0, float* y1) {
+#pragma clang fp contract(off)
+  const float a = x0 * c, b = x1 * s, d = x0 * s, e = x1 * c;
+  *y0 = a - b;
+  *y1 = d + e;
+}
+
+enum GemvMode { GV_PLAIN = 0, GV_DUAL = 1, GV_MSEG = 2, GV_MSEGP = 3 };
 // MODE: one matrix / two matrices of one shape streamed in lockstep (gate/up, SiLU-mul epilogue) / several matrices
-// side by side along N (QKV).  Activations arrive as fp16 (the producer's shadow); fp32-only callers stay on
+// side by side along N (QKV) / the same with "segment pairs" (GV_MSEGP, XV = 1 only): the NeoX form of the RoPE epilogue.  A
+// workgroup streams the two tiles of a rotation pair (columns e and e + head_size / 2 of a head) with GV_DUAL's machinery — ring
+// slots alternating between the two streams, two accumulator sets — through the segment's ONE descriptor; lane (nn, g) ends
+// up with both elements of its pairs.  The grid is half the tile count; the wave count is the one the GV_MSEG launch of the
+// same weights and rows gets (decode_waves on the full tile count), so every column's fp32 sum is built in the same order as in
+// the two-launch form (fused QKV, then ns_hip_rope_qkv_append) and the results are the same bits.  Exception: the doubled
+// rings may not fit LDS beside the staged rows (many rows of a large K); the wave count is then halved further and the result
+// differs in fp32 summation order only.  Activations arrive as fp16 (the producer's shadow); fp32-only callers stay on
 // smallm_kernel, which converts while staging.
 // EXT: the launch carries an RMS norm (ns_norm_link) and / or the RoPE + kv-append epilogue (ns_qkv_rope).  A separate
 // instantiation, because even untaken these paths cost every launch 0.1-0.3 us (later argument fetch, longer cold
@@ -206,10 +226,12 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
   static_assert(!PL || ((KIND == WK_INT4 || KIND == WK_INT8) && !I8S && !MOE), "native planes: integer formats, fp16 numerics");
   static_assert(!I8S || KIND == WK_INT4 || KIND == WK_INT8, "integer weights only");
   constexpr uint32_t AEL = I8S ? 1u : 2u;  // bytes per staged activation element
-  constexpr bool DUAL = MODE == GV_DUAL, MSEG = MODE == GV_MSEG;
+  constexpr bool DUAL = MODE == GV_DUAL, MSEG = MODE == GV_MSEG, MSEGP = MODE == GV_MSEGP;
+  constexpr bool MSEGX = MSEG || MSEGP;  // the tile's matrix is selected among up to three
+  static_assert(!MSEGP || (EXT && !PL), "segment pairs exist for the RoPE epilogue only");
   constexpr int NJ = kind_is_8bit(KIND) ? 2 : 4;
   constexpr int KSTEP = NJ * 32;
-  constexpr int NQ = DUAL ? 2 : 1;
+  constexpr int NQ = (DUAL || MSEGP) ? 2 : 1;
   constexpr int PF = kGvPF;
   static_assert(PF % NQ == 0, "ring slots alternate between the two matrices");
   constexpr int SBYTES = SPS * (SK == SK_F32 ? 4 : 2);
@@ -225,9 +247,10 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
                  "s"(p.srows), "s"(p.srow_mul), "s"(p.srow_shift), "s"(p.m), "s"(p.k), "s"(p.lda), "s"(p.row_stride),
                  "s"(p.ring_off), "s"(p.ring_stride));
     if constexpr (DUAL) asm volatile("" ::"s"(p.wbase1), "s"(p.s_off1));
-    if constexpr (MSEG)
+    if constexpr (MSEGX)
       asm volatile("" ::"s"(p.tb1), "s"(p.tb2), "s"(p.mat[0].wbase), "s"(p.mat[1].wbase), "s"(p.mat[2].wbase), "s"(p.mat[0].s_off),
                    "s"(p.mat[1].s_off), "s"(p.mat[2].s_off));
+    if constexpr (MSEGP) asm volatile("" ::"s"(p.pair_tiles));
     if constexpr (ASYM) asm volatile("" ::"s"(p.z_off0), "s"(p.z_off1), "s"(p.zstride));
     if constexpr (PL) asm volatile("" ::"s"(p.pl_bits), "s"(p.pl_lanes));
   }
@@ -237,7 +260,7 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
   const int nn = l & 15, g = l >> 4;
   const uint32_t NW = 1u << p.nw_log2;
   const uint32_t ks = p.ks;
-  const uint32_t T = blockIdx.x;  // global tile (across the matrices of a fused QKV launch)
+  const uint32_t T = blockIdx.x;  // global tile (across the matrices of a fused QKV launch; GV_MSEGP: global tile pair)
 
   typedef __attribute__((address_space(3))) unsigned char* LdsPtr;
   // ---- descriptors: one per matrix over its whole allocation (codes, scales and zero points share the base) ----
@@ -250,7 +273,7 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
     rw[1] = make_rsrc(p.wbase1, 0x80000000u);
     so[0] = p.s_off0, so[1] = p.s_off1;
     zo[0] = p.z_off0, zo[1] = p.z_off1;
-  } else if constexpr (MSEG) {
+  } else if constexpr (MSEGX) {
     // all three matrices' bases and offsets come with the one batch of argument loads and are SELECTED (a lookup by
     // index in the argument segment would be a second, dependent round trip in front of the first weight request)
     sg = int(T >= p.tb1) + int(T >= p.tb2);
@@ -260,6 +283,10 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
     if constexpr (ASYM) zo[0] = sg == 0 ? p.mat[0].z_off : (sg == 1 ? p.mat[1].z_off : p.mat[2].z_off);
     else zo[0] = 0;
     tl = T - (sg == 0 ? 0u : (sg == 1 ? p.tb1 : p.tb2));
+    if constexpr (MSEGP) {  // pair u of the matrix -> its first tile (the second lies pair_tiles further on); both streams share the descriptor
+      tl += (tl / p.pair_tiles) * p.pair_tiles;
+      rw[1] = rw[0], so[1] = so[0], zo[1] = zo[0];
+    }
   } else if constexpr (MOE) {
     const int e = *p.moe_id;  // wave-uniform: scalar loads
     if (e < 0 || e >= p.moe_n) {  // an out-of-range id: a zero PRODUCT for the row (the reference would assert), through the epilogue of section 6
@@ -289,8 +316,13 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
     so[0] = p.s_off0;
     zo[0] = p.z_off0;
   }
-  const uint32_t tile_q = tl * ks * p.qstride;
-  const uint32_t tile_c = tl * p.srows;
+  uint32_t tile_q[NQ], tile_c[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; q++) {
+    const uint32_t tlq = (MSEGP && q) ? tl + p.pair_tiles : tl;
+    tile_q[q] = tlq * ks * p.qstride;
+    tile_c[q] = tlq * p.srows;
+  }
   const uint32_t voff_q = l * 16, voff_s = nn * SBYTES, voff_z = nn * SPS;  // the only per-lane address parts
   const I4Consts i4c = {0x000f000fu, 0x00f000f0u, 0x64006400u};
 
@@ -309,11 +341,11 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
     constexpr int slot = decltype(slot_c)::value;
     constexpr int q = slot % NQ;
 #if defined(__HIP_DEVICE_COMPILE__)  // (the host pass of hipcc cannot type-check this builtin and would drop the kernel stub)
-    const uint32_t crow = tile_c + ((s * p.srow_mul) >> p.srow_shift);
+    const uint32_t crow = tile_c[q] + ((s * p.srow_mul) >> p.srow_shift);
     const LdsPtr dst = ring + slot * SLOT;
     if (!PL || uint32_t(l) < p.pl_lanes)  // (a native record is shorter than 64 x 16 bytes)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rw[q], reinterpret_cast<__attribute__((address_space(3))) void*>(dst), 16, voff_q,
-                                               tile_q + s * p.qstride, 0, 2);
+                                               tile_q[q] + s * p.qstride, 0, 2);
     if (l < SBYTES)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rw[q], reinterpret_cast<__attribute__((address_space(3))) void*>(dst + 1024), 16,
                                                voff_q, so[q] + crow * p.sstride, 0, 2);
@@ -774,7 +806,7 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
 #pragma unroll
   for (int q = 0; q < NQ; q++) red[w * kRedWave + q * 64 + l] = acc[q];
   const KArgs cold = late_args();  // epilogue-only arguments: fetched here, not held through the streaming loop
-  const auto* mp = &cold->mat[MSEG ? sg : 0];  // indexed scalar loads
+  const auto* mp = &cold->mat[MSEGX ? sg : 0];  // indexed scalar loads
   const int ncols = mp->n;
   float* cbase = mp->c;
   _Float16* c16 = mp->c16;
@@ -799,7 +831,7 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
   float dvp[4] = {0.f, 0.f, 0.f, 0.f};
   float gam = 1.f;
   float2 cs[4];
-  int rope_head = 0, rope_e = 0;
+  int rope_head = 0, rope_e = 0, rope_half = 0;
   bool rope_on = false;
   _Float16* rope_cache = nullptr;
   float* rope_cell = nullptr;
@@ -837,6 +869,18 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
                                 : cold->rope.v32 + kk * cold->rope.v32_tok + rope_head * cold->rope.v32_head + rope_e * cold->rope.v32_dim;
         }
       }
+      if constexpr (MSEGP) {  // (always with the epilogue on: launch_gemv) col is the pair's first element, e < head_size / 2
+        const int hs = cold->rope.head_size;
+        rope_half = hs >> 1;
+        rope_head = col / hs;
+        rope_e = col - rope_head * hs;
+        if (sg < 2) {
+#pragma unroll
+          for (int rr = 0; rr < 4; rr++) cs[rr] = cold->rope.cos_sin[min(4 * g + rr, rows - 1) * rope_half + rope_e];
+        }
+        rope_sl = cold->rope.c_sl;
+        rope_cache = (sg == 1 ? cold->rope.kc : cold->rope.vc) + (long long)cold->rope.n_past * rope_sl + (long long)rope_head * cold->rope.c_head + rope_e;
+      }
       if (in_ssq) {  // wave 0 requested the pieces itself and has waited for all its requests (last record: vmcnt 0)
         const uint32_t ssq_ld = ((in_parts * 4u + 1023u) >> 10) << 8;  // floats per staged row
         const float* sl = reinterpret_cast<const float*>(smem + ssq_off);
@@ -869,6 +913,21 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
       const int row = 4 * g + rr;
       const bool ok = col_ok && row < p.m;
       float v = sum[0][rr] * rscale[rr];
+      if constexpr (MSEGP) {
+        // ne_rope (mode 2, NeoX) on q and k, then the kv-cache append: x0 = column e < head_size / 2, x1 = column e + head_size / 2 of the
+        // head; rope_qkv_append_kernel's arithmetic (ns_quant.hip), every product and sum rounded on its own
+        float y0 = v, y1 = sum[1][rr] * rscale[rr];
+        if (sg < 2) neox_rotate(v, y1, cs[rr].x, cs[rr].y, &y0, &y1);
+        if (ok) {
+          if (sg > 0) {
+            rope_cache[(long long)row * rope_sl] = (_Float16)y0;
+            rope_cache[(long long)row * rope_sl + rope_half] = (_Float16)y1;
+          }
+          cbase[size_t(row) * ldc + col] = y0;
+          cbase[size_t(row) * ldc + col + rope_half] = y1;
+        }
+        continue;
+      }
       if constexpr (MSEG && EXT) {
         if (rope_on) {
           // ne_rope (mode 0) on q and k, then the kv-cache append (models/llama/llama.cpp:232-262): the arithmetic of
@@ -1011,7 +1070,10 @@ static hipError_t launch_gemv_k(const GemvParams& p, int mode, int grid, int nw,
     if (attr != hipSuccess && lds > 64 * 1024) return attr;                                                     \
     hipLaunchKernelGGL(k, g, b, lds, st, p);                                                                    \
   }
-  if (mode == GV_DUAL)
+  if (mode == GV_MSEGP) {  // the NeoX RoPE epilogue's pair mode: one instantiation per format (XV = 1)
+    if (moe || i8s || a32 || !p.rope.on) return hipErrorNotSupported;
+    NS_GV_LAUNCH_E(GV_MSEGP, 1)
+  } else if (mode == GV_DUAL)
     NS_GV_LAUNCH(GV_DUAL)
   else if (mode == GV_MSEG)
     NS_GV_LAUNCH(GV_MSEG)
@@ -1102,7 +1164,8 @@ hipError_t launch_gemv(const SmallMArgs& a, hipStream_t st) {
   if (gemv_mode() == 0 || a.m < 1 || a.m > kGvMaxRows) return hipErrorNotSupported;
   const int nmat = a.nseg;  // matrices the launch touches (dual: 2)
   // bit-plane formats: every matrix of the launch has its native clone (same shapes and scales, shorter code records) -> stream those
-  bool planes = gemv_planes() && !a.i8 && !a.moe;
+  const bool neox = a.rope && (a.rope->flags & NS_QKV_ROPE_NEOX) != 0;  // the pair mode (GV_MSEGP) streams the widened records
+  bool planes = gemv_planes() && !a.i8 && !a.moe && !neox;
   for (int i = 0; i < nmat; i++)
     planes = planes && a.seg[i].w->native && a.seg[i].w->native->scale_dt != DT_F16 && a.seg[i].w->native->pl_bits == a.seg[0].w->native->pl_bits;
   auto pick = [&](const ns_weight* w) { return planes ? static_cast<const ns_weight*>(w->native) : w; };
@@ -1124,7 +1187,15 @@ hipError_t launch_gemv(const SmallMArgs& a, hipStream_t st) {
     p.mat[i] = GemvMat{wb[i], soff[i], zoff[i], tbeg[i], w->n, a.seg[i].c, static_cast<_Float16*>(a.seg[i].c16)};
   }
   const bool mseg = !a.dual && nmat > 1;
-  const int mode = a.dual ? GV_DUAL : (mseg ? GV_MSEG : GV_PLAIN);
+  const int mode = a.dual ? GV_DUAL : (mseg ? (neox ? GV_MSEGP : GV_MSEG) : GV_PLAIN);
+  if (neox) {  // whole pairs of tiles per head and matrix: a workgroup per pair
+    const int hs = a.rope->head_size;
+    if (!mseg || nmat != 3 || a.rope_route || hs < 32 || (hs % 32) != 0) return hipErrorInvalidValue;
+    for (int i = 0; i < nmat; i++)
+      if (p.mat[i].n % hs != 0 || uint32_t(p.mat[i].n) != 16u * uint32_t(pick(a.seg[i].w)->ntiles)) return hipErrorInvalidValue;
+    p.pair_tiles = uint32_t(hs / 32);
+    tbeg[1] /= 2, tbeg[2] /= 2;  // in workgroups (p.mat[].tile_begin is not read by the kernel)
+  }
   p.wbase0 = wb[0];
   p.wbase1 = wb[1];
   p.s_off0 = soff[0], p.s_off1 = soff[1], p.z_off0 = zoff[0], p.z_off1 = zoff[1];
@@ -1198,7 +1269,7 @@ hipError_t launch_gemv(const SmallMArgs& a, hipStream_t st) {
   }
   if (a.rope) {
     const ns_qkv_rope& r = *a.rope;
-    if (mode != GV_MSEG || nmat != 3 || r.mode != 0 || r.head_size < 2 || (r.head_size & 1) || r.n_dims != r.head_size ||
+    if ((mode != GV_MSEG && mode != GV_MSEGP) || nmat != 3 || r.mode != (neox ? 2 : 0) || r.head_size < 2 || (r.head_size & 1) || r.n_dims != r.head_size ||
         !r.kcache16 || !r.vcache16 || !r.cos_sin || r.n_past < 0 || p.mat[0].n != r.heads * r.head_size ||
         p.mat[1].n != r.heads_kv * r.head_size || p.mat[2].n != r.heads_kv * r.head_size)
       return hipErrorInvalidValue;
@@ -1221,8 +1292,8 @@ hipError_t launch_gemv(const SmallMArgs& a, hipStream_t st) {
 
   // waves per workgroup: enough waves on the chip to overlap dequantisation with the stream (as tuned for
   // smallm_kernel, profiles/r01*); the rings of a workgroup must fit in LDS beside the staged activations
-  const int grid = int(tiles);
-  const int nq = a.dual ? 2 : 1;
+  const int grid = neox ? int(tiles / 2) : int(tiles);
+  const int nq = (a.dual || neox) ? 2 : 1;
   const uint32_t sbytes = uint32_t(w0->sps) * (w0->scale_dt == DT_F32 ? 4u : 2u);
   const uint32_t slot = 1024u + 16u * sbytes + (w0->asym ? 16u * uint32_t(w0->sps) : 0u);
   auto ring_bytes = [&](int waves) {  // a wave's ring: one slot per item it can have in flight, at least the reduction scratch
@@ -1230,7 +1301,8 @@ hipError_t launch_gemv(const SmallMArgs& a, hipStream_t st) {
     const size_t b = size_t(std::min<uint32_t>(items, uint32_t(kGvPF))) * slot;
     return std::max<size_t>((b + 15) & ~size_t(15), size_t(nq) * 1024);
   };
-  int nw = decode_waves(grid, int(ks), a.dual);
+  // (the pair mode takes the wave count of the GV_MSEG launch of the same weights: the same split of K, the same bits)
+  int nw = decode_waves(int(tiles), int(ks), a.dual);
   {
     while (nw > 1 && ((a_bytes + 15) & ~size_t(15)) + ssq_bytes + size_t(nw) * ring_bytes(nw) > kGvMaxLds) nw /= 2;
   }

@@ -899,23 +899,26 @@ __global__ void rope_qkv_append_kernel(float* __restrict__ q, const float* __res
 }
 // (cos, sin) * attn_factor of the mode-0 pairs of positions n_past .. n_past + m - 1: the angle arithmetic of
 // rope_qkv_append_kernel, once per token for all layers (ns_qkv_rope)
+// neox (ns_hip_rope_cos_sin_mode, mode 2): the NeoX branch's angles — freq_scale goes into theta_base first and is applied again below
 __global__ void rope_cos_sin_kernel(int m, int n_past, int npairs, float theta_scale, float freq_scale, float attn_factor,
-                                    float2* __restrict__ out, const int* __restrict__ kmove, int kdelta) {
+                                    float2* __restrict__ out, const int* __restrict__ kmove, int kdelta, int neox) {
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= m * npairs) return;
   if (kmove) n_past += kdelta * *kmove;  // replayed device route: the position moves with the graph's token counter
   const int i2 = gid / npairs, pr = gid % npairs;
   float theta_base = float(n_past + i2);
+  if (neox) theta_base = __fmul_rn(theta_base, freq_scale);
   for (int t = 0; t < pr; t++) theta_base = __fmul_rn(theta_base, theta_scale);
   const float theta = __fmul_rn(freq_scale, theta_base);
   out[gid] = float2{__fmul_rn(cosf(theta), attn_factor), __fmul_rn(sinf(theta), attn_factor)};
 }
 hipError_t launch_rope_cos_sin(int m, int n_past, int n_dims, float freq_base, float freq_scale, float attn_factor,
-                               float* out, hipStream_t st) {
+                               float* out, hipStream_t st, bool neox) {
   const int total = m * (n_dims / 2);
   if (total <= 0) return hipSuccess;
   hipLaunchKernelGGL(rope_cos_sin_kernel, grid1d(size_t(total), 64), dim3(64), 0, st, m, n_past, n_dims / 2,
-                     powf(freq_base, -2.0f / n_dims), freq_scale, attn_factor, reinterpret_cast<float2*>(out), g_affine.k, int(g_affine.delta));
+                     powf(freq_base, -2.0f / n_dims), freq_scale, attn_factor, reinterpret_cast<float2*>(out), g_affine.k, int(g_affine.delta),
+                     neox ? 1 : 0);
   return hipGetLastError();
 }
 
