@@ -233,6 +233,10 @@ int ns_hip_get_compute_mode(void);
  *                     ranges of one head, -1 (default) = by the cache layout (position-major caches take 1: 5-10 % faster at 2048 / 4096 keys)
  *   "gv_nw"           waves per 16-column tile of the decode kernels (2 / 4 / 8 / 16), 0 = by shape (default); the
  *                     partial sums of a tile are added in wave order, so this selects the summation order
+ *   "gv_rows1"        1 (default) = a decode launch of ONE row takes the one-row instantiation of gemv_kernel where there is one (integer weights;
+ *                     fp16, carried-norm / RoPE and int8-reference launches; plain, fused gate / up, fused QKV): the arithmetic beside the weight
+ *                     stream sized for one row; 0 = always the general (up to 16 rows) instantiation; bit-identical results; also
+ *                     NS_GV_ROWS1=0 in the environment
  *   "g3_min_m"        rows from which the tiled prefill GEMM is used inside its envelope (0 = default)
  *   "moe_gemv_rows"   ns_hip_mul_mat_id: token rows up to which a call takes one decode-kernel launch per row (0 = default: NS_MOE_GEMV_ROWS
  *                     in the environment, else 8; negative = never)

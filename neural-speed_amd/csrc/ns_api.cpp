@@ -1201,6 +1201,10 @@ int ns_hip_set_tuning(const char* key, int value) {
     set_decode_waves(value);
     return 0;
   }
+  if (key && !strcmp(key, "gv_rows1")) {
+    set_gemv_rows1(value);
+    return 0;
+  }
   if (key && !strcmp(key, "attn_wg_target")) {
     set_attn_tuning(value, 0);
     return 0;

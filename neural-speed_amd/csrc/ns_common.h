@@ -252,6 +252,7 @@ bool gemm3_f8_on();
 bool gemm3_takes(const ns_weight* w);
 void set_gemm3_bm(int bm);  // ns_gemm.hip: force gemm3_kernel's row-tile height (tests / A-B runs); 0 = automatic  // ns_attn.hip: context-split rule of the decode attention kernel
 void set_decode_waves(int nw);  // 0 = by shape
+void set_gemv_rows1(int on);    // 1 (default): one-row launches of gemv_kernel take its one-row instantiation; 0: the general one (same bits)
 int decode_waves(int grid, int ks, bool dual);  // waves per workgroup of a decode launch (both kernel generations)
 void srow_rule(const ns_weight* w, int* num, int* den);          // scale row of k-step s = s * num / den
 // the same rule as a branch-free (s * mul) >> shift, verified for every k-step; false = not expressible

@@ -220,9 +220,19 @@ constexpr int kGvA32Regs = 8;  // 16-byte loads of fp32 activations a wave holds
 // 256 .. 896 bytes per k-step instead of the 1 KiB nibble / byte container — and each lane rebuilds its container words from its
 // plane words with shifts and masks (stored codes, bias 2^(bits-1) folded into the conversion constants: the same fp16 values,
 // hence the same bits out, as from the widened records).  KIND says which container: WK_INT4 for 1-3 bits, WK_INT8 for 5-7.
-template <int KIND, int SPS, int SK, bool ASYM, int MODE, int XV, bool PL = false>
+// R1 (round 7): the launch has ONE activation row (m == 1, what a batch-1 decode chain runs) and the arithmetic beside the stream is
+// sized for it: element 0 of each MFMA result is the only live output (every A row of the fragment is row 0), so the post-scale is
+// one FMA per slice instead of four, the accumulators one register per stream, the reduction one float per lane; the int8-reference
+// path has no row loop, no per-slice guard on full k-steps and 24-bit integer algebra.  Which bytes are requested, and when, is the
+// same as without it, and so are the bits out: the live row goes through the same operations in the same order.
+// Instantiated for integer weights, XV 0 / 1 / 3 / 5, modes PLAIN / DUAL / MSEG (gemv_has_rows1); ns_hip_set_tuning("gv_rows1", 0)
+// or NS_GV_ROWS1=0 keep every launch on the general form.
+template <int KIND, int SPS, int SK, bool ASYM, int MODE, int XV, bool PL = false, bool R1 = false>
 __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
   constexpr bool EXT = XV == 1, MOE = XV == 4, I8Q = XV == 5, A32 = XV == 2 || MOE || I8Q, I8S = XV == 3 || I8Q;
+  static_assert(!R1 || ((KIND == WK_INT4 || KIND == WK_INT8) && !PL && (XV == 0 || XV == 1 || XV == 3 || XV == 5) && MODE != GV_MSEGP),
+                "one-row form: integer weights, fp16 / carried-norm / int8-reference launches");
+  constexpr int RR = R1 ? 1 : 4;  // result rows a lane finishes in the epilogue
   static_assert(!PL || ((KIND == WK_INT4 || KIND == WK_INT8) && !I8S && !MOE), "native planes: integer formats, fp16 numerics");
   static_assert(!I8S || KIND == WK_INT4 || KIND == WK_INT8, "integer weights only");
   constexpr uint32_t AEL = I8S ? 1u : 2u;  // bytes per staged activation element
@@ -377,7 +387,7 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
   // ---- 1. activations requested first (small, and they must be in LDS before the first MFMA): fp16 rows go
   //      HBM/L2 -> LDS directly in 1 KiB pieces, piece c of row r by wave (r * pieces + c) % NW; LDS row r holds
   //      ks * KSTEP halves (columns >= K read as zero through the descriptor: k-step padding) ----
-  const int rows = min(p.m, kGvMaxRows);
+  const int rows = R1 ? 1 : min(p.m, kGvMaxRows);
   floatx4 areg[A32 ? kGvA32Regs : 1];
   if constexpr (A32) {
     // fp32 rows: 1 KiB pieces (256 columns) by wave (r * pieces + c) % NW again, at most kGvA32Regs per wave (host)
@@ -394,7 +404,8 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
       const uint32_t u = w + (uint32_t(i) << p.nw_log2);
       areg[i] = floatx4{0.f, 0.f, 0.f, 0.f};
       if (u < total) {
-        while (c >= pieces) c -= pieces, r++;
+        if constexpr (!R1)
+          while (c >= pieces) c -= pieces, r++;
 #if defined(__HIP_DEVICE_COMPILE__)
         // columns >= K of the last k-step come back as zero through the descriptor
         // by hand: hipcc does not count LDS-DMA requests, so for a load it knows of it waits for everything in flight
@@ -493,7 +504,8 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
       for (int i = 0; i < kGvA32Regs; i++) {
         const uint32_t u = w + (uint32_t(i) << p.nw_log2);
         if (u < total) {  // (wave-uniform)
-          while (c >= pieces) c -= pieces, r++;
+          if constexpr (!R1)
+            while (c >= pieces) c -= pieces, r++;
           const floatx4 v = areg[i];
           float maxval = 1.17549435e-38f /* FLT_MIN: a full block, kernel_ref.h:1832 */, minval = 0.f;
 #pragma unroll
@@ -566,10 +578,13 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
   NS_GSTAMP(2);
 
   // A-fragment LDS offset of this lane (rows >= m are clamped: their output rows are discarded)
-  const uint32_t aoff = uint32_t(min(nn, rows - 1)) * p.row_stride + 8 * g;
+  const uint32_t aoff = R1 ? uint32_t(8 * g) : uint32_t(min(nn, rows - 1)) * p.row_stride + 8 * g;
   floatx4 acc[NQ];
 #pragma unroll
   for (int q = 0; q < NQ; q++) acc[q] = floatx4{0.f, 0.f, 0.f, 0.f};
+  float acc1[NQ];  // R1: row 0 of column nn (every lane group holds it: all A rows of the fragment are row 0); I8S: this lane's k-slots
+#pragma unroll
+  for (int q = 0; q < NQ; q++) acc1[q] = 0.f;
 
   float accr[NQ][4];  // I8S: rows 0..3 of column nn, this lane's k-slots
 #pragma unroll
@@ -629,6 +644,89 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
         su[j] = int(__builtin_amdgcn_udot4(u0[j], 0x01010101u, __builtin_amdgcn_udot4(u1[j], 0x01010101u, 0u, false), false));
         zbq[j] = (ASYM ? int(zp[j]) : 0) + BIAS;
         kb[j] = min((kbase + 32u * uint32_t(j)) >> p.i8_bshift, p.i8_nblk - 1u);  // (slices past K: clamped, never used)
+      }
+      if constexpr (R1) {
+        // One row: no row loop.  A full k-step (every wave's k-steps but possibly its last) runs without the per-slice test; only a partial
+        // last k-step takes the guarded copy.  Integer algebra in 32 bits with 24-bit multiplies: codes <= 255, so sa, su <= 8 * 255 = 2040,
+        // za <= 255, zbq = zero point + bias <= 255, |su - 8 zbq| <= 2040 — every operand fits 12 bits, every product 23, and
+        //   isum = dot - zbq sa - za su + 8 za zbq = dot + (-zbq) sa + za (8 zbq - su)
+        // is two multiply-adds per slice with the weight side's two factors made once per record.  Exact, hence the same integer.
+        int nzb[NJ], nsu[NJ];
+#pragma unroll
+        for (int j = 0; j < NJ; j++) nzb[j] = -zbq[j], nsu[j] = 8 * zbq[j] - su[j];
+        const uint32_t aaddr = lds0 + kbase + 8u * uint32_t(g);
+        auto row0 = [&](auto guard_c, auto wide_c) {
+          constexpr bool GUARD = decltype(guard_c)::value, WIDE = decltype(wide_c)::value;
+          uint64_t av[4] = {0, 0, 0, 0};
+          uint32_t zau[4] = {0, 0, 0, 0}, asu[4] = {0, 0, 0, 0};
+          // LDS reads by hand (see the general form below)
+          if constexpr (WIDE) {
+            // 32-column activation k-blocks: the record's slices are consecutive blocks — their scales are NJ contiguous words, their
+            // zero points NJ contiguous bytes (both aligned: kbase / 32 is a multiple of NJ)
+            const uint32_t sa0 = i8_sbase + (kbase >> 5) * 4u, za0 = i8_zbase + (kbase >> 5);
+            if constexpr (NJ == 4) {
+              uint4v sv;
+              uint32_t zw;
+              asm volatile(
+                  "ds_read_b64 %0, %6\n\tds_read_b64 %1, %6 offset:32\n\tds_read_b64 %2, %6 offset:64\n\tds_read_b64 %3, %6 offset:96\n\t"
+                  "ds_read_b128 %4, %7\n\tds_read_b32 %5, %8\n\ts_waitcnt lgkmcnt(0)"
+                  : "=&v"(av[0]), "=&v"(av[1]), "=&v"(av[2]), "=&v"(av[3]), "=&v"(sv), "=&v"(zw)
+                  : "v"(aaddr), "v"(sa0), "v"(za0)
+                  : "memory");
+              asu[0] = sv.x, asu[1] = sv.y, asu[2] = sv.z, asu[3] = sv.w;
+#pragma unroll
+              for (int j = 0; j < 4; j++) zau[j] = (zw >> (8 * j)) & 0xffu;
+            } else {
+              uint64_t sv;
+              uint32_t zw;
+              asm volatile(
+                  "ds_read_b64 %0, %4\n\tds_read_b64 %1, %4 offset:32\n\tds_read_b64 %2, %5\n\tds_read_u16 %3, %6\n\ts_waitcnt lgkmcnt(0)"
+                  : "=&v"(av[0]), "=&v"(av[1]), "=&v"(sv), "=&v"(zw)
+                  : "v"(aaddr), "v"(sa0), "v"(za0)
+                  : "memory");
+              asu[0] = uint32_t(sv), asu[1] = uint32_t(sv >> 32);
+              zau[0] = zw & 0xffu, zau[1] = zw >> 8;
+            }
+          } else if constexpr (NJ == 4) {
+            asm volatile(
+                "ds_read_b64 %0, %12\n\tds_read_b64 %1, %12 offset:32\n\tds_read_b64 %2, %12 offset:64\n\tds_read_b64 %3, %12 offset:96\n\t"
+                "ds_read_u8 %4, %13\n\tds_read_u8 %5, %14\n\tds_read_u8 %6, %15\n\tds_read_u8 %7, %16\n\t"
+                "ds_read_b32 %8, %17\n\tds_read_b32 %9, %18\n\tds_read_b32 %10, %19\n\tds_read_b32 %11, %20\n\ts_waitcnt lgkmcnt(0)"
+                : "=&v"(av[0]), "=&v"(av[1]), "=&v"(av[2]), "=&v"(av[3]), "=&v"(zau[0]), "=&v"(zau[1]), "=&v"(zau[2]), "=&v"(zau[3]),
+                  "=&v"(asu[0]), "=&v"(asu[1]), "=&v"(asu[2]), "=&v"(asu[3])
+                : "v"(aaddr), "v"(i8_zbase + kb[0]), "v"(i8_zbase + kb[1]), "v"(i8_zbase + kb[2]), "v"(i8_zbase + kb[3]), "v"(i8_sbase + kb[0] * 4u),
+                  "v"(i8_sbase + kb[1] * 4u), "v"(i8_sbase + kb[2] * 4u), "v"(i8_sbase + kb[3] * 4u)
+                : "memory");
+          } else {
+            asm volatile(
+                "ds_read_b64 %0, %6\n\tds_read_b64 %1, %6 offset:32\n\tds_read_u8 %2, %7\n\tds_read_u8 %3, %8\n\t"
+                "ds_read_b32 %4, %9\n\tds_read_b32 %5, %10\n\ts_waitcnt lgkmcnt(0)"
+                : "=&v"(av[0]), "=&v"(av[1]), "=&v"(zau[0]), "=&v"(zau[1]), "=&v"(asu[0]), "=&v"(asu[1])
+                : "v"(aaddr), "v"(i8_zbase + kb[0]), "v"(i8_zbase + kb[1]), "v"(i8_sbase + kb[0] * 4u), "v"(i8_sbase + kb[1] * 4u)
+                : "memory");
+          }
+#pragma unroll
+          for (int j = 0; j < NJ; j++) {
+            if (!GUARD || kbase + 32u * uint32_t(j) < uint32_t(p.k)) {  // wave-uniform: a 32-deep slice lies inside K or outside
+              const uint32_t avx = uint32_t(av[j]), avy = uint32_t(av[j] >> 32);
+              const int dot = int(__builtin_amdgcn_udot4(avx, u0[j], __builtin_amdgcn_udot4(avy, u1[j], 0u, false), false));
+              const int sa = int(__builtin_amdgcn_udot4(avx, 0x01010101u, __builtin_amdgcn_udot4(avy, 0x01010101u, 0u, false), false));
+              const int isum = __mul24(int(zau[j]), nsu[j]) + (__mul24(nzb[j], sa) + dot);
+              // the general form's  accr += float(isum) * (asu * sc)  is contracted into one FMA per slice; written out here, because left
+              // as an expression the vectorizer pairs the slices' products into v_pk_mul_f32 + separate adds (another rounding)
+              acc1[q] = __builtin_fmaf(float(isum), __builtin_bit_cast(float, asu[j]) * sc[j], acc1[q]);
+            }
+          }
+        };
+        if (kbase + uint32_t(KSTEP) <= uint32_t(p.k)) {
+          if (p.i8_bshift == 5u)
+            row0(std::false_type{}, std::true_type{});
+          else
+            row0(std::false_type{}, std::false_type{});
+        } else {
+          row0(std::true_type{}, std::false_type{});
+        }
+        return;
       }
 #pragma unroll
       for (int r = 0; r < 4; r++) {
@@ -763,8 +861,17 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
       const half8_t afrag = *reinterpret_cast<const half8_t*>(abase + 32 * j);
       dd[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(afrag, bq[j], floatx4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
     }
+    if constexpr (R1) {
+      // element 0 is the live one; the whole result stays alive behind its MFMA — otherwise hipcc hands the other three registers to
+      // something else while the MFMA is still in flight (docs/kernels/experiments.md, finding (a))
 #pragma unroll
-    for (int j = 0; j < NJ; j++) acc[q] += dd[j] * sc[j];
+      for (int j = 0; j < NJ; j++) asm volatile("" : "+v"(dd[j]));
+#pragma unroll
+      for (int j = 0; j < NJ; j++) acc1[q] += dd[j][0] * sc[j];
+    } else {
+#pragma unroll
+      for (int j = 0; j < NJ; j++) acc[q] += dd[j] * sc[j];
+    }
   };
 
   // ---- 4. stream: consume the oldest record, refill its slot with the record PF items ahead ----
@@ -786,7 +893,15 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
   }
   NS_GSTAMP(4);
 
-  if constexpr (I8S) {  // the four k-slots of a column live in lanes nn, nn + 16, nn + 32, nn + 48; rows 0..3 = lane group 0's
+  if constexpr (I8S && R1) {
+#pragma unroll
+    for (int q = 0; q < NQ; q++) {
+      float v = acc1[q];
+      v += __shfl_xor(v, 16, 64);
+      v += __shfl_xor(v, 32, 64);
+      acc1[q] = g == 0 ? v : 0.f;
+    }
+  } else if constexpr (I8S) {  // the four k-slots of a column live in lanes nn, nn + 16, nn + 32, nn + 48; rows 0..3 = lane group 0's
 #pragma unroll
     for (int q = 0; q < NQ; q++) {
       float t[4];
@@ -803,8 +918,15 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
   // ---- 5. cross-wave reduction: every wave writes its partial sums over ITS OWN ring, wave 0 adds them in wave order ----
   floatx4* red = reinterpret_cast<floatx4*>(smem + p.ring_off);
   const uint32_t kRedWave = p.ring_stride / 16;  // floatx4 per wave region (>= NQ KiB, checked by the host)
+  float* red1 = reinterpret_cast<float*>(smem + p.ring_off);  // R1: one float per lane and stream, same wave regions
+  const uint32_t kRedWave1 = p.ring_stride / 4;
 #pragma unroll
-  for (int q = 0; q < NQ; q++) red[w * kRedWave + q * 64 + l] = acc[q];
+  for (int q = 0; q < NQ; q++) {
+    if constexpr (R1)
+      red1[w * kRedWave1 + q * 64 + l] = acc1[q];
+    else
+      red[w * kRedWave + q * 64 + l] = acc[q];
+  }
   const KArgs cold = late_args();  // epilogue-only arguments: fetched here, not held through the streaming loop
   const auto* mp = &cold->mat[MSEGX ? sg : 0];  // indexed scalar loads
   const int ncols = mp->n;
@@ -844,7 +966,7 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
     if constexpr (!DUAL) {
       if (dptr && col_ok) {
 #pragma unroll
-        for (int rr = 0; rr < 4; rr++)
+        for (int rr = 0; rr < RR; rr++)
           if (4 * g + rr < p.m) dvp[rr] = dptr[size_t(4 * g + rr) * ldd + col];
       }
     }
@@ -858,7 +980,7 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
           rope_e = col - rope_head * hs;
           if (sg < 2) {
 #pragma unroll
-            for (int rr = 0; rr < 4; rr++) cs[rr] = cold->rope.cos_sin[min(4 * g + rr, rows - 1) * (hs >> 1) + (rope_e >> 1)];
+            for (int rr = 0; rr < RR; rr++) cs[rr] = cold->rope.cos_sin[min(4 * g + rr, rows - 1) * (hs >> 1) + (rope_e >> 1)];
           }
           rope_sl = cold->rope.c_sl;
           const long long kk = cold->rope.kmove ? (long long)*cold->rope.kmove : 0ll;  // tokens since the plan was captured
@@ -905,11 +1027,15 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
 #pragma unroll
     for (int q = 0; q < NQ; q++) {
       sum[q] = floatx4{0.f, 0.f, 0.f, 0.f};
-      for (uint32_t ww = 0; ww < NW; ww++) sum[q] += red[ww * kRedWave + q * 64 + l];
+      if constexpr (R1) {
+        for (uint32_t ww = 0; ww < NW; ww++) sum[q][0] += red1[ww * kRedWave1 + q * 64 + l];
+      } else {
+        for (uint32_t ww = 0; ww < NW; ww++) sum[q] += red[ww * kRedWave + q * 64 + l];
+      }
     }
-    // ---- 6. epilogue: lane (nn, g) holds rows 4g .. 4g+3 of column nn ----
+    // ---- 6. epilogue: lane (nn, g) holds rows 4g .. 4g+3 of column nn (R1: row 0 alone, live in lane group 0) ----
 #pragma unroll
-    for (int rr = 0; rr < 4; rr++) {
+    for (int rr = 0; rr < RR; rr++) {
       const int row = 4 * g + rr;
       const bool ok = col_ok && row < p.m;
       float v = sum[0][rr] * rscale[rr];
@@ -1030,10 +1156,27 @@ static hipError_t launch_gemv_planes(const GemvParams& p, int mode, int grid, in
     return hipErrorNotSupported;
   }
 }
+// the one-row form (R1) exists for these instantiations; every other launch of one row takes the general form
+constexpr bool gemv_has_rows1(int kind, int mode, int xv) {
+  return (kind == WK_INT4 || kind == WK_INT8) && (mode == GV_PLAIN || mode == GV_DUAL || mode == GV_MSEG) && (xv == 0 || xv == 1 || xv == 3 || xv == 5);
+}
+static std::atomic<int> g_gemv_rows1{-1};  // ns_hip_set_tuning("gv_rows1"): 1 (default) = launches of one row take the one-row form; -1: read NS_GV_ROWS1 once
+void set_gemv_rows1(int on) { g_gemv_rows1.store(on != 0); }
+static bool gemv_rows1() {
+  int v = g_gemv_rows1.load(std::memory_order_relaxed);
+  if (v < 0) {
+    const char* e = getenv("NS_GV_ROWS1");
+    v = e ? atoi(e) != 0 : 1;
+    g_gemv_rows1.store(v);
+  }
+  return v != 0;
+}
+
 template <int KIND, int SPS, int SK, bool ASYM>
 static hipError_t launch_gemv_k(const GemvParams& p, int mode, int grid, int nw, size_t lds, hipStream_t st) {
   if (mode & kGvModePlanes) return launch_gemv_planes<KIND, SPS, SK, ASYM>(p, mode & ~kGvModePlanes, grid, nw, lds, st);
   const dim3 g(grid), b(nw * 64);
+  const bool r1 = p.m == 1 && gemv_rows1();
   const bool ext = p.in_ssq || p.out_gamma || p.out_ssq || p.rope.on;
   const bool a32 = (mode & kGvModeA32) != 0;  // never together with ext (launch_gemv)
   const bool i8s = (mode & kGvModeI8) != 0;
@@ -1064,7 +1207,14 @@ static hipError_t launch_gemv_k(const GemvParams& p, int mode, int grid, int nw,
   }
 #define NS_GV_LAUNCH_E(MODEV, EXTV)                                                                             \
   {                                                                                                             \
-    auto k = gemv_kernel<KIND, SPS, SK, ASYM, MODEV, EXTV>;                                                      \
+    if constexpr (gemv_has_rows1(KIND, MODEV, EXTV)) {                                                          \
+      if (r1) NS_GV_LAUNCH_K(MODEV, EXTV, true) else NS_GV_LAUNCH_K(MODEV, EXTV, false)                         \
+    } else                                                                                                      \
+      NS_GV_LAUNCH_K(MODEV, EXTV, false)                                                                        \
+  }
+#define NS_GV_LAUNCH_K(MODEV, EXTV, R1V)                                                                        \
+  {                                                                                                             \
+    auto k = gemv_kernel<KIND, SPS, SK, ASYM, MODEV, EXTV, false, R1V>;                                          \
     static const hipError_t attr =                                                                              \
         hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, int(kGvMaxLds)); \
     if (attr != hipSuccess && lds > 64 * 1024) return attr;                                                     \
@@ -1081,6 +1231,7 @@ static hipError_t launch_gemv_k(const GemvParams& p, int mode, int grid, int nw,
     NS_GV_LAUNCH(GV_PLAIN)
 #undef NS_GV_LAUNCH
 #undef NS_GV_LAUNCH_E
+#undef NS_GV_LAUNCH_K
 #undef NS_GV_LAUNCH_I8
 #undef NS_GV_LAUNCH_I8Q
 #undef NS_GV_LAUNCH_MOE
