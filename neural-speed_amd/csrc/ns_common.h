@@ -216,8 +216,8 @@ void* stream_scratch(hipStream_t st, size_t bytes, int slot);
 void* stream_scratch_zeroed(hipStream_t st, size_t bytes, int slot);  // zero-filled when (re)allocated: self-resetting counters
 // fp32 [m][lda] -> fp16 [m][ld16] (ld16 a multiple of 8, columns k..ld16-1 zero)
 hipError_t launch_cvt_a16(const float* a, void* out16, int m, int k, int lda, int ld16, hipStream_t st);
-// ns_gemv.hip: second-generation decode kernel (m <= 16): lean prologue, one 16-column tile per workgroup;
-// hipErrorNotSupported = outside its envelope (use smallm_kernel)
+// ns_gemv_host.cpp: second-generation decode kernel (m <= 16; gemv_kernel, ns_gemv.hip — compiled once per weight kind and scales-per-record
+// count, ns_gemv.h): lean prologue, one 16-column tile per workgroup; hipErrorNotSupported = outside its envelope (use smallm_kernel)
 hipError_t launch_gemv(const SmallMArgs& a, hipStream_t st);
 void set_gemv_mode(int mode);  // 0 off (first-generation kernel), 1 on, -1 re-read NS_GEMV2
 // ns_gemvs.hip: small-batch / narrow-output decode kernel (2 .. 16 rows; activations staged once per workgroup and shared
@@ -313,7 +313,8 @@ struct Affine {
 bool attn_prepare_moving(hipStream_t st, int batch, int heads, int heads_kv, int head_size, int cap);
 // One function per translation unit with kernels of the hot paths: asks the runtime for one kernel's attributes, which makes it load that unit's code object
 // for the device NOW (HIP loads a code object at the first launch from it: 36 ms for the tiled GEMM's, 21 ms for the decode GEMV's — otherwise paid by the first
-// prompt and the first generated token).  ns_hip_warm_up() / bestla_create_device call them once.
+// prompt and the first generated token).  ns_hip_warm_up() / bestla_create_device call them once.  (touch_gemv_module: one kernel of every object
+// ns_gemv.hip is compiled into — each has a code object of its own.)
 void touch_gemm_module();
 void touch_gemv_module();
 void touch_attn_module();

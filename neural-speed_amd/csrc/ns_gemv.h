@@ -1,0 +1,144 @@
+// ns_gemv.h — interface between the host logic of the decode kernel (ns_gemv_host.cpp: launch_gemv, its tuning state) and the
+// translation units that hold gemv_kernel's instantiations (ns_gemv.hip, compiled once per weight kind and scales-per-record
+// count — NS_GEMV_SLICES below: the 1169 instantiations in one translation unit took thirteen minutes to compile).
+// Declarations only: the kernel, its device helpers and the launch ladder are in ns_gemv.hip.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "ns_dev.h"
+
+namespace ns {
+
+#ifndef NS_GV_PF
+#define NS_GV_PF 4
+#endif
+// records each wave keeps in flight (fused gate/up: half of them per matrix).  A CU's memory pipeline holds about
+// 50 KiB of requests; beyond that the ISSUE of further requests stalls (profiles/r02h_wave_trace: ring fills of a
+// 24-wave CU complete 0.5 ... 6 us after entry), so a deeper ring only delays the other waves' first records:
+// 8 deep measured 12 % slower on the whole chain than 4 deep (profiles/r02g_sweep.txt)
+constexpr int kGvPF = NS_GV_PF;
+constexpr int kGvMaxRows = 16;
+constexpr size_t kGvMaxALds = 64 * 1024;    // staged activations (fp16) per workgroup
+constexpr size_t kGvMaxLds = 160 * 1024;
+constexpr int kGvA32Regs = 8;  // 16-byte loads of fp32 activations a wave holds in registers (XV = 2)
+
+// one matrix of a launch as the kernel sees it; a fused QKV launch looks its matrix up BY INDEX in the kernel-argument
+// segment (one scalar load) instead of carrying three of everything in SGPRs
+struct GemvMat {
+  const uint8_t* wbase;  // ONE allocation: records at 0, scales at s_off, zero points at z_off
+  uint32_t s_off, z_off;
+  uint32_t tile_begin;   // first global tile of this matrix in the launch
+  int n;
+  float* c;
+  _Float16* c16;
+};
+static_assert(sizeof(GemvMat) == 40, "GemvMat is addressed by index in the kernel-argument segment");
+
+// RoPE of q and k + kv-cache append as the epilogue of a fused QKV launch (ns_qkv_rope).  Adjacent pairs (mode 0) always lie
+// inside one 16-column tile (GV_MSEG).  NeoX pairs (e, e + head_size / 2) lie head_size / 32 tiles apart: a workgroup of the
+// pair mode (GV_MSEGP) streams both tiles, so no value is handed between workgroups
+struct GemvRope {
+  _Float16* kc;
+  _Float16* vc;
+  long long c_sl, c_head;  // cache element strides per position / per head
+  const float2* cos_sin;   // [row][head_size / 2] (cos, sin) * attn_factor of position n_past + row (ns_hip_rope_cos_sin)
+  int head_size, n_past;
+  int on;
+  // replayed device route (QkvRopeRoute, ns_common.h; one row): k (rotated) and v also go to the reference's fp32 cache cells, and the
+  // position follows the captured graph's token counter
+  int kd_pos;
+  const int* kmove;
+  float* k32;
+  float* v32;
+  long long k32_head, k32_dim, k32_tok, v32_head, v32_dim, v32_tok;
+  uint32_t* ovf;
+};
+
+// one row of an expert group's device table (ns_moe.hip: MoeExpert — same layout)
+struct MoeExpertRow {
+  const uint8_t* codes;
+  const uint8_t* scales;
+  const int8_t* zps;
+};
+
+struct GemvParams {
+  // ---- hot head: everything the prologue needs, fetched by one batch of scalar loads ----
+  const uint8_t* wbase0;    // matrix 0 (and, for the fused gate/up launch, matrix 1)
+  const uint8_t* wbase1;
+  const void* a;            // activations, fp16 [m][lda]
+  uint32_t ks;              // k-steps per tile
+  uint32_t qstride;         // bytes per (tile, k-step) record
+  uint32_t nw_log2;         // log2(waves per workgroup)
+  uint32_t s_off0, s_off1;
+  uint32_t sstride;
+  uint32_t srows, srow_mul, srow_shift;
+  uint32_t tb1, tb2;        // first global tile of matrices 1 and 2 of a fused QKV launch (2^32 - 1: absent)
+  int m, k, lda;
+  uint32_t row_stride;      // halves per staged row in LDS
+  uint32_t ring_off;        // byte offset of the per-wave rings in LDS (the reduction scratch reuses them)
+  uint32_t ring_stride;     // bytes of one wave's ring = slots x slot size
+  uint32_t z_off0, z_off1, zstride;  // asymmetric formats only: last, so that the rest is one contiguous run of words
+  // int8-reference numerics (XV = 3): a = u8 activation codes [m][lda]; i8_corr = [m][nblk] fp32 scales followed by
+  // [m][nblk] u8 zero points (one span, staged at ssq_off); k-block of column kk = kk >> i8_bshift
+  const uint8_t* i8_corr;
+  uint32_t i8_span, i8_nblk, i8_bshift;
+  // expert-indexed launch (XV = 4, ns_hip_mul_mat_id at decode size): the weight base is table[*moe_id].codes — every expert of a
+  // group has the same shape and layout, so the offsets above hold for all of them; an id outside [0, moe_n) gives epi(0, d)
+  const MoeExpertRow* moe_table;
+  const int32_t* moe_id;
+  int moe_n;
+  // native bit-plane records (PL = true: ns_weight::native): the format's bit width and the lanes of a record request
+  // (record bytes / 16; the record's planes are contiguous, so a k-step is still ONE request)
+  uint32_t pl_bits, pl_lanes;
+  // segment pairs (GV_MSEGP): 16-column tiles per half head (head_size / 32) — workgroup u of a matrix owns tiles
+  // t0 = head * 2 pair_tiles + j and t0 + pair_tiles (head = u / pair_tiles, j = u % pair_tiles); tb1 / tb2 count workgroups there
+  uint32_t pair_tiles;
+  // ---- cold: read late, through the kernel-argument pointer (keeps them out of the streaming loop's SGPRs) ----
+  GemvMat mat[3];
+  float* c2;
+  const float* d;
+  int ldc, ldd, epilogue;
+  // carried RMS norm, consumer side (ns_norm_link): per row, in_parts partial sums of squares of the un-normalised
+  // activations, staged into LDS at ssq_off beside A (nullptr: A is already normalised);
+  // row scale = 1 / sqrt(sum * in_inv_size + in_eps)
+  const float* in_ssq;
+  uint32_t in_parts, in_stride;
+  uint32_t ssq_off;
+  float in_eps, in_inv_size;
+  const float* out_gamma;     // carried norm, producer: fp16 shadow = v * gamma[col] ...
+  float* out_ssq;             // ... and out_ssq[row * out_stride + tile] = sum of v^2 over the tile's columns
+  uint32_t out_stride;
+  uint32_t* out_ovf;          // pinned host word, set when gamma * v does not fit the fp16 shadow (ns_route.h: the route then evaluates the token again without carried norms)
+  GemvRope rope;
+  F4Lut lut;
+  F8Consts f8;
+#ifdef NS_TRACE
+  unsigned long long* trace;
+#endif
+};
+
+// MODE of gemv_kernel (described above the kernel)
+enum GemvMode { GV_PLAIN = 0, GV_DUAL = 1, GV_MSEG = 2, GV_MSEGP = 3 };
+constexpr int kGvModeA32 = 0x100;  // or-ed into the launch mode: fp32 activations (XV = 2)
+constexpr int kGvModeI8 = 0x200;   // int8-reference numerics (XV = 3)
+constexpr int kGvModeMoe = 0x400;  // expert picked on the device (XV = 4; fp32 activations)
+constexpr int kGvModePlanes = 0x800;  // native bit-plane records (PL = true)
+
+bool gemv_rows1();  // ns_gemv_host.cpp: the "gv_rows1" tuning value — launches of one row take the one-row form
+
+// One object per slice X(weight kind, scales per record), each with its own device code object.  Per slice:
+//   launch_gemv_<KIND>_<SPS>: launches the instantiation for (scale type, sym / asym, mode bits) on a prepared GemvParams;
+//     hipErrorNotSupported: no such instantiation (the caller falls back to smallm_kernel)
+//   touch_gemv_<KIND>_<SPS>: makes the runtime load the slice's code object (touch_gemv_module, ns_common.h)
+#define NS_GEMV_SLICES(X) X(INT4, 4) X(INT4, 2) X(INT4, 1) X(INT8, 2) X(INT8, 1) X(F4, 4) X(F4, 2) X(F4, 1) X(F8, 2) X(F8, 1)
+#define NS_GEMV_DECLARE(KIND, SPS)                                                                                      \
+  hipError_t launch_gemv_##KIND##_##SPS(const GemvParams& p, uint32_t scale_dt, bool asym, int mode, int grid, int nw, \
+                                        size_t lds, hipStream_t st);                                                   \
+  void touch_gemv_##KIND##_##SPS();
+NS_GEMV_SLICES(NS_GEMV_DECLARE)
+#undef NS_GEMV_DECLARE
+
+}  // namespace ns

@@ -25,130 +25,33 @@
 // ("stream-K") with partial sums handed between workgroups through write-through stores + flags.  The hand-off costs
 // 3-5 us under load (the poll queues behind the consumer CU's own weight requests) — more than the 2 us of imbalance it
 // removes in an 11 us launch; narrow tensor-parallel shards lost 3 us per launch to it.
+//
+// This file is compiled once per SLICE — weight kind x scales per record (NS_GEMV_KIND, NS_GEMV_SPS; csrc/Makefile: GEMV) —
+// into objects built side by side: the kernel, the ladder that picks an instantiation from a launch's run-time format and mode,
+// and the ONE exported launcher of the slice, named after the two macros.  ns_gemv.h has the parameter structs and the
+// launchers' declarations, ns_gemv_host.cpp the host logic in front of them (launch_gemv, decode_waves, tuning state).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <cstddef>
-#include <cstdlib>
 #include <cstring>
 #include <type_traits>
 #include <utility>
 
 #include "../../include/ns_bestla.h"
 #include "ns_common.h"
-#include "ns_route.h"
 #include "ns_dev.h"
+#include "ns_gemv.h"
+
+// the slice this object holds (Makefile: GEMV_SLICES); a bare `hipcc -c ns_gemv.hip` builds the Q4_0 one
+#ifndef NS_GEMV_KIND
+#define NS_GEMV_KIND INT4
+#define NS_GEMV_SPS 4
+#endif
 
 namespace ns {
 
-#ifndef NS_GV_PF
-#define NS_GV_PF 4
-#endif
-// records each wave keeps in flight (fused gate/up: half of them per matrix).  A CU's memory pipeline holds about
-// 50 KiB of requests; beyond that the ISSUE of further requests stalls (profiles/r02h_wave_trace: ring fills of a
-// 24-wave CU complete 0.5 ... 6 us after entry), so a deeper ring only delays the other waves' first records:
-// 8 deep measured 12 % slower on the whole chain than 4 deep (profiles/r02g_sweep.txt)
-constexpr int kGvPF = NS_GV_PF;
-constexpr int kGvMaxRows = 16;
-constexpr size_t kGvMaxALds = 64 * 1024;    // staged activations (fp16) per workgroup
-constexpr size_t kGvMaxLds = 160 * 1024;
-
-// one matrix of a launch as the kernel sees it; a fused QKV launch looks its matrix up BY INDEX in the kernel-argument
-// segment (one scalar load) instead of carrying three of everything in SGPRs
-struct GemvMat {
-  const uint8_t* wbase;  // ONE allocation: records at 0, scales at s_off, zero points at z_off
-  uint32_t s_off, z_off;
-  uint32_t tile_begin;   // first global tile of this matrix in the launch
-  int n;
-  float* c;
-  _Float16* c16;
-};
-static_assert(sizeof(GemvMat) == 40, "GemvMat is addressed by index in the kernel-argument segment");
-
-// RoPE of q and k + kv-cache append as the epilogue of a fused QKV launch (ns_qkv_rope).  Adjacent pairs (mode 0) always lie
-// inside one 16-column tile (GV_MSEG).  NeoX pairs (e, e + head_size / 2) lie head_size / 32 tiles apart: a workgroup of the
-// pair mode (GV_MSEGP) streams both tiles, so no value is handed between workgroups
-struct GemvRope {
-  _Float16* kc;
-  _Float16* vc;
-  long long c_sl, c_head;  // cache element strides per position / per head
-  const float2* cos_sin;   // [row][head_size / 2] (cos, sin) * attn_factor of position n_past + row (ns_hip_rope_cos_sin)
-  int head_size, n_past;
-  int on;
-  // replayed device route (QkvRopeRoute, ns_common.h; one row): k (rotated) and v also go to the reference's fp32 cache cells, and the
-  // position follows the captured graph's token counter
-  int kd_pos;
-  const int* kmove;
-  float* k32;
-  float* v32;
-  long long k32_head, k32_dim, k32_tok, v32_head, v32_dim, v32_tok;
-  uint32_t* ovf;
-};
-
-// one row of an expert group's device table (ns_moe.hip: MoeExpert — same layout)
-struct MoeExpertRow {
-  const uint8_t* codes;
-  const uint8_t* scales;
-  const int8_t* zps;
-};
-
-struct GemvParams {
-  // ---- hot head: everything the prologue needs, fetched by one batch of scalar loads ----
-  const uint8_t* wbase0;    // matrix 0 (and, for the fused gate/up launch, matrix 1)
-  const uint8_t* wbase1;
-  const void* a;            // activations, fp16 [m][lda]
-  uint32_t ks;              // k-steps per tile
-  uint32_t qstride;         // bytes per (tile, k-step) record
-  uint32_t nw_log2;         // log2(waves per workgroup)
-  uint32_t s_off0, s_off1;
-  uint32_t sstride;
-  uint32_t srows, srow_mul, srow_shift;
-  uint32_t tb1, tb2;        // first global tile of matrices 1 and 2 of a fused QKV launch (2^32 - 1: absent)
-  int m, k, lda;
-  uint32_t row_stride;      // halves per staged row in LDS
-  uint32_t ring_off;        // byte offset of the per-wave rings in LDS (the reduction scratch reuses them)
-  uint32_t ring_stride;     // bytes of one wave's ring = slots x slot size
-  uint32_t z_off0, z_off1, zstride;  // asymmetric formats only: last, so that the rest is one contiguous run of words
-  // int8-reference numerics (XV = 3): a = u8 activation codes [m][lda]; i8_corr = [m][nblk] fp32 scales followed by
-  // [m][nblk] u8 zero points (one span, staged at ssq_off); k-block of column kk = kk >> i8_bshift
-  const uint8_t* i8_corr;
-  uint32_t i8_span, i8_nblk, i8_bshift;
-  // expert-indexed launch (XV = 4, ns_hip_mul_mat_id at decode size): the weight base is table[*moe_id].codes — every expert of a
-  // group has the same shape and layout, so the offsets above hold for all of them; an id outside [0, moe_n) gives epi(0, d)
-  const MoeExpertRow* moe_table;
-  const int32_t* moe_id;
-  int moe_n;
-  // native bit-plane records (PL = true: ns_weight::native): the format's bit width and the lanes of a record request
-  // (record bytes / 16; the record's planes are contiguous, so a k-step is still ONE request)
-  uint32_t pl_bits, pl_lanes;
-  // segment pairs (GV_MSEGP): 16-column tiles per half head (head_size / 32) — workgroup u of a matrix owns tiles
-  // t0 = head * 2 pair_tiles + j and t0 + pair_tiles (head = u / pair_tiles, j = u % pair_tiles); tb1 / tb2 count workgroups there
-  uint32_t pair_tiles;
-  // ---- cold: read late, through the kernel-argument pointer (keeps them out of the streaming loop's SGPRs) ----
-  GemvMat mat[3];
-  float* c2;
-  const float* d;
-  int ldc, ldd, epilogue;
-  // carried RMS norm, consumer side (ns_norm_link): per row, in_parts partial sums of squares of the un-normalised
-  // activations, staged into LDS at ssq_off beside A (nullptr: A is already normalised);
-  // row scale = 1 / sqrt(sum * in_inv_size + in_eps)
-  const float* in_ssq;
-  uint32_t in_parts, in_stride;
-  uint32_t ssq_off;
-  float in_eps, in_inv_size;
-  const float* out_gamma;     // carried norm, producer: fp16 shadow = v * gamma[col] ...
-  float* out_ssq;             // ... and out_ssq[row * out_stride + tile] = sum of v^2 over the tile's columns
-  uint32_t out_stride;
-  uint32_t* out_ovf;          // pinned host word, set when gamma * v does not fit the fp16 shadow (ns_route.h: the route then evaluates the token again without carried norms)
-  GemvRope rope;
-  F4Lut lut;
-  F8Consts f8;
-#ifdef NS_TRACE
-  unsigned long long* trace;
-#endif
-};
 // the kernel-argument segment as an opaque pointer: loads through it cannot be hoisted above the point it is made
 using KArgs = const __attribute__((address_space(4))) GemvParams*;
 __device__ __forceinline__ KArgs late_args() {
@@ -183,7 +86,6 @@ __device__ __forceinline__ void neox_rotate(float x0, float x1, float c, float s
   *y1 = d + e;
 }
 
-enum GemvMode { GV_PLAIN = 0, GV_DUAL = 1, GV_MSEG = 2, GV_MSEGP = 3 };
 // MODE: one matrix / two matrices of one shape streamed in lockstep (gate/up, SiLU-mul epilogue) / several matrices
 // side by side along N (QKV) / the same with "segment pairs" (GV_MSEGP, XV = 1 only): the NeoX form of the RoPE epilogue.  A
 // workgroup streams the two tiles of a rotation pair (columns e and e + head_size / 2 of a head) with GV_DUAL's machinery — ring
@@ -201,7 +103,6 @@ enum GemvMode { GV_PLAIN = 0, GV_DUAL = 1, GV_MSEG = 2, GV_MSEGP = 3 };
 // device graph hands bestla_device_f32f32_forward fp32 tensors).  The wave's share of A is loaded into registers in
 // front of the ring requests, converted (round to nearest even, as the shadow's producers do) and written to LDS once
 // only ring requests are left in flight — the weights are requested exactly as early as with a shadow.
-constexpr int kGvA32Regs = 8;  // 16-byte loads of fp32 activations a wave holds in registers
 // XV = 4 (MOE): A32 + the weight picked on the DEVICE: ne_compute_forward_mul_mat_id_q_f32_bestla (ne_layers.c:7783-7916) reads
 // ids[token][id] on the host and calls bestla_f32f32_forward per (token, expert); here the id stays where the router's top-k left
 // it — one scalar load of the id, one of the expert's base pointer, in front of the first weight request (two dependent round
@@ -1118,12 +1019,19 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
 }
 
 // ============================================================================================================
-// host side
+// host side: the ladder from a launch's run-time format and mode to its instantiation.  The if constexpr guards decide
+// WHICH instantiations exist (launch_gemv, ns_gemv_host.cpp, prepares the GemvParams and picks the slice)
 // ============================================================================================================
-constexpr int kGvModeA32 = 0x100;  // or-ed into the launch mode: fp32 activations (XV = 2)
-constexpr int kGvModeI8 = 0x200;   // int8-reference numerics (XV = 3)
-constexpr int kGvModeMoe = 0x400;  // expert picked on the device (XV = 4; fp32 activations)
-constexpr int kGvModePlanes = 0x800;  // native bit-plane records (PL = true)
+// one instantiation's launch; its dynamic LDS limit is raised once, at its first launch
+template <int KIND, int SPS, int SK, bool ASYM, int MODE, int XV, bool PL, bool R1>
+static hipError_t gv_launch(dim3 g, dim3 b, size_t lds, hipStream_t st, const GemvParams& p) {
+  auto k = gemv_kernel<KIND, SPS, SK, ASYM, MODE, XV, PL, R1>;
+  static const hipError_t attr =
+      hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, int(kGvMaxLds));
+  if (attr != hipSuccess && lds > 64 * 1024) return attr;
+  hipLaunchKernelGGL(k, g, b, lds, st, p);
+  return hipGetLastError();
+}
 template <int KIND, int SPS, int SK, bool ASYM>
 static hipError_t launch_gemv_planes(const GemvParams& p, int mode, int grid, int nw, size_t lds, hipStream_t st) {
   if constexpr ((KIND == WK_INT4 || KIND == WK_INT8) && SK != SK_F16) {
@@ -1131,14 +1039,7 @@ static hipError_t launch_gemv_planes(const GemvParams& p, int mode, int grid, in
     const bool ext = p.in_ssq || p.out_gamma || p.out_ssq || p.rope.on;
     const bool a32 = (mode & kGvModeA32) != 0;
     mode &= 3;
-#define NS_GVP(MODEV, EXTV)                                                                                                  \
-  {                                                                                                                         \
-    auto k = gemv_kernel<KIND, SPS, SK, ASYM, MODEV, EXTV, true>;                                                            \
-    static const hipError_t attr =                                                                                          \
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, int(kGvMaxLds));   \
-    if (attr != hipSuccess && lds > 64 * 1024) return attr;                                                                 \
-    hipLaunchKernelGGL(k, g, b, lds, st, p);                                                                                \
-  }
+#define NS_GVP(MODEV, EXTV) return gv_launch<KIND, SPS, SK, ASYM, MODEV, EXTV, true, false>(g, b, lds, st, p);
 #define NS_GVP_M(MODEV)                                                              \
   {                                                                                 \
     if (ext) NS_GVP(MODEV, 1) else if (a32) NS_GVP(MODEV, 2) else NS_GVP(MODEV, 0)   \
@@ -1151,7 +1052,6 @@ static hipError_t launch_gemv_planes(const GemvParams& p, int mode, int grid, in
       NS_GVP_M(GV_PLAIN)
 #undef NS_GVP_M
 #undef NS_GVP
-    return hipGetLastError();
   } else {
     return hipErrorNotSupported;
   }
@@ -1159,17 +1059,6 @@ static hipError_t launch_gemv_planes(const GemvParams& p, int mode, int grid, in
 // the one-row form (R1) exists for these instantiations; every other launch of one row takes the general form
 constexpr bool gemv_has_rows1(int kind, int mode, int xv) {
   return (kind == WK_INT4 || kind == WK_INT8) && (mode == GV_PLAIN || mode == GV_DUAL || mode == GV_MSEG) && (xv == 0 || xv == 1 || xv == 3 || xv == 5);
-}
-static std::atomic<int> g_gemv_rows1{-1};  // ns_hip_set_tuning("gv_rows1"): 1 (default) = launches of one row take the one-row form; -1: read NS_GV_ROWS1 once
-void set_gemv_rows1(int on) { g_gemv_rows1.store(on != 0); }
-static bool gemv_rows1() {
-  int v = g_gemv_rows1.load(std::memory_order_relaxed);
-  if (v < 0) {
-    const char* e = getenv("NS_GV_ROWS1");
-    v = e ? atoi(e) != 0 : 1;
-    g_gemv_rows1.store(v);
-  }
-  return v != 0;
 }
 
 template <int KIND, int SPS, int SK, bool ASYM>
@@ -1207,18 +1096,9 @@ static hipError_t launch_gemv_k(const GemvParams& p, int mode, int grid, int nw,
   }
 #define NS_GV_LAUNCH_E(MODEV, EXTV)                                                                             \
   {                                                                                                             \
-    if constexpr (gemv_has_rows1(KIND, MODEV, EXTV)) {                                                          \
-      if (r1) NS_GV_LAUNCH_K(MODEV, EXTV, true) else NS_GV_LAUNCH_K(MODEV, EXTV, false)                         \
-    } else                                                                                                      \
-      NS_GV_LAUNCH_K(MODEV, EXTV, false)                                                                        \
-  }
-#define NS_GV_LAUNCH_K(MODEV, EXTV, R1V)                                                                        \
-  {                                                                                                             \
-    auto k = gemv_kernel<KIND, SPS, SK, ASYM, MODEV, EXTV, false, R1V>;                                          \
-    static const hipError_t attr =                                                                              \
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, int(kGvMaxLds)); \
-    if (attr != hipSuccess && lds > 64 * 1024) return attr;                                                     \
-    hipLaunchKernelGGL(k, g, b, lds, st, p);                                                                    \
+    if constexpr (gemv_has_rows1(KIND, MODEV, EXTV))                                                            \
+      if (r1) return gv_launch<KIND, SPS, SK, ASYM, MODEV, EXTV, false, true>(g, b, lds, st, p);                \
+    return gv_launch<KIND, SPS, SK, ASYM, MODEV, EXTV, false, false>(g, b, lds, st, p);                         \
   }
   if (mode == GV_MSEGP) {  // the NeoX RoPE epilogue's pair mode: one instantiation per format (XV = 1)
     if (moe || i8s || a32 || !p.rope.on) return hipErrorNotSupported;
@@ -1231,7 +1111,6 @@ static hipError_t launch_gemv_k(const GemvParams& p, int mode, int grid, int nw,
     NS_GV_LAUNCH(GV_PLAIN)
 #undef NS_GV_LAUNCH
 #undef NS_GV_LAUNCH_E
-#undef NS_GV_LAUNCH_K
 #undef NS_GV_LAUNCH_I8
 #undef NS_GV_LAUNCH_I8Q
 #undef NS_GV_LAUNCH_MOE
@@ -1256,276 +1135,28 @@ static hipError_t launch_gemv_s(const GemvParams& p, uint32_t scale_dt, bool asy
   return launch_gemv_a<KIND, SPS, SK_BF16>(p, asym, mode, grid, nw, lds, st);
 }
 
-#ifdef NS_TRACE
-unsigned long long* trace_buffer();
-#endif
 
-static std::atomic<int> g_gemv_mode{-1};  // -1: read NS_GEMV2 once; 0 off (first-generation kernel); 1 on
-void set_gemv_mode(int mode) { g_gemv_mode.store(mode); }
-static int gemv_mode() {
-  int m = g_gemv_mode.load();
-  if (m < 0) {
-    const char* e = getenv("NS_GEMV2");
-    m = e ? atoi(e) : 1;
-    g_gemv_mode.store(m);
-  }
-  return m;
+// ---- this object's slice ----
+#define NS_GV_PASTE_(a, b) a##b
+#define NS_GV_PASTE(a, b) NS_GV_PASTE_(a, b)
+#define NS_GV_SLICE_FN(prefix) NS_GV_PASTE(NS_GV_PASTE(NS_GV_PASTE(prefix, NS_GEMV_KIND), _), NS_GEMV_SPS)
+constexpr int kGvSliceKind = NS_GV_PASTE(WK_, NS_GEMV_KIND);
+
+template <int KIND, int SPS>
+static hipError_t launch_gemv_slice(const GemvParams& p, uint32_t scale_dt, bool asym, int mode, int grid, int nw, size_t lds,
+                                    hipStream_t st) {
+  if constexpr (KIND == WK_F8)  // device scales are always fp32 (E8M0 shared exponents are expanded at load)
+    return launch_gemv_a<KIND, SPS, SK_F32>(p, false, mode, grid, nw, lds, st);
+  else
+    return launch_gemv_s<KIND, SPS>(p, scale_dt, asym, mode, grid, nw, lds, st);
 }
-
-// waves per workgroup of a decode launch (one 16-column tile per workgroup, k-steps dealt round-robin to the waves).
-// Shared with smallm_kernel so that both kernels split K the same way — bit-identical sums between a caller that passes
-// the fp16 shadow of A and an fp32-only caller — wherever this rule alone decides: launch_gemv additionally halves the
-// wave count until activations + rings fit in LDS (several rows of a large K), where smallm_kernel keeps the rule's value;
-// the two then differ in fp32 summation order only (fp32-only callers of decode shapes are served by gemv_kernel itself
-// since round 3, bit-equal to the shadow path: tests/test_gpu_fullsize.py).
-static std::atomic<int> g_decode_waves{0};  // ns_hip_set_tuning("gv_nw", n)
-void set_decode_waves(int nw) { g_decode_waves.store(nw); }
-int decode_waves(int grid, int ks, bool dual) {
-  // measured on the 7B shapes (profiles/r02g_sweep.txt): 256 tiles x 32 k-steps (attention output) 16 waves, 256 tiles
-  // x 86 k-steps (FFN down) 8 waves (7.5 vs 8.0 us at 16), 768 tiles 4 waves, 2000 tiles (lm_head) 2 waves
-  int nw = (grid <= 320 && ks >= 32 && ks <= 48 && !dual) ? 16 : 8;
-  if (dual) {
-    nw = grid * 4 >= 1300 ? 4 : 8;
-  } else {
-    const int target_waves = 2560;
-    while (nw > 2 && grid * (nw / 2) >= target_waves) nw /= 2;
-  }
-  static const int env_nw0 = getenv("NS_GV_NW") ? atoi(getenv("NS_GV_NW")) : 0;  // diagnostics
-  const int forced = g_decode_waves.load();
-  const int env_nw = forced ? forced : env_nw0;
-  if (env_nw == 2 || env_nw == 4 || env_nw == 8 || (env_nw == 16 && !dual)) nw = env_nw;
-  while (nw > 1 && nw > ks) nw /= 2;
-  return nw;
+hipError_t NS_GV_SLICE_FN(launch_gemv_)(const GemvParams& p, uint32_t scale_dt, bool asym, int mode, int grid, int nw, size_t lds,
+                                        hipStream_t st) {
+  return launch_gemv_slice<kGvSliceKind, NS_GEMV_SPS>(p, scale_dt, asym, mode, grid, nw, lds, st);
 }
-
-// hipErrorNotSupported: outside the kernel's envelope — the caller falls back to smallm_kernel
-static std::atomic<int> g_gemv_planes{-1};  // ns_hip_set_tuning("planes"): 1 (default) = bit-plane formats stream their native records
-void set_gemv_planes(int on) { g_gemv_planes.store(on != 0); }
-static bool gemv_planes() {
-  int v = g_gemv_planes.load();
-  if (v < 0) {
-    const char* e = getenv("NS_GEMV_PLANES");
-    v = e ? atoi(e) != 0 : 1;
-    g_gemv_planes.store(v);
-  }
-  return v != 0;
-}
-
-hipError_t launch_gemv(const SmallMArgs& a, hipStream_t st) {
-  if (gemv_mode() == 0 || a.m < 1 || a.m > kGvMaxRows) return hipErrorNotSupported;
-  const int nmat = a.nseg;  // matrices the launch touches (dual: 2)
-  // bit-plane formats: every matrix of the launch has its native clone (same shapes and scales, shorter code records) -> stream those
-  const bool neox = a.rope && (a.rope->flags & NS_QKV_ROPE_NEOX) != 0;  // the pair mode (GV_MSEGP) streams the widened records
-  bool planes = gemv_planes() && !a.i8 && !a.moe && !neox;
-  for (int i = 0; i < nmat; i++)
-    planes = planes && a.seg[i].w->native && a.seg[i].w->native->scale_dt != DT_F16 && a.seg[i].w->native->pl_bits == a.seg[0].w->native->pl_bits;
-  auto pick = [&](const ns_weight* w) { return planes ? static_cast<const ns_weight*>(w->native) : w; };
-  const ns_weight* w0 = pick(a.seg[0].w);
-  GemvParams p;
-  memset(&p, 0, sizeof(p));
-  uint32_t tiles = 0;
-  uint32_t tbeg[3] = {0, 0xffffffffu, 0xffffffffu};  // absent matrices begin beyond every tile
-  const uint8_t* wb[3] = {nullptr, nullptr, nullptr};
-  uint32_t soff[3] = {0, 0, 0}, zoff[3] = {0, 0, 0};
-  for (int i = 0; i < nmat; i++) {
-    const ns_weight* w = pick(a.seg[i].w);
-    if (!w->single_span || w->alloc_bytes >= (size_t(1) << 31)) return hipErrorNotSupported;
-    wb[i] = reinterpret_cast<const uint8_t*>(w->codes);
-    soff[i] = uint32_t(reinterpret_cast<const uint8_t*>(w->scales) - wb[i]);
-    zoff[i] = w->zps ? uint32_t(reinterpret_cast<const uint8_t*>(w->zps) - wb[i]) : 0u;
-    tbeg[i] = a.dual ? 0u : tiles;
-    if (!a.dual || i == 0) tiles += uint32_t(w->ntiles);
-    p.mat[i] = GemvMat{wb[i], soff[i], zoff[i], tbeg[i], w->n, a.seg[i].c, static_cast<_Float16*>(a.seg[i].c16)};
-  }
-  const bool mseg = !a.dual && nmat > 1;
-  const int mode = a.dual ? GV_DUAL : (mseg ? (neox ? GV_MSEGP : GV_MSEG) : GV_PLAIN);
-  if (neox) {  // whole pairs of tiles per head and matrix: a workgroup per pair
-    const int hs = a.rope->head_size;
-    if (!mseg || nmat != 3 || a.rope_route || hs < 32 || (hs % 32) != 0) return hipErrorInvalidValue;
-    for (int i = 0; i < nmat; i++)
-      if (p.mat[i].n % hs != 0 || uint32_t(p.mat[i].n) != 16u * uint32_t(pick(a.seg[i].w)->ntiles)) return hipErrorInvalidValue;
-    p.pair_tiles = uint32_t(hs / 32);
-    tbeg[1] /= 2, tbeg[2] /= 2;  // in workgroups (p.mat[].tile_begin is not read by the kernel)
-  }
-  p.wbase0 = wb[0];
-  p.wbase1 = wb[1];
-  p.s_off0 = soff[0], p.s_off1 = soff[1], p.z_off0 = zoff[0], p.z_off1 = zoff[1];
-  p.tb1 = mseg ? tbeg[1] : 0xffffffffu;
-  p.tb2 = (mseg && nmat > 2) ? tbeg[2] : 0xffffffffu;
-  const uint32_t ks = uint32_t(w0->ksteps);
-  const int kstep = w0->kstep_len;
-  if (tiles == 0 || ks == 0) return hipErrorNotSupported;
-
-  // staged activations: [rows][ks * KSTEP + 8] halves (int8-reference numerics: [rows][ks * KSTEP + 16] bytes)
-  const int rows = a.m;
-  const bool i8s = a.i8 != nullptr;
-  bool i8q = false;
-  const uint32_t row_stride = i8s ? (ks * uint32_t(kstep) + 16) / 2 : ks * uint32_t(kstep) + 8;
-  const size_t a_bytes = size_t(rows) * row_stride * 2;
-  if (a_bytes > kGvMaxALds) return hipErrorNotSupported;
-  uint32_t i8_shift = 0;
-  if (i8s) {
-    const I8Act& q = *a.i8;
-    const bool int_w = w0->kind == WK_INT4 || w0->kind == WK_INT8;
-    // a 32-deep slice must lie inside one k-block and inside or outside K; block index by shift (one block: any shift >= 31)
-    const bool one_block = q.nblk == 1;
-    while (!one_block && (1u << i8_shift) < uint32_t(q.blocksize)) i8_shift++;
-    if (!int_w || rows > 4 || a.link || a.rope || (w0->k & 31) || !q.aq || !q.corr || (reinterpret_cast<uintptr_t>(q.aq) & 15) ||
-        (reinterpret_cast<uintptr_t>(q.corr) & 15) || (q.ldq & 15) || q.ldq < w0->k ||
-        (!one_block && ((1u << i8_shift) != uint32_t(q.blocksize) || q.blocksize < 32)))
-      return hipErrorNotSupported;
-    if (one_block) i8_shift = 31;
-    // XV = 5: quantize inside the launch when the rows are at hand as fp32 and the k-block is 32 .. 256 columns dividing K
-    static const bool i8q_off = getenv("NS_I8_INKERNEL") && atoi(getenv("NS_I8_INKERNEL")) == 0;  // A-B runs
-    i8q = !i8q_off && q.a32 && !one_block && i8_shift >= 5 && i8_shift <= 8 && w0->k % q.blocksize == 0 && (q.lda32 & 3) == 0 &&
-          (w0->k & 3) == 0 && (reinterpret_cast<uintptr_t>(q.a32) & 15) == 0;
-    if (!i8q && !q.quantized) return hipErrorNotReady;  // the caller runs the quantizer launch (i8_quantize_finish) and comes back
-    p.i8_corr = q.corr;
-    p.i8_nblk = uint32_t(q.nblk);
-    p.i8_span = (uint32_t(rows) * uint32_t(q.nblk) * 5u + 3u) & ~3u;  // whole words: a buffer load drops a word that straddles the bound (the scratch has the slack)
-    p.i8_bshift = i8_shift;
-  }
-  // fp16 activations with 16-byte aligned rows; several rows need K to fill whole k-steps (a row's padding columns
-  // would otherwise read the next row through the descriptor)
-  const bool a16 = (i8s && !i8q) || (!i8s && a.a16 != nullptr && (a.lda & 7) == 0 && (w0->k & 7) == 0 && (reinterpret_cast<uintptr_t>(a.a16) & 15) == 0);
-  // fp32-only callers: converted while staging (XV = 2); not together with a carried norm / fused RoPE, whose producers
-  // always leave a shadow
-  const bool moe = a.moe != nullptr;
-  if (moe && (a.m != 1 || nmat != 1 || a.dual || a.link || a.rope || i8s || a.a16 || !a.moe->table || !a.moe->id)) return hipErrorNotSupported;
-  const bool a32 = i8q || (!i8s && !a16 && a.a != nullptr && !a.link && !a.rope && (a.lda & 3) == 0 && (w0->k & 3) == 0 &&
-                   (reinterpret_cast<uintptr_t>(a.a) & 15) == 0);
-  if (moe && !a32) return hipErrorNotSupported;
-  if ((!a16 && !a32) || (rows > 1 && w0->k % kstep != 0)) return hipErrorNotSupported;
-  p.a = i8q ? static_cast<const void*>(a.i8->a32) : i8s ? static_cast<const void*>(a.i8->aq) : (a16 ? a.a16 : static_cast<const void*>(a.a));
-  // carried RMS norm (ns_norm_link): consumer side stages in_parts floats per row behind A
-  size_t ssq_bytes = 0;
-  if (i8s) ssq_bytes = (size_t(p.i8_span) + 1023) >> 10 << 10;  // the scales / zero points span sits where a carried norm's sums would
-  if (a.link) {
-    const ns_norm_link& k = *a.link;
-    if (k.in_ssq) {
-      if (k.in_parts < 1 || k.in_stride < k.in_parts || (k.in_stride & 3) || (reinterpret_cast<uintptr_t>(k.in_ssq) & 15) ||
-          k.norm_size < 1)
-        return hipErrorInvalidValue;
-      ssq_bytes = size_t(rows) * ((size_t(k.in_parts) * 4 + 1023) >> 10 << 10);
-      if (ssq_bytes > 32 * 1024) return hipErrorNotSupported;  // at most 32 one-KiB pieces (request counter budget)
-      p.in_ssq = k.in_ssq;
-      p.in_parts = uint32_t(k.in_parts), p.in_stride = uint32_t(k.in_stride);
-      p.in_eps = k.eps, p.in_inv_size = 1.0f / float(k.norm_size);
-    }
-    if (k.out_ssq || k.out_gamma) {
-      if (a.dual || nmat != 1 || (k.out_ssq && k.out_stride < w0->ntiles)) return hipErrorInvalidValue;
-      p.out_gamma = k.out_gamma, p.out_ssq = k.out_ssq, p.out_stride = uint32_t(k.out_stride);
-      p.out_ovf = k.out_gamma ? kvm_overflow_word() : nullptr;
-    }
-  }
-  if (a.rope) {
-    const ns_qkv_rope& r = *a.rope;
-    if ((mode != GV_MSEG && mode != GV_MSEGP) || nmat != 3 || r.mode != (neox ? 2 : 0) || r.head_size < 2 || (r.head_size & 1) || r.n_dims != r.head_size ||
-        !r.kcache16 || !r.vcache16 || !r.cos_sin || r.n_past < 0 || p.mat[0].n != r.heads * r.head_size ||
-        p.mat[1].n != r.heads_kv * r.head_size || p.mat[2].n != r.heads_kv * r.head_size)
-      return hipErrorInvalidValue;
-    p.rope.kc = static_cast<_Float16*>(r.kcache16), p.rope.vc = static_cast<_Float16*>(r.vcache16);
-    p.rope.c_sl = r.cache_step_sl, p.rope.c_head = r.cache_step_head;
-    p.rope.head_size = r.head_size, p.rope.n_past = r.n_past;
-    p.rope.cos_sin = reinterpret_cast<const float2*>(r.cos_sin);
-    p.rope.on = 1;
-    if (a.rope_route) {
-      const QkvRopeRoute& q = *a.rope_route;
-      if (rows != 1) return hipErrorInvalidValue;
-      p.rope.kmove = q.kmove, p.rope.kd_pos = q.kd_pos;
-      p.rope.k32 = q.k32, p.rope.v32 = q.v32;
-      p.rope.k32_head = q.k32_head, p.rope.k32_dim = q.k32_dim, p.rope.k32_tok = q.k32_tok;
-      p.rope.v32_head = q.v32_head, p.rope.v32_dim = q.v32_dim, p.rope.v32_tok = q.v32_tok;
-      p.rope.ovf = q.overflow;
-    }
-  }
-  if (uint64_t(rows) * uint64_t(a.lda) * 4 >= (uint64_t(1) << 30)) return hipErrorNotSupported;  // staging offsets
-
-  // waves per workgroup: enough waves on the chip to overlap dequantisation with the stream (as tuned for
-  // smallm_kernel, profiles/r01*); the rings of a workgroup must fit in LDS beside the staged activations
-  const int grid = neox ? int(tiles / 2) : int(tiles);
-  const int nq = (a.dual || neox) ? 2 : 1;
-  const uint32_t sbytes = uint32_t(w0->sps) * (w0->scale_dt == DT_F32 ? 4u : 2u);
-  const uint32_t slot = 1024u + 16u * sbytes + (w0->asym ? 16u * uint32_t(w0->sps) : 0u);
-  auto ring_bytes = [&](int waves) {  // a wave's ring: one slot per item it can have in flight, at least the reduction scratch
-    const uint32_t items = ((ks + uint32_t(waves) - 1) / uint32_t(waves)) * uint32_t(nq);
-    const size_t b = size_t(std::min<uint32_t>(items, uint32_t(kGvPF))) * slot;
-    return std::max<size_t>((b + 15) & ~size_t(15), size_t(nq) * 1024);
-  };
-  // (the pair mode takes the wave count of the GV_MSEG launch of the same weights: the same split of K, the same bits)
-  int nw = decode_waves(int(tiles), int(ks), a.dual);
-  {
-    while (nw > 1 && ((a_bytes + 15) & ~size_t(15)) + ssq_bytes + size_t(nw) * ring_bytes(nw) > kGvMaxLds) nw /= 2;
-  }
-  uint32_t nw_log2 = 0;
-  while ((1 << nw_log2) < nw) nw_log2++;
-  if (a32 && uint64_t(rows) * ((uint64_t(ks) * uint32_t(kstep) * 4u + 1023u) >> 10) > uint64_t(nw) * kGvA32Regs) {
-    if (i8q) return a.i8->quantized ? hipErrorNotSupported : hipErrorNotReady;  // (quantized beforehand it fits: the caller's retry takes XV = 3)
-    return hipErrorNotSupported;  // more fp32 pieces than the waves hold in registers: smallm_kernel stages those
-  }
-
-  p.ks = ks;
-  p.qstride = w0->qstride;
-  p.nw_log2 = nw_log2;
-  p.sstride = w0->sstride;
-  p.zstride = w0->zstride;
-  p.srows = uint32_t(w0->srows);
-  {
-    int mul, shift;
-    if (!srow_params(w0, &mul, &shift)) return hipErrorNotSupported;
-    p.srow_mul = uint32_t(mul), p.srow_shift = uint32_t(shift);
-  }
-  p.m = a.m;
-  p.k = w0->k;
-  p.lda = i8q ? a.i8->lda32 : i8s ? a.i8->ldq : a.lda;
-  p.row_stride = row_stride;
-  p.ssq_off = uint32_t((a_bytes + 15) & ~size_t(15));
-  p.ring_off = p.ssq_off + uint32_t(ssq_bytes);
-  p.c2 = a.c2;
-  p.d = a.d;
-  p.ldc = a.ldc;
-  p.ldd = a.ldd;
-  p.epilogue = a.epilogue;
-  if (w0->kind == WK_F4) f4_lut_planes(w0->lut, &p.lut);
-  p.f8 = f8_consts(w0->qtype);
-#ifdef NS_TRACE
-  p.trace = trace_buffer();
-#endif
-  p.ring_stride = uint32_t(ring_bytes(nw));
-  const size_t lds = size_t(p.ring_off) + size_t(nw) * p.ring_stride;
-  if (lds > kGvMaxLds) return hipErrorNotSupported;
-  if (moe) {
-    p.moe_table = static_cast<const MoeExpertRow*>(a.moe->table);
-    p.moe_id = a.moe->id;
-    p.moe_n = a.moe->n_as;
-  }
-  p.pl_bits = planes ? uint32_t(w0->pl_bits) : 0u;
-  p.pl_lanes = planes ? w0->code_rec / 16u : 64u;
-  const int mode_x = mode | (a32 && !moe ? kGvModeA32 : 0) | (i8s ? kGvModeI8 : 0) | (moe ? kGvModeMoe : 0) | (planes ? kGvModePlanes : 0);
-
-#define NS_DISPATCH(KIND)                                                                       \
-  switch (w0->sps) {                                                                            \
-    case 4: return launch_gemv_s<KIND, 4>(p, w0->scale_dt, w0->asym, mode_x, grid, nw, lds, st);  \
-    case 2: return launch_gemv_s<KIND, 2>(p, w0->scale_dt, w0->asym, mode_x, grid, nw, lds, st);  \
-    default: return launch_gemv_s<KIND, 1>(p, w0->scale_dt, w0->asym, mode_x, grid, nw, lds, st); \
-  }
-  if (w0->kind == WK_INT4) {
-    NS_DISPATCH(WK_INT4)
-  } else if (w0->kind == WK_INT8) {
-    if (w0->sps == 2) return launch_gemv_s<WK_INT8, 2>(p, w0->scale_dt, w0->asym, mode_x, grid, nw, lds, st);
-    return launch_gemv_s<WK_INT8, 1>(p, w0->scale_dt, w0->asym, mode_x, grid, nw, lds, st);
-  } else if (w0->kind == WK_F8) {  // device scales are always fp32 (E8M0 shared exponents are expanded at load)
-    if (w0->sps == 2) return launch_gemv_a<WK_F8, 2, SK_F32>(p, false, mode_x, grid, nw, lds, st);
-    return launch_gemv_a<WK_F8, 1, SK_F32>(p, false, mode_x, grid, nw, lds, st);
-  } else {
-    NS_DISPATCH(WK_F4)
-  }
-#undef NS_DISPATCH
-}
-
-void touch_gemv_module() {
+void NS_GV_SLICE_FN(touch_gemv_)() {  // (an instantiation every slice has)
   hipFuncAttributes fa;
-  (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(gemv_kernel<WK_INT4, 4, SK_BF16, false, GV_PLAIN, 0>));
+  (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(gemv_kernel<kGvSliceKind, NS_GEMV_SPS, SK_F32, false, GV_PLAIN, 0>));
   (void)hipGetLastError();
 }
 }  // namespace ns

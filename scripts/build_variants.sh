@@ -4,19 +4,27 @@
 set -e
 cd "$(dirname "$0")/../neural-speed_amd/csrc"
 mkdir -p ../../variants
+all_objs=$(make -s objs)  # the library's object list, in link order
 for spec in "$@"; do
   name=${spec%%:*}; flags=${spec#*:}
-  # FILES = which kernel sources get the flags (the others are linked from the regular build)
+  # FILES = which kernel sources get the flags (the others are linked from the regular build); ns_gemv = gemv_kernel's slice objects
+  # (ns_gemv_<KIND>_<SPS>.o, defines as in the Makefile) and its host file
   objs=""
-  for f in ns_kernels ns_gemv ns_gemvs ns_gemm ns_attn; do
+  for o in $all_objs; do
+    b=${o%.o}; f=$b; src="$b.hip"
+    case $b in
+      ns_gemv_host) f=ns_gemv; src="-x hip ns_gemv_host.cpp" ;;
+      ns_gemv_*_*) f=ns_gemv; IFS=_ read -r _ _ kind sps <<<"$b"; src="-DNS_GEMV_KIND=$kind -DNS_GEMV_SPS=$sps ns_gemv.hip" ;;
+    esac
     if [[ " ${FILES:-ns_kernels ns_gemv ns_gemm} " == *" $f "* ]]; then
-      /opt/rocm/bin/hipcc -O3 -std=c++20 $flags -fPIC --offload-arch=gfx950 -c $f.hip -o /tmp/${f}_$name.o &
-      objs="$objs /tmp/${f}_$name.o"
+      while (( $(jobs -rp | wc -l) >= ${JOBS:-8} )); do wait -n; done
+      /opt/rocm/bin/hipcc -O3 -std=c++20 $flags -fPIC --offload-arch=gfx950 -c $src -o /tmp/${b}_$name.o &
+      objs="$objs /tmp/${b}_$name.o"
     else
-      objs="$objs $f.o"
+      objs="$objs $o"
     fi
   done
   wait
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../../variants/libns_hip_$name.so ns_api.o ns_blob.o ns_split.o ns_tp.o ns_route.o $objs ns_quant.o ns_p2p.o ns_i8ref.o ns_i8g2_n4.o ns_i8g2_n2.o ns_i8g2_n1.o ns_i8g2_b2.o ns_i8g2_b1.o ns_moe.o ns_device.o -ldl
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../../variants/libns_hip_$name.so $objs -ldl
   echo built variants/libns_hip_$name.so
 done
