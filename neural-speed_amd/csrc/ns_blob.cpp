@@ -35,7 +35,7 @@ inline size_t round_up(size_t a, size_t b) { return ceil_div(a, b) * b; }
 
 // A cursor that either reads the header words out of a blob or lays a new header down.  The words are scattered
 // between the payload sections, so access goes through a callback: plain memcpy for host blobs, small
-// hipMemcpy's for blobs that live in device memory (ns_api.cpp).
+// hipMemcpy's for blobs that live in device memory (ns_weights.cpp, ns_host_entry.cpp).
 class HeaderIO {
  public:
   HeaderIO(const BlobIo& io, uintptr_t base_addr, bool writing) : io_(io), pos_(0), addr_(base_addr), w_(writing) {}

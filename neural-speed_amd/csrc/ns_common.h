@@ -323,7 +323,7 @@ extern thread_local Affine g_affine;
 // ... and the device-layout attention may be asked for an fp16 copy of its output row beside the fp32 one (the carried norm of the route's
 // attention-output projection needs the fp16 shadow of its activations): set around the captured call, nullptr otherwise
 extern thread_local void* g_mha_out16;
-// ns_api.cpp: may this weight's decode launch carry an RMS norm (ns_norm_link)?  (what link_ok() refuses, without setting an error)
+// ns_dispatch.cpp: may this weight's decode launch carry an RMS norm (ns_norm_link)?  (what link_ok() refuses, without setting an error)
 bool route_link_weight_ok(const ns_weight* w);
 // ns_route.cpp: one launch of the reference's device route as plain data (compared bytewise: zero-initialise before filling)
 enum RouteKind : uint32_t { RK_GEMM = 1, RK_ADD, RK_MUL, RK_SILU, RK_RMSNORM, RK_ROPE, RK_ROPE_YARN, RK_DUP, RK_MHA };
@@ -355,7 +355,7 @@ hipError_t launch_rope_glm(const float* src, float* dst, int batch, int seq, int
                            bool skip, float freq_base, int prompt_size, const int* n_padding, hipStream_t st);
 hipError_t launch_rope_cos_sin(int m, int n_past, int n_dims, float freq_base, float freq_scale, float attn_factor,
                                float* out, hipStream_t st, bool neox = false);  // (n_past follows g_affine inside a route capture; neox: the mode-2 angles)
-// ns_api.cpp: the fused QKV + RoPE + cache-write launch of a replayed token: weights by ROLE, each result at its own tensor
+// ns_dispatch.cpp: the fused QKV + RoPE + cache-write launch of a replayed token: weights by ROLE, each result at its own tensor
 int qkv_rope_route_forward_m(const float* dA, const void* dA16, const ns_weight* wq, const ns_weight* wk, const ns_weight* wv, float* cq, float* ck, float* cv, int m,
                              int lda, int ldc, const ns_qkv_rope* rope, hipStream_t st);  // a window's prompt-sized form (-2: shape not taken)
 extern thread_local bool g_mha_out16_written;  // the device-layout attention wrote the fp16 copy it was asked for (g_mha_out16)
