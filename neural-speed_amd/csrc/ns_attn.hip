@@ -33,6 +33,7 @@
 
 #include "../../include/ns_bestla.h"
 #include "ns_common.h"
+#include "ns_launch.h"
 
 namespace ns {
 
@@ -822,20 +823,8 @@ static bool attn_streams(const AttnParams& a) {
 template <int G>
 static hipError_t launch_split_g(const AttnSplitParams& sp, dim3 grid, hipStream_t st, bool stream) {
   const int hs = sp.a.head_size;
-  if (stream && hs > 64) {
-    static const hipError_t attr =
-        hipFuncSetAttribute(reinterpret_cast<const void*>(attn_stream_kernel<G, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, int(kAsLdsBytes));
-    if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL((attn_stream_kernel<G, 16>), grid, dim3(kAttnThreads), kAsLdsBytes, st, sp);
-    return hipGetLastError();
-  }
-  if (stream) {  // head sizes 40 .. 64: eight lanes per key
-    static const hipError_t attr =
-        hipFuncSetAttribute(reinterpret_cast<const void*>(attn_stream_kernel<G, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, int(kAsLdsBytes));
-    if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL((attn_stream_kernel<G, 8>), grid, dim3(kAttnThreads), kAsLdsBytes, st, sp);
-    return hipGetLastError();
-  }
+  if (stream && hs > 64) return launch_lds<attn_stream_kernel<G, 16>>(int(kAsLdsBytes), grid, dim3(kAttnThreads), kAsLdsBytes, st, sp);
+  if (stream) return launch_lds<attn_stream_kernel<G, 8>>(int(kAsLdsBytes), grid, dim3(kAttnThreads), kAsLdsBytes, st, sp);  // head sizes 40 .. 64: eight lanes per key
   if (hs <= 128) {
     hipLaunchKernelGGL((attn_split_kernel<G, 8>), grid, dim3(kAttnThreads), size_t(4) * G * 128 * 4, st, sp);
   } else {
@@ -1801,11 +1790,8 @@ static hipError_t launch_attn(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, hipS
                           a.step_dst_bs % 4 == 0 && (!dst16 || (reinterpret_cast<uintptr_t>(dst16) & 7) == 0);
       static const bool no_xcd = getenv("NS_ATTN_NO_XCD_MAP") != nullptr;  // diagnostics (A/B)
       const int xcd_map = !no_xcd && (size_t(a.heads_kv) * a.batch_size) % 8 == 0;
-      auto go = [&](auto kern, int stage, int extra = 0) {
-        static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * stage);
-        if (attr != hipSuccess) return attr;
-        hipLaunchKernelGGL(kern, dim3(unsigned(wgs2)), dim3(256), size_t(2) * stage, st, p, int(nqb), aligned, xcd_map | extra);
-        return hipGetLastError();
+      auto go = [&](auto kern_c, int stage, int extra = 0) {  // (kernel_c: the kernel is part of the argument's type, so each has its own LDS limit)
+        return launch_lds<decltype(kern_c)::value>(2 * stage, dim3(unsigned(wgs2)), dim3(256), size_t(2) * stage, st, p, int(nqb), aligned, xcd_map | extra);
       };
       const bool pad = a.head_size != 64 && a.head_size != 128 && a.head_size != 256;
       // round 6: the pipelined schedule (attn_mfma3_kernel) for the exact head sizes without score bias; rows inside a 32-bit buffer descriptor
@@ -1817,14 +1803,14 @@ static hipError_t launch_attn(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, hipS
       const int pvar = pvar_env >= 0 ? pvar_env : (a.sl_kv >= 3072 ? 3 : 0);
       const bool in32 = (size_t(a.sl_kv) * size_t(a.step_k_sl) + 256) * 2 < (size_t(1) << 32) && (size_t(a.sl_kv) * size_t(a.step_v_sl) + 256) * 2 < (size_t(1) << 32);
       if (pipe && !biased && !pad && !hs256 && in32)
-        return a.head_size == 64 ? go(attn_mfma3_kernel<64>, a2_stage_bytes<64>(), pvar << 8) : go(attn_mfma3_kernel<128>, a2_stage_bytes<128>(), pvar << 8);
+        return a.head_size == 64 ? go(kernel_c<attn_mfma3_kernel<64>>{}, a2_stage_bytes<64>(), pvar << 8) : go(kernel_c<attn_mfma3_kernel<128>>{}, a2_stage_bytes<128>(), pvar << 8);
       if (hs256)
-        return biased ? (pad ? go(attn_mfma2_hs256_kernel<true, true>, a2_stage_bytes<256>()) : go(attn_mfma2_hs256_kernel<true, false>, a2_stage_bytes<256>()))
-                      : (pad ? go(attn_mfma2_hs256_kernel<false, true>, a2_stage_bytes<256>()) : go(attn_mfma2_hs256_kernel<false, false>, a2_stage_bytes<256>()));
+        return biased ? (pad ? go(kernel_c<attn_mfma2_hs256_kernel<true, true>>{}, a2_stage_bytes<256>()) : go(kernel_c<attn_mfma2_hs256_kernel<true, false>>{}, a2_stage_bytes<256>()))
+                      : (pad ? go(kernel_c<attn_mfma2_hs256_kernel<false, true>>{}, a2_stage_bytes<256>()) : go(kernel_c<attn_mfma2_hs256_kernel<false, false>>{}, a2_stage_bytes<256>()));
       auto pick = [&](auto hs_c) {
         constexpr int H = decltype(hs_c)::value;
-        if (biased) return pad ? go(attn_mfma2_kernel<H, true, true>, a2_stage_bytes<H>()) : go(attn_mfma2_kernel<H, true, false>, a2_stage_bytes<H>());
-        return pad ? go(attn_mfma2_kernel<H, false, true>, a2_stage_bytes<H>()) : go(attn_mfma2_kernel<H, false, false>, a2_stage_bytes<H>());
+        if (biased) return pad ? go(kernel_c<attn_mfma2_kernel<H, true, true>>{}, a2_stage_bytes<H>()) : go(kernel_c<attn_mfma2_kernel<H, true, false>>{}, a2_stage_bytes<H>());
+        return pad ? go(kernel_c<attn_mfma2_kernel<H, false, true>>{}, a2_stage_bytes<H>()) : go(kernel_c<attn_mfma2_kernel<H, false, false>>{}, a2_stage_bytes<H>());
       };
       return a.head_size <= 64 ? pick(std::integral_constant<int, 64>{}) : pick(std::integral_constant<int, 128>{});
     }

@@ -69,6 +69,9 @@ void blob_write_header_io(const BlobView& v, const BlobIo& io, uintptr_t base_ad
 
 // ---- device weight -------------------------------------------------------------------------------------------
 enum WKind { WK_INT4 = 0, WK_INT8 = 1, WK_F4 = 2, WK_F8 = 3 };
+constexpr bool kind_is_8bit(int kind) { return kind == WK_INT8 || kind == WK_F8; }
+// type of the scales as the kernels are instantiated for it (template argument SK; with_scales, ns_launch.h)
+enum ScaleKind { SK_BF16 = 0, SK_F16 = 1, SK_F32 = 2 };
 
 }  // namespace ns
 

@@ -1,7 +1,11 @@
-// ns_dev.h — device-side helpers shared by the gfx950 kernels of libns_hip.so (ns_kernels.hip, ns_gemv.hip, ns_gemm.hip):
-// code -> fp16 converters, raw scale / zero-point records, buffer-descriptor loads, epilogue activations.
+// ns_dev.h — device-side helpers shared by the gfx950 kernels of libns_hip.so (ns_kernels.hip, ns_gemv.hip, ns_gemvs.hip, ns_gemm.hip,
+// ns_moe.hip, ns_i8ref.hip, ns_i8g2.hip): code -> fp16 converters, raw scale / zero-point records, buffer-descriptor loads, the output
+// epilogue (epi_apply), the slot loop of the prefetch rings (NS_FOR_SLOTS).  The host side of a launch is in ns_launch.h.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
+#include <utility>
 
 #include "ns_common.h"
 
@@ -104,7 +108,6 @@ __device__ __forceinline__ half8_t cvt_u8x8(uint32_t a, uint32_t b, half2_t off)
 //                   bits 0x200 + (m << 7) — both cases are max(u, (u >> 1) + 0x200)
 // so one formula with two constants covers both: abs = max(u & M, (u >> 1) + C);  E4M3: C = 0x2000, M = 0;
 // E5M2: C = 0x0200, M = 0xffff.  v_mfma_f32_16x16x32_f16 keeps fp16 subnormal inputs (default kernel mode).
-constexpr bool kind_is_8bit(int kind) { return kind == WK_INT8 || kind == WK_F8; }
 struct F8Consts {
   uint32_t c2, m2;  // C and M replicated into both 16-bit halves
 };
@@ -148,7 +151,6 @@ __device__ __forceinline__ half8_t cvt_f4x8(uint32_t x, const F4Lut& lut) {
 }
 
 // raw (unconverted) per-k-step correction words of one lane: loaded early, converted at use
-enum ScaleKind { SK_BF16 = 0, SK_F16 = 1, SK_F32 = 2 };
 template <int SPS, int SK, bool ASYM>
 struct CorrRaw {
   static constexpr bool S32 = SK == SK_F32;
@@ -247,6 +249,26 @@ __device__ __forceinline__ float epi_gelu(float x) {  // kernel_ref.h:1570-1572
   return 0.5f * x * (1.f + tanhf(0.7978845834732056f * (x + 0.044714998453855515f * x * x * x)));
 }
 __device__ __forceinline__ float epi_silu(float x) { return x / (1.f + expf(-x)); }  // kernel_ref.h:1573-1575
+// the output operator of a launch (enum ns_epilogue): v = the matrix product's element, dv = the D operand's (0 when there is none)
+__device__ __forceinline__ float epi_apply(float v, float dv, int epilogue) {
+  switch (epilogue) {
+    case 1: return v + dv;            // custom::epilogue::Add
+    case 2: return v * dv;            // custom::epilogue::Mul
+    case 3: return epi_gelu(v + dv);  // custom::epilogue::Add_Gelu
+    case 4: return epi_gelu(v);
+    case 5: return epi_silu(v);
+    default: return v;
+  }
+}
+
+// compile-time loop over the PF slots of a wave's prefetch ring: BODY runs once per slot with i (constexpr int) and ic
+// (std::integral_constant) naming it; PF is the enclosing kernel's
+#define NS_FOR_SLOTS(BODY)                                        \
+  {                                                               \
+    [&]<int... I>(std::integer_sequence<int, I...>) {             \
+      (([&] { constexpr int i = I; std::integral_constant<int, I> ic; (void)i; (void)ic; BODY }()), ...); \
+    }(std::make_integer_sequence<int, PF>{});                     \
+  }
 
 // host side: fp16 LUT -> byte planes of F4Lut
 inline void f4_lut_planes(const _Float16* lut, F4Lut* out) {

@@ -32,6 +32,7 @@
 
 #include "../../include/ns_bestla.h"
 #include "ns_common.h"
+#include "ns_launch.h"
 #include "ns_route.h"
 
 namespace ns {
@@ -1215,16 +1216,9 @@ int ns_hip_mha_f32_device_layout(const float* dQ, const float* dK, const float* 
     ns::set_error("mha_f32: context too long for the device-layout attention kernel");
     return -1;
   }
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(ns::mha_f32_kernel),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (attr != hipSuccess && lds > 64 * 1024) {
-    ns::set_error("mha_f32: cannot raise the LDS limit");
-    return -1;
-  }
-  hipLaunchKernelGGL(ns::mha_f32_kernel, dim3(heads, seq, batch), dim3(256), lds, static_cast<hipStream_t>(stream), dQ, dK, dV, dO, seq,
-                     seq_all, heads, heads_kv, head_size, n_ctx, scale, masked);
-  if (hipGetLastError() != hipSuccess) {
-    ns::set_error("mha_f32: launch failed");
+  if (ns::launch_lds<ns::mha_f32_kernel>(160 * 1024, dim3(heads, seq, batch), dim3(256), lds, static_cast<hipStream_t>(stream), dQ, dK, dV, dO, seq, seq_all,
+                                         heads, heads_kv, head_size, n_ctx, scale, masked) != hipSuccess) {
+    ns::set_error("mha_f32: launch failed, or the LDS limit it needs could not be raised");
     return -1;
   }
   return 0;

@@ -27,6 +27,7 @@
 #include "../../include/ns_bestla.h"
 #include "ns_common.h"
 #include "ns_dev.h"
+#include "ns_launch.h"
 
 namespace ns {
 
@@ -287,14 +288,7 @@ __global__ __launch_bounds__(256, NS_G2_OCC) void gemm2_kernel(const Gemm2Params
           continue;
         }
         const float dv = p.d ? p.d[size_t(row) * p.ldd + col] : 0.f;
-        switch (p.epilogue) {
-          case 1: v = v + dv; break;            // custom::epilogue::Add
-          case 2: v = v * dv; break;            // custom::epilogue::Mul
-          case 3: v = epi_gelu(v + dv); break;  // custom::epilogue::Add_Gelu
-          case 4: v = epi_gelu(v); break;
-          case 5: v = epi_silu(v); break;
-          default: break;
-        }
+        v = epi_apply(v, dv, p.epilogue);
         p.c[size_t(row) * p.ldc + col] = v;
         if (p.c16) p.c16[size_t(row) * p.ldc + col] = (_Float16)v;
       }
@@ -823,16 +817,6 @@ __global__ __launch_bounds__(256, (BM == 256 ? 2 : 3)) void gemm3_kernel(const G
   //      (nothing below indexes the accumulators dynamically — with the switch inside the unrolled accumulator loops hipcc
   //      kept all 128 accumulator registers in scratch memory, a store behind every MFMA of the main loop). ----
   const int epi = p.epilogue;
-  auto finish = [&](float v, float dv) {
-    switch (epi) {
-      case 1: return v + dv;            // custom::epilogue::Add
-      case 2: return v * dv;            // custom::epilogue::Mul
-      case 3: return epi_gelu(v + dv);  // custom::epilogue::Add_Gelu
-      case 4: return epi_gelu(v);
-      case 5: return epi_silu(v);
-      default: return v;
-    }
-  };
   // ---- the cross-wave form of that epilogue (round 5; waves 1 x 4).  Measured on the 7B shapes at 2048 rows (profiles/r05a_prefill_probe.txt):
   //      with the stores skipped a 11008-wide GEMM takes 184 us, with the fp32 stores 187, with fp32 + the fp16 shadow 205 — the shadow left
   //      each wave as 8-byte stores in 64-byte runs (half a memory line).  Here the four waves park their 64-row halves side by side
@@ -864,13 +848,13 @@ __global__ __launch_bounds__(256, (BM == 256 ? 2 : 3)) void gemm3_kernel(const G
         float4 v = *reinterpret_cast<const float4*>(q);
         if constexpr (DUAL) {
           const float4 u = *reinterpret_cast<const float4*>(q + 16);
-          v = float4{finish(v.x, 0.f), finish(v.y, 0.f), finish(v.z, 0.f), finish(v.w, 0.f)};
+          v = float4{epi_apply(v.x, 0.f, epi), epi_apply(v.y, 0.f, epi), epi_apply(v.z, 0.f, epi), epi_apply(v.w, 0.f, epi)};
           if (gate4) *gate4 = v;
           v = float4{v.x * u.x, v.y * u.y, v.z * u.z, v.w * u.w};
         } else {
           float4 dv = {0.f, 0.f, 0.f, 0.f};
           if (use_d) dv = *reinterpret_cast<const float4*>(p.d + size_t(row) * p.ldd + colb + oc);
-          v = float4{finish(v.x, dv.x), finish(v.y, dv.y), finish(v.z, dv.z), finish(v.w, dv.w)};
+          v = float4{epi_apply(v.x, dv.x, epi), epi_apply(v.y, dv.y, epi), epi_apply(v.z, dv.z, epi), epi_apply(v.w, dv.w, epi)};
         }
         return v;
       };
@@ -916,11 +900,11 @@ __global__ __launch_bounds__(256, (BM == 256 ? 2 : 3)) void gemm3_kernel(const G
             const float* q = parkw + (w * 16 + rl) * WROW + pcol(oc);
             float v = q[0];
             if constexpr (DUAL) {
-              v = finish(v, 0.f);
+              v = epi_apply(v, 0.f, epi);
               if (p.c2) p.c2[size_t(row) * p.ldc + col] = v;
               v *= q[16];
             } else {
-              v = finish(v, use_d ? p.d[size_t(row) * p.ldd + col] : 0.f);
+              v = epi_apply(v, use_d ? p.d[size_t(row) * p.ldd + col] : 0.f, epi);
             }
             if (c_out) c_out[size_t(row) * p.ldc + col] = v;
             if (c16_out) c16_out[size_t(row) * p.ldc + col] = (_Float16)v;
@@ -1012,7 +996,7 @@ __global__ __launch_bounds__(256, (BM == 256 ? 2 : 3)) void gemm3_kernel(const G
         }
         float4 dv = {0.f, 0.f, 0.f, 0.f};
         if (p.d && epi >= 1 && epi <= 3) dv = *reinterpret_cast<const float4*>(p.d + size_t(row) * p.ldd + col);
-        v = float4{finish(v.x, dv.x), finish(v.y, dv.y), finish(v.z, dv.z), finish(v.w, dv.w)};
+        v = float4{epi_apply(v.x, dv.x, epi), epi_apply(v.y, dv.y, epi), epi_apply(v.z, dv.z, epi), epi_apply(v.w, dv.w, epi)};
         if (c_out) *reinterpret_cast<float4*>(c_out + size_t(row) * p.ldc + col) = v;
         if (c16_out) {
           typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
@@ -1031,7 +1015,7 @@ __global__ __launch_bounds__(256, (BM == 256 ? 2 : 3)) void gemm3_kernel(const G
           continue;
         }
         const float dv = (p.d && epi >= 1 && epi <= 3) ? p.d[size_t(row) * p.ldd + col] : 0.f;
-        v = finish(v, dv);
+        v = epi_apply(v, dv, epi);
         if (c_out) c_out[size_t(row) * p.ldc + col] = v;
         if (c16_out) c16_out[size_t(row) * p.ldc + col] = (_Float16)v;
       }
@@ -1331,16 +1315,6 @@ __global__ __launch_bounds__(kG3dThreads, 1) void gemm3d_kernel(const Gemm2Param
                     (!p.d || ((p.ldd & 3) == 0 && (reinterpret_cast<uintptr_t>(p.d) & 15) == 0)) &&
                     (!p.c16 || (reinterpret_cast<uintptr_t>(p.c16) & 7) == 0);
   const int epi = p.epilogue;
-  auto finish = [&](float v, float dv) {
-    switch (epi) {
-      case 1: return v + dv;
-      case 2: return v * dv;
-      case 3: return epi_gelu(v + dv);
-      case 4: return epi_gelu(v);
-      case 5: return epi_silu(v);
-      default: return v;
-    }
-  };
 #pragma unroll
   for (int hh = 0; hh < 2; hh++) {
 #pragma unroll
@@ -1362,7 +1336,7 @@ __global__ __launch_bounds__(kG3dThreads, 1) void gemm3d_kernel(const Gemm2Param
         }
         float4 dv = {0.f, 0.f, 0.f, 0.f};
         if (p.d && epi >= 1 && epi <= 3) dv = *reinterpret_cast<const float4*>(p.d + size_t(row) * p.ldd + col);
-        v = float4{finish(v.x, dv.x), finish(v.y, dv.y), finish(v.z, dv.z), finish(v.w, dv.w)};
+        v = float4{epi_apply(v.x, dv.x, epi), epi_apply(v.y, dv.y, epi), epi_apply(v.z, dv.z, epi), epi_apply(v.w, dv.w, epi)};
         *reinterpret_cast<float4*>(p.c + size_t(row) * p.ldc + col) = v;
         if (p.c16) {
           typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
@@ -1380,7 +1354,7 @@ __global__ __launch_bounds__(kG3dThreads, 1) void gemm3d_kernel(const Gemm2Param
           continue;
         }
         const float dv = (p.d && epi >= 1 && epi <= 3) ? p.d[size_t(row) * p.ldd + col] : 0.f;
-        v = finish(v, dv);
+        v = epi_apply(v, dv, epi);
         p.c[size_t(row) * p.ldc + col] = v;
         if (p.c16) p.c16[size_t(row) * p.ldc + col] = (_Float16)v;
       }
@@ -1398,14 +1372,7 @@ __global__ void gemm2_reduce_kernel(const Gemm2Params p) {
   float v = 0.f;
   for (int z = 0; z < p.ksplit; z++) v += p.part[(size_t(z) * p.m + row) * p.n + col];
   const float dv = p.d ? p.d[size_t(row) * p.ldd + col] : 0.f;
-  switch (p.epilogue) {
-    case 1: v = v + dv; break;
-    case 2: v = v * dv; break;
-    case 3: v = epi_gelu(v + dv); break;
-    case 4: v = epi_gelu(v); break;
-    case 5: v = epi_silu(v); break;
-    default: break;
-  }
+  v = epi_apply(v, dv, p.epilogue);
   p.c[size_t(row) * p.ldc + col] = v;
   if (p.c16) p.c16[size_t(row) * p.ldc + col] = (_Float16)v;
 }
@@ -1519,31 +1486,21 @@ void gemm_scratch_release() {
   g_scratch_retired.clear();
 }
 
-template <int KIND, int SPS, int SK>
-static hipError_t launch_gemm2_k(const Gemm2Params& p, bool asym, dim3 grid, size_t lds, hipStream_t st) {
-  auto go = [&](auto kern) {
-    static const hipError_t attr =
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(kG2Stages * kG2StageBytes));
-    if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, p);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && p.ksplit > 1) {
-      const size_t total = size_t(p.m) * p.n;
-      hipLaunchKernelGGL(gemm2_reduce_kernel, dim3(unsigned((total + 255) / 256)), dim3(256), 0, st, p);
-      e = hipGetLastError();
-    }
-    return e;
-  };
-  if constexpr (KIND == WK_F4) {
-    (void)asym;
-    return go(gemm2_kernel<KIND, SPS, SK, false>);
-  } else {
-    if (asym) return go(gemm2_kernel<KIND, SPS, SK, true>);
-    return go(gemm2_kernel<KIND, SPS, SK, false>);
+// the reduction pass of a launch that split K (e: the result of the main launch)
+static hipError_t gemm2_reduce(hipError_t e, const Gemm2Params& p, hipStream_t st) {
+  if (e == hipSuccess && p.ksplit > 1) {
+    const size_t total = size_t(p.m) * p.n;
+    hipLaunchKernelGGL(gemm2_reduce_kernel, dim3(unsigned((total + 255) / 256)), dim3(256), 0, st, p);
+    e = hipGetLastError();
   }
+  return e;
 }
-template <int KIND, int SPS, int SK, int BM, bool TALL = false, bool DUAL = false>
-static hipError_t launch_gemm3_k(const Gemm2Params& p, bool asym, dim3 grid, hipStream_t st) {
+template <int KIND, int SPS, int SK, bool ASYM>
+static hipError_t launch_gemm2_k(const Gemm2Params& p, dim3 grid, size_t lds, hipStream_t st) {
+  return gemm2_reduce(launch_lds<gemm2_kernel<KIND, SPS, SK, ASYM>>(int(kG2Stages * kG2StageBytes), grid, dim3(256), lds, st, p), p, st);
+}
+template <int KIND, int SPS, int SK, bool ASYM, int BM, bool TALL, bool DUAL>
+static hipError_t launch_gemm3_k(const Gemm2Params& p, dim3 grid, hipStream_t st) {
   // A stages + the B stage of this format: records, scale rows, zero-point rows of 8 column tiles for one superstep
   constexpr int rps = kind_is_8bit(KIND) ? 2 : 1;
   constexpr int sbytes = SPS * (SK == SK_F32 ? 4 : 2);
@@ -1553,118 +1510,44 @@ static hipError_t launch_gemm3_k(const Gemm2Params& p, bool asym, dim3 grid, hip
   // the cross-wave epilogue (waves 1 x 4) parks 64 rows of the whole tile width: 128 columns (64 for gate/up pairs) + 4
   constexpr size_t park_wide = (BM == 256 && !TALL) ? 0 : size_t(64) * (128 + 4) * 4;
   const size_t park_bytes = std::max(park_old, p.wide ? park_wide : size_t(0));
-  const size_t lds3 = std::max(size_t(kG3Stages) * BM * kG3KC * 2 + size_t(kG3Tiles) * rps * (1024 + 16 * sbytes + (asym ? 16 * SPS : 0)), park_bytes);
-  auto go = [&](auto kern) {
-    static const hipError_t attr =
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(kG3Stages * kG3StageBytes + kG3BStageMax));
-    if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds3, st, p);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && p.ksplit > 1) {
-      const size_t total = size_t(p.m) * p.n;
-      hipLaunchKernelGGL(gemm2_reduce_kernel, dim3(unsigned((total + 255) / 256)), dim3(256), 0, st, p);
-      e = hipGetLastError();
-    }
-    return e;
-  };
-  if constexpr (KIND == WK_F4 || KIND == WK_F8) {
-    (void)asym;
-    return go(gemm3_kernel<KIND, SPS, SK, false, BM, TALL, DUAL>);
-  } else {
-    if (asym) return go(gemm3_kernel<KIND, SPS, SK, true, BM, TALL, DUAL>);
-    return go(gemm3_kernel<KIND, SPS, SK, false, BM, TALL, DUAL>);
-  }
+  const size_t lds3 = std::max(size_t(kG3Stages) * BM * kG3KC * 2 + size_t(kG3Tiles) * rps * (1024 + 16 * sbytes + (ASYM ? 16 * SPS : 0)), park_bytes);
+  return gemm2_reduce(launch_lds<gemm3_kernel<KIND, SPS, SK, ASYM, BM, TALL, DUAL>>(int(kG3Stages * kG3StageBytes + kG3BStageMax), grid, dim3(256), lds3, st, p), p, st);
 }
 #ifdef NS_WITH_GEMM3D
-template <int KIND, int SPS, int SK>
-static hipError_t launch_gemm3d_k(const Gemm2Params& p, bool asym, dim3 grid, hipStream_t st) {
+template <int KIND, int SPS, int SK, bool ASYM>
+static hipError_t launch_gemm3d_k(const Gemm2Params& p, dim3 grid, hipStream_t st) {
   constexpr int rps = KIND == WK_INT8 ? 2 : 1;
   constexpr int ns = KIND == WK_INT8 ? 3 : 4;
   constexpr int sbytes = SPS * (SK == SK_F32 ? 4 : 2);
-  const size_t ldsd = size_t(ns) * kG3StageBytes + 2 * size_t(kG3Tiles) * rps * (1024 + 16 * sbytes + (asym ? 16 * SPS : 0));
-  auto go = [&](auto kern) {
-    static const hipError_t attr =
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL(kern, grid, dim3(kG3dThreads), ldsd, st, p);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && p.ksplit > 1) {
-      const size_t total = size_t(p.m) * p.n;
-      hipLaunchKernelGGL(gemm2_reduce_kernel, dim3(unsigned((total + 255) / 256)), dim3(256), 0, st, p);
-      e = hipGetLastError();
-    }
-    return e;
-  };
-  if constexpr (KIND == WK_F4) {
-    (void)asym;
-    return go(gemm3d_kernel<KIND, SPS, SK, false>);
-  } else {
-    if (asym) return go(gemm3d_kernel<KIND, SPS, SK, true>);
-    return go(gemm3d_kernel<KIND, SPS, SK, false>);
-  }
+  const size_t ldsd = size_t(ns) * kG3StageBytes + 2 * size_t(kG3Tiles) * rps * (1024 + 16 * sbytes + (ASYM ? 16 * SPS : 0));
+  return gemm2_reduce(launch_lds<gemm3d_kernel<KIND, SPS, SK, ASYM>>(160 * 1024, grid, dim3(kG3dThreads), ldsd, st, p), p, st);
 }
 #endif
-template <int KIND, int SPS>
-static hipError_t launch_gemm3_s(const Gemm2Params& p, uint32_t scale_dt, bool asym, dim3 grid, hipStream_t st, bool deep) {
+// gemm3_kernel for w0's format (with_format, ns_launch.h); the tile form (BM, TALL, DUAL) is chosen once, from what launch_gemm2 set
+// in p.  deep: gemm3d_kernel instead (NS_WITH_GEMM3D builds; it has no fp8 form)
+static hipError_t launch_gemm3(const Gemm2Params& p, const ns_weight* w0, dim3 grid, hipStream_t st, bool deep) {
+  return with_format(w0->kind, w0->sps, w0->scale_dt, w0->asym, [&](auto kind_c, auto sps_c, auto sk_c, auto asym_c) {
+    constexpr int KIND = kind_c, SPS = sps_c, SK = sk_c;
+    constexpr bool ASYM = asym_c;
 #ifdef NS_WITH_GEMM3D
-  if (deep) {
-    if (scale_dt == DT_F32) return launch_gemm3d_k<KIND, SPS, SK_F32>(p, asym, grid, st);
-    if (scale_dt == DT_F16) return launch_gemm3d_k<KIND, SPS, SK_F16>(p, asym, grid, st);
-    return launch_gemm3d_k<KIND, SPS, SK_BF16>(p, asym, grid, st);
-  }
+    if constexpr (KIND != WK_F8)
+      if (deep) return launch_gemm3d_k<KIND, SPS, SK, ASYM>(p, grid, st);
 #else
-  (void)deep;
+    (void)deep;
 #endif
-  if (p.dual) {  // gate/up pairs: the 1 x 4 wave tiles only
-    if (p.bm3 == 64) {
-      if (scale_dt == DT_F32) return launch_gemm3_k<KIND, SPS, SK_F32, 64, false, true>(p, asym, grid, st);
-      if (scale_dt == DT_F16) return launch_gemm3_k<KIND, SPS, SK_F16, 64, false, true>(p, asym, grid, st);
-      return launch_gemm3_k<KIND, SPS, SK_BF16, 64, false, true>(p, asym, grid, st);
+    auto tile = [&](auto bm_c, auto tall_c, auto dual_c) { return launch_gemm3_k<KIND, SPS, SK, ASYM, bm_c, tall_c, dual_c>(p, grid, st); };
+    constexpr std::true_type yes;
+    constexpr std::false_type no;
+    if (p.dual) {  // gate/up pairs: the 1 x 4 wave tiles only
+      if (p.bm3 == 64) return tile(int_c<64>{}, no, yes);
+      return tile(int_c<128>{}, no, yes);
     }
-    if (scale_dt == DT_F32) return launch_gemm3_k<KIND, SPS, SK_F32, 128, false, true>(p, asym, grid, st);
-    if (scale_dt == DT_F16) return launch_gemm3_k<KIND, SPS, SK_F16, 128, false, true>(p, asym, grid, st);
-    return launch_gemm3_k<KIND, SPS, SK_BF16, 128, false, true>(p, asym, grid, st);
-  }
-  if (p.bm3 == 64) {  // calls of at most 64 rows: a quarter / half of the 128-row tile's MFMA work is padding otherwise
-    if (scale_dt == DT_F32) return launch_gemm3_k<KIND, SPS, SK_F32, 64>(p, asym, grid, st);
-    if (scale_dt == DT_F16) return launch_gemm3_k<KIND, SPS, SK_F16, 64>(p, asym, grid, st);
-    return launch_gemm3_k<KIND, SPS, SK_BF16, 64>(p, asym, grid, st);
-  }
-  if (p.bm3 == 128) {
-    if (scale_dt == DT_F32) return launch_gemm3_k<KIND, SPS, SK_F32, 128>(p, asym, grid, st);
-    if (scale_dt == DT_F16) return launch_gemm3_k<KIND, SPS, SK_F16, 128>(p, asym, grid, st);
-    return launch_gemm3_k<KIND, SPS, SK_BF16, 128>(p, asym, grid, st);
-  }
-  if constexpr (KIND == WK_INT4) {
-    if (p.tall3) {
-      if (scale_dt == DT_F32) return launch_gemm3_k<KIND, SPS, SK_F32, 256, true>(p, asym, grid, st);
-      if (scale_dt == DT_F16) return launch_gemm3_k<KIND, SPS, SK_F16, 256, true>(p, asym, grid, st);
-      return launch_gemm3_k<KIND, SPS, SK_BF16, 256, true>(p, asym, grid, st);
-    }
-  }
-  if (scale_dt == DT_F32) return launch_gemm3_k<KIND, SPS, SK_F32, 256>(p, asym, grid, st);
-  if (scale_dt == DT_F16) return launch_gemm3_k<KIND, SPS, SK_F16, 256>(p, asym, grid, st);
-  return launch_gemm3_k<KIND, SPS, SK_BF16, 256>(p, asym, grid, st);
-}
-
-// fp8 weights: device scales are always fp32 (E8M0 is expanded at load), no zero points — five instantiations per SPS
-template <int SPS>
-static hipError_t launch_gemm3_f8(const Gemm2Params& p, dim3 grid, hipStream_t st) {
-  if (p.dual) {
-    if (p.bm3 == 64) return launch_gemm3_k<WK_F8, SPS, SK_F32, 64, false, true>(p, false, grid, st);
-    return launch_gemm3_k<WK_F8, SPS, SK_F32, 128, false, true>(p, false, grid, st);
-  }
-  if (p.bm3 == 64) return launch_gemm3_k<WK_F8, SPS, SK_F32, 64>(p, false, grid, st);
-  if (p.bm3 == 128) return launch_gemm3_k<WK_F8, SPS, SK_F32, 128>(p, false, grid, st);
-  return launch_gemm3_k<WK_F8, SPS, SK_F32, 256>(p, false, grid, st);
-}
-
-template <int KIND, int SPS>
-static hipError_t launch_gemm2_s(const Gemm2Params& p, uint32_t scale_dt, bool asym, dim3 grid, size_t lds,
-                                 hipStream_t st) {
-  if (scale_dt == DT_F32) return launch_gemm2_k<KIND, SPS, SK_F32>(p, asym, grid, lds, st);
-  if (scale_dt == DT_F16) return launch_gemm2_k<KIND, SPS, SK_F16>(p, asym, grid, lds, st);
-  return launch_gemm2_k<KIND, SPS, SK_BF16>(p, asym, grid, lds, st);
+    if (p.bm3 == 64) return tile(int_c<64>{}, no, no);  // calls of at most 64 rows: a quarter / half of the 128-row tile's MFMA work is padding otherwise
+    if (p.bm3 == 128) return tile(int_c<128>{}, no, no);
+    if constexpr (KIND == WK_INT4)
+      if (p.tall3) return tile(int_c<256>{}, yes, no);
+    return tile(int_c<256>{}, no, no);
+  });
 }
 
 static std::atomic<int> g_g3_bm{0};
@@ -1756,15 +1639,18 @@ hipError_t launch_gemm2(const SmallMArgs& a, hipStream_t st) {
   static const int g3_diag = getenv("NS_G3_DIAG") ? atoi(getenv("NS_G3_DIAG")) : 0;
   p.diag = g3_diag;
   p.nbn = (w0->ntiles + kG2Tiles - 1) / kG2Tiles;
+  // the matrices of a fused launch share one format and one record layout (gate/up pairs: the column count and the array sizes as well)
+  auto same_layout = [](const ns_weight* w, const ns_weight* w0, bool with_n_and_bytes) {
+    return w->k == w0->k && w->kind == w0->kind && w->sps == w0->sps && w->scale_dt == w0->scale_dt && w->asym == w0->asym &&
+           w->ksteps == w0->ksteps && w->qstride == w0->qstride && w->sstride == w0->sstride && w->zstride == w0->zstride &&
+           w->srows == w0->srows && w->qtype == w0->qtype &&
+           (!with_n_and_bytes || (w->n == w0->n && w->codes_bytes == w0->codes_bytes && w->scales_bytes == w0->scales_bytes && w->zps_bytes == w0->zps_bytes));
+  };
   if (a.dual) {  // fused gate/up at GEMM size (round 5): gemm3_kernel only, a column block = 4 tile pairs = 64 output columns
     static const bool g3_off_env = getenv("NS_GEMM3") && atoi(getenv("NS_GEMM3")) != 1;
     const ns_weight* w = a.seg[1].w;
     if (a.nseg != 2 || !w || a.m < gemm3_min_m() || (p.lda16 & 7) != 0 || g3_off_env || a.d || kG3M32) return hipErrorNotSupported;
-    if (w->k != w0->k || w->n != w0->n || w->kind != w0->kind || w->sps != w0->sps || w->scale_dt != w0->scale_dt || w->asym != w0->asym ||
-        w->ksteps != w0->ksteps || w->qstride != w0->qstride || w->sstride != w0->sstride || w->zstride != w0->zstride ||
-        w->srows != w0->srows || w->qtype != w0->qtype ||
-        w->codes_bytes != w0->codes_bytes || w->scales_bytes != w0->scales_bytes || w->zps_bytes != w0->zps_bytes)
-      return hipErrorNotSupported;
+    if (!same_layout(w, w0, true)) return hipErrorNotSupported;
     if (!p.c && !p.c16) return hipErrorInvalidValue;
     p.dual = 1;
     p.codes2 = w->codes, p.scales2 = w->scales, p.zps2 = w->zps;
@@ -1778,26 +1664,7 @@ hipError_t launch_gemm2(const SmallMArgs& a, hipStream_t st) {
     p.cps = p.nchunks;
     const int nbm3 = (a.m + p.bm3 - 1) / p.bm3;
     const dim3 grid3(unsigned(8 * p.cpx * nbm3), 1u);
-    switch (w0->kind) {
-      case WK_INT4:
-        switch (w0->sps) {
-          case 4: return launch_gemm3_s<WK_INT4, 4>(p, w0->scale_dt, w0->asym, grid3, st, false);
-          case 2: return launch_gemm3_s<WK_INT4, 2>(p, w0->scale_dt, w0->asym, grid3, st, false);
-          default: return launch_gemm3_s<WK_INT4, 1>(p, w0->scale_dt, w0->asym, grid3, st, false);
-        }
-      case WK_INT8:
-        if (w0->sps == 2) return launch_gemm3_s<WK_INT8, 2>(p, w0->scale_dt, w0->asym, grid3, st, false);
-        return launch_gemm3_s<WK_INT8, 1>(p, w0->scale_dt, w0->asym, grid3, st, false);
-      case WK_F8:
-        if (w0->sps == 2) return launch_gemm3_f8<2>(p, grid3, st);
-        return launch_gemm3_f8<1>(p, grid3, st);
-      default:
-        switch (w0->sps) {
-          case 4: return launch_gemm3_s<WK_F4, 4>(p, w0->scale_dt, w0->asym, grid3, st, false);
-          case 2: return launch_gemm3_s<WK_F4, 2>(p, w0->scale_dt, w0->asym, grid3, st, false);
-          default: return launch_gemm3_s<WK_F4, 1>(p, w0->scale_dt, w0->asym, grid3, st, false);
-        }
-    }
+    return launch_gemm3(p, w0, grid3, st, false);
   }
   if (a.nseg > 1) {  // fused QKV at GEMM size: gemm3_kernel only, whole column blocks per matrix
     static const bool g3_off_env = getenv("NS_GEMM3") && atoi(getenv("NS_GEMM3")) != 1;
@@ -1806,10 +1673,7 @@ hipError_t launch_gemm2(const SmallMArgs& a, hipStream_t st) {
     int bn0 = 0;
     for (int i = 0; i < a.nseg; i++) {
       const ns_weight* w = a.seg[i].w;
-      if (w->k != w0->k || w->kind != w0->kind || w->sps != w0->sps || w->scale_dt != w0->scale_dt || w->asym != w0->asym ||
-          w->ksteps != w0->ksteps || w->qstride != w0->qstride || w->sstride != w0->sstride || w->zstride != w0->zstride ||
-          w->srows != w0->srows || w->qtype != w0->qtype)
-        return hipErrorNotSupported;
+      if (!same_layout(w, w0, false)) return hipErrorNotSupported;
       p.seg_spre[i] = w->g2_pre, p.seg_spost[i] = w->g2_post;
       p.seg_bn0[i] = bn0;
       p.seg_n[i] = w->n;
@@ -1893,24 +1757,7 @@ hipError_t launch_gemm2(const SmallMArgs& a, hipStream_t st) {
       }
     }
     const dim3 grid3(unsigned(8 * p.cpx * nbm3), unsigned(p.ksplit));
-#define NS_G3DISPATCH(KIND)                                                           \
-  switch (w0->sps) {                                                                  \
-    case 4: return launch_gemm3_s<KIND, 4>(p, w0->scale_dt, w0->asym, grid3, st, deep);     \
-    case 2: return launch_gemm3_s<KIND, 2>(p, w0->scale_dt, w0->asym, grid3, st, deep);     \
-    default: return launch_gemm3_s<KIND, 1>(p, w0->scale_dt, w0->asym, grid3, st, deep);    \
-  }
-    if (w0->kind == WK_INT4) {
-      NS_G3DISPATCH(WK_INT4)
-    } else if (w0->kind == WK_INT8) {
-      if (w0->sps == 2) return launch_gemm3_s<WK_INT8, 2>(p, w0->scale_dt, w0->asym, grid3, st, deep);
-      return launch_gemm3_s<WK_INT8, 1>(p, w0->scale_dt, w0->asym, grid3, st, deep);
-    } else if (f8) {
-      if (w0->sps == 2) return launch_gemm3_f8<2>(p, grid3, st);
-      return launch_gemm3_f8<1>(p, grid3, st);
-    } else {
-      NS_G3DISPATCH(WK_F4)
-    }
-#undef NS_G3DISPATCH
+    return launch_gemm3(p, w0, grid3, st, deep);
   }
   if (p.rope_on || f8) return hipErrorNotSupported;  // (the RoPE epilogue and the fp8 conversion are gemm3_kernel's)
   const int nbm = (a.m + kG2BM - 1) / kG2BM;
@@ -1936,25 +1783,16 @@ hipError_t launch_gemm2(const SmallMArgs& a, hipStream_t st) {
   const size_t lds = size_t(kG2Stages) * kG2StageBytes;
 #ifdef NS_GEMM_MIN  // development builds: the two bench formats only
   if (w0->scale_dt != DT_BF16 || w0->asym) return hipErrorNotSupported;
-  if (w0->kind == WK_INT4 && w0->sps == 4) return launch_gemm2_k<WK_INT4, 4, SK_BF16>(p, false, grid, lds, st);
-  if (w0->kind == WK_INT8 && w0->sps == 2) return launch_gemm2_k<WK_INT8, 2, SK_BF16>(p, false, grid, lds, st);
+  if (w0->kind == WK_INT4 && w0->sps == 4) return launch_gemm2_k<WK_INT4, 4, SK_BF16, false>(p, grid, lds, st);
+  if (w0->kind == WK_INT8 && w0->sps == 2) return launch_gemm2_k<WK_INT8, 2, SK_BF16, false>(p, grid, lds, st);
   return hipErrorNotSupported;
 #else
-#define NS_G2DISPATCH(KIND)                                                                \
-  switch (w0->sps) {                                                                       \
-    case 4: return launch_gemm2_s<KIND, 4>(p, w0->scale_dt, w0->asym, grid, lds, st);      \
-    case 2: return launch_gemm2_s<KIND, 2>(p, w0->scale_dt, w0->asym, grid, lds, st);      \
-    default: return launch_gemm2_s<KIND, 1>(p, w0->scale_dt, w0->asym, grid, lds, st);     \
-  }
-  if (w0->kind == WK_INT4) {
-    NS_G2DISPATCH(WK_INT4)
-  } else if (w0->kind == WK_INT8) {
-    if (w0->sps == 2) return launch_gemm2_s<WK_INT8, 2>(p, w0->scale_dt, w0->asym, grid, lds, st);
-    return launch_gemm2_s<WK_INT8, 1>(p, w0->scale_dt, w0->asym, grid, lds, st);
-  } else {
-    NS_G2DISPATCH(WK_F4)
-  }
-#undef NS_G2DISPATCH
+  return with_format(w0->kind, w0->sps, w0->scale_dt, w0->asym, [&](auto kind_c, auto sps_c, auto sk_c, auto asym_c) {
+    if constexpr (kind_c == WK_F8)
+      return hipErrorNotSupported;  // (refused above: gemm2_kernel has no fp8 form)
+    else
+      return launch_gemm2_k<kind_c, sps_c, sk_c, asym_c>(p, grid, lds, st);
+  });
 #endif
 }
 

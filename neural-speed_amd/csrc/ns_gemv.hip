@@ -43,6 +43,7 @@
 #include "ns_common.h"
 #include "ns_dev.h"
 #include "ns_gemv.h"
+#include "ns_launch.h"
 
 // the slice this object holds (Makefile: GEMV_SLICES); a bare `hipcc -c ns_gemv.hip` builds the Q4_0 one
 #ifndef NS_GEMV_KIND
@@ -206,14 +207,7 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
       if (w == 0 && g == 0 && colz < cz->mat[0].n) {
         float v = 0.f;
         const float dv = cz->d ? cz->d[colz] : 0.f;
-        switch (cz->epilogue) {
-          case 1: v = v + dv; break;
-          case 2: v = v * dv; break;
-          case 3: v = epi_gelu(v + dv); break;
-          case 4: v = epi_gelu(v); break;
-          case 5: v = epi_silu(v); break;
-          default: break;
-        }
+        v = epi_apply(v, dv, cz->epilogue);
         cz->mat[0].c[colz] = v;
         if (cz->mat[0].c16) cz->mat[0].c16[colz] = (_Float16)v;
       }
@@ -277,13 +271,6 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
       (void)((younger == uint32_t(K) ? (wait_vmcnt<OPS * K>(), true) : false) || ...);
     }(std::make_integer_sequence<int, PF + 1>{});
   };
-
-#define NS_FOR_SLOTS(BODY)                                        \
-  {                                                               \
-    [&]<int... I>(std::integer_sequence<int, I...>) {             \
-      (([&] { constexpr int i = I; std::integral_constant<int, I> ic; (void)i; (void)ic; BODY }()), ...); \
-    }(std::make_integer_sequence<int, PF>{});                     \
-  }
 
   // ---- 1. activations requested first (small, and they must be in LDS before the first MFMA): fp16 rows go
   //      HBM/L2 -> LDS directly in 1 KiB pieces, piece c of row r by wave (r * pieces + c) % NW; LDS row r holds
@@ -982,14 +969,7 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
           v = sum[1][rr] * rscale[rr] * t1;
         } else {
           const float dv = dvp[rr];
-          switch (epi) {
-            case 1: v = v + dv; break;            // custom::epilogue::Add
-            case 2: v = v * dv; break;            // custom::epilogue::Mul
-            case 3: v = epi_gelu(v + dv); break;  // custom::epilogue::Add_Gelu
-            case 4: v = epi_gelu(v); break;
-            case 5: v = epi_silu(v); break;
-            default: break;
-          }
+          v = epi_apply(v, dv, epi);
         }
         cbase[size_t(row) * ldc + col] = v;
         // carried norm, producer side: the shadow the NEXT operator streams is gamma * v (its norm's weight), the
@@ -1009,7 +989,6 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
       }
     }
   }
-#undef NS_FOR_SLOTS
   NS_GSTAMP(6);
 #ifdef NS_TRACE
   if ((threadIdx.x & 63) == 0 && blockIdx.x < 4096)  // where the wave ran: XCC_ID (reg 20) and HW_ID (reg 4)
@@ -1022,15 +1001,10 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
 // host side: the ladder from a launch's run-time format and mode to its instantiation.  The if constexpr guards decide
 // WHICH instantiations exist (launch_gemv, ns_gemv_host.cpp, prepares the GemvParams and picks the slice)
 // ============================================================================================================
-// one instantiation's launch; its dynamic LDS limit is raised once, at its first launch
+// one instantiation's launch (launch_lds, ns_launch.h: its dynamic LDS limit is raised once, at its first launch)
 template <int KIND, int SPS, int SK, bool ASYM, int MODE, int XV, bool PL, bool R1>
 static hipError_t gv_launch(dim3 g, dim3 b, size_t lds, hipStream_t st, const GemvParams& p) {
-  auto k = gemv_kernel<KIND, SPS, SK, ASYM, MODE, XV, PL, R1>;
-  static const hipError_t attr =
-      hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, int(kGvMaxLds));
-  if (attr != hipSuccess && lds > 64 * 1024) return attr;
-  hipLaunchKernelGGL(k, g, b, lds, st, p);
-  return hipGetLastError();
+  return launch_lds<gemv_kernel<KIND, SPS, SK, ASYM, MODE, XV, PL, R1>>(int(kGvMaxLds), g, b, lds, st, p);
 }
 template <int KIND, int SPS, int SK, bool ASYM>
 static hipError_t launch_gemv_planes(const GemvParams& p, int mode, int grid, int nw, size_t lds, hipStream_t st) {
@@ -1116,25 +1090,6 @@ static hipError_t launch_gemv_k(const GemvParams& p, int mode, int grid, int nw,
 #undef NS_GV_LAUNCH_MOE
   return hipGetLastError();
 }
-template <int KIND, int SPS, int SK>
-static hipError_t launch_gemv_a(const GemvParams& p, bool asym, int mode, int grid, int nw, size_t lds,
-                                hipStream_t st) {
-  if constexpr (KIND == WK_F4 || KIND == WK_F8) {
-    (void)asym;
-    return launch_gemv_k<KIND, SPS, SK, false>(p, mode, grid, nw, lds, st);
-  } else {
-    if (asym) return launch_gemv_k<KIND, SPS, SK, true>(p, mode, grid, nw, lds, st);
-    return launch_gemv_k<KIND, SPS, SK, false>(p, mode, grid, nw, lds, st);
-  }
-}
-template <int KIND, int SPS>
-static hipError_t launch_gemv_s(const GemvParams& p, uint32_t scale_dt, bool asym, int mode, int grid, int nw,
-                                size_t lds, hipStream_t st) {
-  if (scale_dt == DT_F32) return launch_gemv_a<KIND, SPS, SK_F32>(p, asym, mode, grid, nw, lds, st);
-  if (scale_dt == DT_F16) return launch_gemv_a<KIND, SPS, SK_F16>(p, asym, mode, grid, nw, lds, st);
-  return launch_gemv_a<KIND, SPS, SK_BF16>(p, asym, mode, grid, nw, lds, st);
-}
-
 
 // ---- this object's slice ----
 #define NS_GV_PASTE_(a, b) a##b
@@ -1142,17 +1097,11 @@ static hipError_t launch_gemv_s(const GemvParams& p, uint32_t scale_dt, bool asy
 #define NS_GV_SLICE_FN(prefix) NS_GV_PASTE(NS_GV_PASTE(NS_GV_PASTE(prefix, NS_GEMV_KIND), _), NS_GEMV_SPS)
 constexpr int kGvSliceKind = NS_GV_PASTE(WK_, NS_GEMV_KIND);
 
-template <int KIND, int SPS>
-static hipError_t launch_gemv_slice(const GemvParams& p, uint32_t scale_dt, bool asym, int mode, int grid, int nw, size_t lds,
-                                    hipStream_t st) {
-  if constexpr (KIND == WK_F8)  // device scales are always fp32 (E8M0 shared exponents are expanded at load)
-    return launch_gemv_a<KIND, SPS, SK_F32>(p, false, mode, grid, nw, lds, st);
-  else
-    return launch_gemv_s<KIND, SPS>(p, scale_dt, asym, mode, grid, nw, lds, st);
-}
 hipError_t NS_GV_SLICE_FN(launch_gemv_)(const GemvParams& p, uint32_t scale_dt, bool asym, int mode, int grid, int nw, size_t lds,
                                         hipStream_t st) {
-  return launch_gemv_slice<kGvSliceKind, NS_GEMV_SPS>(p, scale_dt, asym, mode, grid, nw, lds, st);
+  return with_scales<kGvSliceKind>(scale_dt, asym, [&](auto sk_c, auto asym_c) {
+    return launch_gemv_k<kGvSliceKind, NS_GEMV_SPS, sk_c, asym_c>(p, mode, grid, nw, lds, st);
+  });
 }
 void NS_GV_SLICE_FN(touch_gemv_)() {  // (an instantiation every slice has)
   hipFuncAttributes fa;

@@ -51,6 +51,7 @@
 #include "../../include/ns_bestla.h"
 #include "ns_common.h"
 #include "ns_dev.h"
+#include "ns_launch.h"
 
 namespace ns {
 
@@ -196,14 +197,7 @@ __device__ __forceinline__ void gvs_epilogue(const floatx4* sum, int m, int col,
       v = sum[DUAL ? 1 : 0][rr] * t1;
     } else {
       const float dv = dvp[rr];
-      switch (epi) {
-        case 1: v = v + dv; break;
-        case 2: v = v * dv; break;
-        case 3: v = epi_gelu(v + dv); break;
-        case 4: v = epi_gelu(v); break;
-        case 5: v = epi_silu(v); break;
-        default: break;
-      }
+      v = epi_apply(v, dv, epi);
     }
     cbase[size_t(row) * ldc + col] = v;
     if (c16) c16[size_t(row) * ldc + col] = (_Float16)v;
@@ -436,12 +430,6 @@ __global__ __launch_bounds__(1024) void gemvs_kernel(const GvsParams p) {
         (void)((younger == uint32_t(K) ? (gvs_wait_vmcnt<OPS * K>(), true) : false) || ...);
       }(std::make_integer_sequence<int, PF + 1>{});
     };
-#define NS_FOR_SLOTS(BODY)                                        \
-  {                                                               \
-    [&]<int... I>(std::integer_sequence<int, I...>) {             \
-      (([&] { constexpr int i = I; std::integral_constant<int, I> ic; (void)i; (void)ic; BODY }()), ...); \
-    }(std::make_integer_sequence<int, PF>{});                     \
-  }
 
     // ---- 1. this wave's share of the activations (a handful of requests, L2), its first weight records (HBM), then its
     //      share of the f4 table while both are in flight (the table in FRONT of the weight requests delayed them to 3.4 us
@@ -614,7 +602,6 @@ __global__ __launch_bounds__(1024) void gemvs_kernel(const GvsParams p) {
     } else {
       stream(std::false_type{});
     }
-#undef NS_FOR_SLOTS
     NS_SSTAMP(5);
   } else {
     // =========================================== service wave ===========================================
@@ -835,39 +822,9 @@ __global__ __launch_bounds__(256) void gemvs_finalize_kernel(const GvsFinParams 
 template <int KIND, int SPS, int SK, bool ASYM>
 static hipError_t launch_gvs_k(const GvsParams& p, int mode, int grid, int nwaves, size_t lds, hipStream_t st) {
   const dim3 g(grid), b(nwaves * 64);
-#define NS_GS_LAUNCH(MODEV)                                                                                     \
-  {                                                                                                             \
-    auto k = gemvs_kernel<KIND, SPS, SK, ASYM, MODEV>;                                                          \
-    static const hipError_t attr =                                                                              \
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, int(kGsMaxLds)); \
-    if (attr != hipSuccess && lds > 64 * 1024) return attr;                                                     \
-    hipLaunchKernelGGL(k, g, b, lds, st, p);                                                                    \
-  }
-  if (mode == GS_DUAL)
-    NS_GS_LAUNCH(GS_DUAL)
-  else if (mode == GS_MSEG)
-    NS_GS_LAUNCH(GS_MSEG)
-  else
-    NS_GS_LAUNCH(GS_PLAIN)
-#undef NS_GS_LAUNCH
-  return hipGetLastError();
-}
-template <int KIND, int SPS, int SK>
-static hipError_t launch_gvs_a(const GvsParams& p, bool asym, int mode, int grid, int nwaves, size_t lds, hipStream_t st) {
-  if constexpr (KIND == WK_F4 || KIND == WK_F8) {
-    (void)asym;
-    return launch_gvs_k<KIND, SPS, SK, false>(p, mode, grid, nwaves, lds, st);
-  } else {
-    if (asym) return launch_gvs_k<KIND, SPS, SK, true>(p, mode, grid, nwaves, lds, st);
-    return launch_gvs_k<KIND, SPS, SK, false>(p, mode, grid, nwaves, lds, st);
-  }
-}
-template <int KIND, int SPS>
-static hipError_t launch_gvs_s(const GvsParams& p, uint32_t scale_dt, bool asym, int mode, int grid, int nwaves, size_t lds,
-                               hipStream_t st) {
-  if (scale_dt == DT_F32) return launch_gvs_a<KIND, SPS, SK_F32>(p, asym, mode, grid, nwaves, lds, st);
-  if (scale_dt == DT_F16) return launch_gvs_a<KIND, SPS, SK_F16>(p, asym, mode, grid, nwaves, lds, st);
-  return launch_gvs_a<KIND, SPS, SK_BF16>(p, asym, mode, grid, nwaves, lds, st);
+  if (mode == GS_DUAL) return launch_lds<gemvs_kernel<KIND, SPS, SK, ASYM, GS_DUAL>>(int(kGsMaxLds), g, b, lds, st, p);
+  if (mode == GS_MSEG) return launch_lds<gemvs_kernel<KIND, SPS, SK, ASYM, GS_MSEG>>(int(kGsMaxLds), g, b, lds, st, p);
+  return launch_lds<gemvs_kernel<KIND, SPS, SK, ASYM, GS_PLAIN>>(int(kGsMaxLds), g, b, lds, st, p);
 }
 
 // tuning / diagnostics (ns_hip_set_tuning): "gvs" 0 = off, 1 = from 2 rows (default), 2 = from 1 row;
@@ -1116,25 +1073,9 @@ hipError_t launch_gemvs(const SmallMArgs& a, hipStream_t st) {
             mode, S, best.ksl, best.tg, best.ns, lds, best.a_bytes, best.cost);
   if (dbg && w0->kind == WK_F4) fprintf(stderr, "gemvs: f4 pair table %s\n", best.tbl ? "on" : "off");
 
-  hipError_t e = hipSuccess;
-#define NS_DISPATCH(KIND)                                                                          \
-  switch (w0->sps) {                                                                               \
-    case 4: e = launch_gvs_s<KIND, 4>(p, w0->scale_dt, w0->asym, mode, grid, nwaves, lds, st); break;  \
-    case 2: e = launch_gvs_s<KIND, 2>(p, w0->scale_dt, w0->asym, mode, grid, nwaves, lds, st); break;  \
-    default: e = launch_gvs_s<KIND, 1>(p, w0->scale_dt, w0->asym, mode, grid, nwaves, lds, st); break; \
-  }
-  if (w0->kind == WK_INT4) {
-    NS_DISPATCH(WK_INT4)
-  } else if (w0->kind == WK_INT8) {
-    if (w0->sps == 2) e = launch_gvs_s<WK_INT8, 2>(p, w0->scale_dt, w0->asym, mode, grid, nwaves, lds, st);
-    else e = launch_gvs_s<WK_INT8, 1>(p, w0->scale_dt, w0->asym, mode, grid, nwaves, lds, st);
-  } else if (w0->kind == WK_F8) {
-    if (w0->sps == 2) e = launch_gvs_a<WK_F8, 2, SK_F32>(p, false, mode, grid, nwaves, lds, st);
-    else e = launch_gvs_a<WK_F8, 1, SK_F32>(p, false, mode, grid, nwaves, lds, st);
-  } else {
-    NS_DISPATCH(WK_F4)
-  }
-#undef NS_DISPATCH
+  const hipError_t e = with_format(w0->kind, w0->sps, w0->scale_dt, w0->asym, [&](auto kind_c, auto sps_c, auto sk_c, auto asym_c) {
+    return launch_gvs_k<kind_c, sps_c, sk_c, asym_c>(p, mode, grid, nwaves, lds, st);
+  });
   if (e != hipSuccess || S == 1 || tickets) return e;
 
   GvsFinParams f;

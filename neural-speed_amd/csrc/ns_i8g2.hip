@@ -28,6 +28,7 @@
 #include "ns_common.h"
 #include "ns_dev.h"
 #include "ns_i8g2.h"
+#include "ns_launch.h"
 
 #ifndef NS_I8G2_NAME  // a bare `hipcc -c ns_i8g2.hip` builds the Q4_0 variant
 #define NS_I8G2_NAME launch_i8g2_n4
@@ -335,14 +336,7 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 4) void i8mfma2_kernel(const
           if (row >= p.m) continue;
           float v = (i & 1) ? acc[h][ct][rt][i >> 1].y : acc[h][ct][rt][i >> 1].x;
           const float dv = p.d ? p.d[size_t(row) * p.ldd + col] : 0.f;
-          switch (p.epilogue) {
-            case 1: v = v + dv; break;
-            case 2: v = v * dv; break;
-            case 3: v = epi_gelu(v + dv); break;
-            case 4: v = epi_gelu(v); break;
-            case 5: v = epi_silu(v); break;
-            default: break;
-          }
+          v = epi_apply(v, dv, p.epilogue);
           p.c[size_t(row) * p.ldc + col] = v;
           if (p.c16) p.c16[size_t(row) * p.ldc + col] = (_Float16)v;
         }
@@ -351,14 +345,9 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 4) void i8mfma2_kernel(const
 
 template <bool F, int S, int D, int RH, int CT, int WV>
 hipError_t launch_i8mfma2_a(bool asym, dim3 grid, hipStream_t st, const I8Gemm2Params& p) {
-  auto go = [&](auto kern) {
-    static const hipError_t attr =
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(I8G2Geom<RH>::kLds));
-    if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL(kern, grid, dim3(64 * WV), I8G2Geom<RH>::kLds, st, p);
-    return hipGetLastError();
-  };
-  return asym ? go(i8mfma2_kernel<F, D, S, true, RH, CT, WV>) : go(i8mfma2_kernel<F, D, S, false, RH, CT, WV>);
+  constexpr size_t lds = I8G2Geom<RH>::kLds;
+  if (asym) return launch_lds<i8mfma2_kernel<F, D, S, true, RH, CT, WV>>(int(lds), grid, dim3(64 * WV), lds, st, p);
+  return launch_lds<i8mfma2_kernel<F, D, S, false, RH, CT, WV>>(int(lds), grid, dim3(64 * WV), lds, st, p);
 }
 template <bool F, int S, int RH, int CT, int WV>
 hipError_t launch_i8mfma2_t(int sdt, bool asym, int m, int ntiles, hipStream_t st, const I8Gemm2Params& p) {

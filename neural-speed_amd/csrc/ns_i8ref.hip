@@ -219,14 +219,7 @@ __global__ __launch_bounds__(kI8Threads) void i8ref_kernel(const I8RefParams p) 
         for (int ww = 0; ww < kI8Waves; ww++) v += red[ww][r][tid & 15];
         const size_t row = size_t(r0 + r);
         const float dv = p.d ? p.d[row * p.ldd + col] : 0.f;
-        switch (p.epilogue) {
-          case 1: v = v + dv; break;
-          case 2: v = v * dv; break;
-          case 3: v = epi_gelu(v + dv); break;
-          case 4: v = epi_gelu(v); break;
-          case 5: v = epi_silu(v); break;
-          default: break;
-        }
+        v = epi_apply(v, dv, p.epilogue);
         p.c[row * p.ldc + col] = v;
         if (p.c16) p.c16[row * p.ldc + col] = (_Float16)v;
       }
@@ -426,14 +419,7 @@ __global__ __launch_bounds__(256) void i8mfma_kernel(const I8RefParams p) {
       if (row >= p.m) continue;
       float v = acc[rt][i];
       const float dv = p.d ? p.d[size_t(row) * p.ldd + col] : 0.f;
-      switch (p.epilogue) {
-        case 1: v = v + dv; break;
-        case 2: v = v * dv; break;
-        case 3: v = epi_gelu(v + dv); break;
-        case 4: v = epi_gelu(v); break;
-        case 5: v = epi_silu(v); break;
-        default: break;
-      }
+      v = epi_apply(v, dv, p.epilogue);
       p.c[size_t(row) * p.ldc + col] = v;
       if (p.c16) p.c16[size_t(row) * p.ldc + col] = (_Float16)v;
     }

@@ -20,6 +20,7 @@
 
 #include "ns_common.h"
 #include "ns_dev.h"
+#include "ns_launch.h"
 
 namespace ns {
 
@@ -483,14 +484,6 @@ __global__ __launch_bounds__(WIDE ? kMaxNW * 64 : 512) void smallm_kernel(const 
     }
   };
 
-  // compile-time slot loop helper
-#define NS_FOR_SLOTS(BODY)                                        \
-  {                                                               \
-    [&]<int... I>(std::integer_sequence<int, I...>) {             \
-      (([&] { constexpr int i = I; std::integral_constant<int, I> ic; (void)i; BODY }()), ...); \
-    }(std::make_integer_sequence<int, PF>{});                     \
-  }
-
   for (int c0 = 0; c0 < p.ksteps; c0 += p.chunk_steps) {
     const int cend = min(c0 + p.chunk_steps, p.ksteps);
     const int first = c0 + w;
@@ -629,7 +622,6 @@ __global__ __launch_bounds__(WIDE ? kMaxNW * 64 : 512) void smallm_kernel(const 
       })
     }
   }
-#undef NS_FOR_SLOTS
   NS_STAMP(4);
 
   // ---- cross-wave reduction through LDS, then epilogue ----
@@ -665,14 +657,7 @@ __global__ __launch_bounds__(WIDE ? kMaxNW * 64 : 512) void smallm_kernel(const 
           v = sum[1][rr] * t1;
         } else {
           const float dv = p.d ? p.d[size_t(row) * p.ldd + col] : 0.f;
-          switch (p.epilogue) {
-            case 1: v = v + dv; break;                 // custom::epilogue::Add
-            case 2: v = v * dv; break;                 // custom::epilogue::Mul
-            case 3: v = epi_gelu(v + dv); break;       // custom::epilogue::Add_Gelu
-            case 4: v = epi_gelu(v); break;
-            case 5: v = epi_silu(v); break;
-            default: break;
-          }
+          v = epi_apply(v, dv, p.epilogue);
         }
         cbase[size_t(row) * p.ldc + col] = v;
         _Float16* c16 = p.c16[DUAL ? 0 : seg];
@@ -726,48 +711,25 @@ static hipError_t launch_smallm_k(const SmallMParams& p, bool dual, int mb, int 
   // +2 % tokens/s over the 168-VGPR / 4-deep one on QKV, WO and lm_head as well as the down projection; the fused
   // gate/up launch measured the same either way and stays on the 168-VGPR variant.
   static const bool narrow_all = getenv("NS_NO_WIDE") != nullptr;  // diagnostics: 168-VGPR variant where possible
-#define NS_LAUNCH(MBV, DUALV)                                                                             \
-  {                                                                                                       \
-    if (MBV == 1 && !DUALV && (nw > 8 || !narrow_all)) {                                                  \
-      if constexpr (MBV == 1 && !DUALV)                                                                   \
-        hipLaunchKernelGGL((smallm_kernel<KIND, SPS, MBV, DUALV, SK, ASYM, true>), g, b, lds, st, p);     \
-      else                                                                                                \
-        return hipErrorInvalidValue;                                                                      \
-    } else {                                                                                              \
-      if (nw > 8) return hipErrorInvalidValue;                                                            \
-      hipLaunchKernelGGL((smallm_kernel<KIND, SPS, MBV, DUALV, SK, ASYM, false>), g, b, lds, st, p);      \
-    }                                                                                                     \
-  }
-  if (dual && mb == 1)
-    NS_LAUNCH(1, true)
-  else if (mb == 1)
-    NS_LAUNCH(1, false)
-  else if (mb == 2)
-    NS_LAUNCH(2, false)
-  else
-    NS_LAUNCH(4, false)
-#undef NS_LAUNCH
-  return hipGetLastError();
+  // plain MB == 1 launches have the WIDE instantiation as well, the only one that runs more than 8 waves
+  auto go = [&](auto mb_c, auto dual_c) {
+    constexpr int MB = mb_c;
+    constexpr bool DUAL = dual_c;
+    if constexpr (MB == 1 && !DUAL) {
+      if (nw > 8 || !narrow_all) {
+        hipLaunchKernelGGL((smallm_kernel<KIND, SPS, MB, DUAL, SK, ASYM, true>), g, b, lds, st, p);
+        return hipGetLastError();
+      }
+    }
+    if (nw > 8) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((smallm_kernel<KIND, SPS, MB, DUAL, SK, ASYM, false>), g, b, lds, st, p);
+    return hipGetLastError();
+  };
+  if (dual && mb == 1) return go(int_c<1>{}, std::true_type{});
+  if (mb == 1) return go(int_c<1>{}, std::false_type{});
+  if (mb == 2) return go(int_c<2>{}, std::false_type{});
+  return go(int_c<4>{}, std::false_type{});
 }
-template <int KIND, int SPS, int SK>
-static hipError_t launch_smallm_a(const SmallMParams& p, bool asym, bool dual, int mb, int grid, int nw, size_t lds,
-                                  hipStream_t st) {
-  if constexpr (KIND == WK_F4 || KIND == WK_F8) {
-    (void)asym;
-    return launch_smallm_k<KIND, SPS, SK, false>(p, dual, mb, grid, nw, lds, st);
-  } else {
-    if (asym) return launch_smallm_k<KIND, SPS, SK, true>(p, dual, mb, grid, nw, lds, st);
-    return launch_smallm_k<KIND, SPS, SK, false>(p, dual, mb, grid, nw, lds, st);
-  }
-}
-template <int KIND, int SPS>
-static hipError_t launch_smallm_s(const SmallMParams& p, bool asym, bool dual, int mb, int grid, int nw, size_t lds,
-                                  hipStream_t st) {
-  if (p.scale_dt == DT_F32) return launch_smallm_a<KIND, SPS, SK_F32>(p, asym, dual, mb, grid, nw, lds, st);
-  if (p.scale_dt == DT_F16) return launch_smallm_a<KIND, SPS, SK_F16>(p, asym, dual, mb, grid, nw, lds, st);
-  return launch_smallm_a<KIND, SPS, SK_BF16>(p, asym, dual, mb, grid, nw, lds, st);
-}
-
 
 // dual (gate/up) launches need MB == 1; callers split larger M into the unfused path
 bool smallm_dual_ok(int m) { return m <= 16; }
@@ -849,24 +811,9 @@ hipError_t launch_smallm(const SmallMArgs& a, hipStream_t st) {
   const size_t red = size_t(nw) * (a.dual ? 2 : 1) * mb * 64 * 16;
   if (red > lds) lds = red;
 
-#define NS_DISPATCH(KIND)                                                                     \
-  switch (w0->sps) {                                                                          \
-    case 4: return launch_smallm_s<KIND, 4>(p, w0->asym, a.dual, mb, grid, nw, lds, st);      \
-    case 2: return launch_smallm_s<KIND, 2>(p, w0->asym, a.dual, mb, grid, nw, lds, st);      \
-    default: return launch_smallm_s<KIND, 1>(p, w0->asym, a.dual, mb, grid, nw, lds, st);     \
-  }
-  if (w0->kind == WK_INT4) {
-    NS_DISPATCH(WK_INT4)
-  } else if (w0->kind == WK_INT8) {
-    if (w0->sps == 2) return launch_smallm_s<WK_INT8, 2>(p, w0->asym, a.dual, mb, grid, nw, lds, st);
-    return launch_smallm_s<WK_INT8, 1>(p, w0->asym, a.dual, mb, grid, nw, lds, st);
-  } else if (w0->kind == WK_F8) {  // device scales are always fp32 (E8M0 shared exponents are expanded at load)
-    if (w0->sps == 2) return launch_smallm_a<WK_F8, 2, SK_F32>(p, false, a.dual, mb, grid, nw, lds, st);
-    return launch_smallm_a<WK_F8, 1, SK_F32>(p, false, a.dual, mb, grid, nw, lds, st);
-  } else {
-    NS_DISPATCH(WK_F4)
-  }
-#undef NS_DISPATCH
+  return with_format(w0->kind, w0->sps, w0->scale_dt, w0->asym, [&](auto kind_c, auto sps_c, auto sk_c, auto asym_c) {
+    return launch_smallm_k<kind_c, sps_c, sk_c, asym_c>(p, a.dual, mb, grid, nw, lds, st);
+  });
 }
 
 // ============================================================================================================
@@ -1046,14 +993,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmParams p) {
         if (row >= p.m) continue;
         float v = acc[mi][ni][r];
         const float dv = p.d ? p.d[size_t(row) * p.ldd + col] : 0.f;
-        switch (p.epilogue) {
-          case 1: v = v + dv; break;
-          case 2: v = v * dv; break;
-          case 3: v = epi_gelu(v + dv); break;
-          case 4: v = epi_gelu(v); break;
-          case 5: v = epi_silu(v); break;
-          default: break;
-        }
+        v = epi_apply(v, dv, p.epilogue);
         p.c[size_t(row) * p.ldc + col] = v;
       }
     }
@@ -1081,26 +1021,6 @@ bool srow_params(const ns_weight* w0, int* mul, int* shift) {
     }
   }
   return true;
-}
-
-template <int KIND, int SPS, int SK>
-static hipError_t launch_gemm_k(const GemmParams& p, bool asym, dim3 grid, size_t lds, hipStream_t st) {
-  if constexpr (KIND == WK_F4 || KIND == WK_F8) {
-    hipLaunchKernelGGL((gemm_kernel<KIND, SPS, SK, false>), grid, dim3(256), lds, st, p);
-  } else {
-    if (asym)
-      hipLaunchKernelGGL((gemm_kernel<KIND, SPS, SK, true>), grid, dim3(256), lds, st, p);
-    else
-      hipLaunchKernelGGL((gemm_kernel<KIND, SPS, SK, false>), grid, dim3(256), lds, st, p);
-  }
-  return hipGetLastError();
-}
-template <int KIND, int SPS>
-static hipError_t launch_gemm_s(const GemmParams& p, uint32_t scale_dt, bool asym, dim3 grid, size_t lds,
-                                hipStream_t st) {
-  if (scale_dt == DT_F32) return launch_gemm_k<KIND, SPS, SK_F32>(p, asym, grid, lds, st);
-  if (scale_dt == DT_F16) return launch_gemm_k<KIND, SPS, SK_F16>(p, asym, grid, lds, st);
-  return launch_gemm_k<KIND, SPS, SK_BF16>(p, asym, grid, lds, st);
 }
 
 hipError_t launch_gemm(const SmallMArgs& a, hipStream_t st) {
@@ -1140,24 +1060,10 @@ hipError_t launch_gemm(const SmallMArgs& a, hipStream_t st) {
   const int kstep = w0->kstep_len;
   const dim3 grid((w0->ntiles + kGemmTiles - 1) / kGemmTiles, (a.m + kGemmBM - 1) / kGemmBM);
   const size_t lds = size_t(kGemmBM) * (kstep + 8) * 2 + size_t(kGemmTiles) * kstep * 16 * 2;
-#define NS_GDISPATCH(KIND)                                                               \
-  switch (w0->sps) {                                                                     \
-    case 4: return launch_gemm_s<KIND, 4>(p, w0->scale_dt, w0->asym, grid, lds, st);     \
-    case 2: return launch_gemm_s<KIND, 2>(p, w0->scale_dt, w0->asym, grid, lds, st);     \
-    default: return launch_gemm_s<KIND, 1>(p, w0->scale_dt, w0->asym, grid, lds, st);    \
-  }
-  if (w0->kind == WK_INT4) {
-    NS_GDISPATCH(WK_INT4)
-  } else if (w0->kind == WK_INT8) {
-    if (w0->sps == 2) return launch_gemm_s<WK_INT8, 2>(p, w0->scale_dt, w0->asym, grid, lds, st);
-    return launch_gemm_s<WK_INT8, 1>(p, w0->scale_dt, w0->asym, grid, lds, st);
-  } else if (w0->kind == WK_F8) {
-    if (w0->sps == 2) return launch_gemm_k<WK_F8, 2, SK_F32>(p, false, grid, lds, st);
-    return launch_gemm_k<WK_F8, 1, SK_F32>(p, false, grid, lds, st);
-  } else {
-    NS_GDISPATCH(WK_F4)
-  }
-#undef NS_GDISPATCH
+  return with_format(w0->kind, w0->sps, w0->scale_dt, w0->asym, [&](auto kind_c, auto sps_c, auto sk_c, auto asym_c) {
+    hipLaunchKernelGGL((gemm_kernel<kind_c, sps_c, sk_c, asym_c>), grid, dim3(256), lds, st, p);
+    return hipGetLastError();
+  });
 }
 
 // ============================================================================================================

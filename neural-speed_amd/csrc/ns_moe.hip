@@ -90,14 +90,7 @@ __global__ void moe_scatter_epilogue_kernel(const float* __restrict__ cg, const 
   const int t = perm[j];
   float v = valid[j] ? cg[size_t(j) * n + col] : 0.f;  // an id outside the group: a zero product (the per-row kernels do the same)
   const float dv = d ? d[size_t(t) * ldd + col] : 0.f;
-  switch (epilogue) {
-    case 1: v = v + dv; break;
-    case 2: v = v * dv; break;
-    case 3: v = epi_gelu(v + dv); break;
-    case 4: v = epi_gelu(v); break;
-    case 5: v = epi_silu(v); break;
-    default: break;
-  }
+  v = epi_apply(v, dv, epilogue);
   c[size_t(t) * ldc + col] = v;
 }
 
@@ -221,14 +214,7 @@ __global__ __launch_bounds__(kMoeThreads) void moe_gemv_kernel(const MoeParams p
 #pragma unroll
       for (int ww = 0; ww < kMoeWaves; ww++) v += red[ww][tid];
       const float dv = p.d ? p.d[size_t(row) * p.ldd + col] : 0.f;
-      switch (p.epilogue) {
-        case 1: v = v + dv; break;
-        case 2: v = v * dv; break;
-        case 3: v = epi_gelu(v + dv); break;
-        case 4: v = epi_gelu(v); break;
-        case 5: v = epi_silu(v); break;
-        default: break;
-      }
+      v = epi_apply(v, dv, p.epilogue);
       p.c[size_t(row) * p.ldc + col] = v;
     }
   }
