@@ -1,0 +1,147 @@
+// ns_attn.cpp — fused attention behind the reference's mha_dense C surface, host side: the tunables, and the launch of
+// what attn_plan (ns_attn_plan.cpp) decided.  The kernels are in ns_attn_decode.hip and ns_attn_prefill.hip, the library-managed kv-cache and the
+// host-tensor entries in ns_kvcache.hip.
+#include <algorithm>
+#include <atomic>
+#include <cstdio>
+#include <cstdlib>
+#include <string>
+
+#include "ns_attn.h"
+
+namespace ns {
+
+// ---- tunables: ns_hip_set_tuning (ns_api.cpp) and the environment, read once per process ---------------------------------------------------
+static int env_int(const char* name, int otherwise) { return getenv(name) ? atoi(getenv(name)) : otherwise; }
+static std::atomic<int> g_attn_stream{env_int("NS_ATTN_STREAM", 1) != 0};
+static std::atomic<int> g_attn_mfma2_rows{env_int("NS_ATTN_MFMA2_ROWS", 128)};
+// "attn_inlaunch": measured equal (profiles/r04ab_attn_merge_in_launch.txt: split 11.8 us + merge 4.7 us against 16.5 us in one launch, whole token
+// 600 vs 590 tok/s): the cost is the write-through / ticket / read-back chain across XCDs, not the kernel boundary.
+static std::atomic<int> g_attn_inlaunch{env_int("NS_ATTN_INLAUNCH", 0) != 0};
+static std::atomic<int> g_attn_heads_first{env_int("NS_ATTN_HEADS_FIRST", -1)};
+static std::atomic<int> g_attn_wg_target{1024}, g_attn_min_keys{128}, g_attn_wg_target_s{256}, g_attn_min_keys_s{32};
+static std::atomic<int> g_alibi_heads{0}, g_alibi_off{0};  // ns_hip_attn_set_head_partition
+void set_attn_stream(int on) { g_attn_stream.store(on != 0); }
+void set_attn_mfma2_rows(int rows) { g_attn_mfma2_rows.store(rows > 0 ? rows : 128); }
+void set_attn_inlaunch(int on) { g_attn_inlaunch.store(on != 0); }
+void set_attn_heads_first(int on) { g_attn_heads_first.store(on < 0 ? -1 : (on != 0)); }
+void set_attn_tuning(int wg_target, int min_keys) {
+  if (wg_target > 0) g_attn_wg_target.store(wg_target);
+  if (min_keys > 0) g_attn_min_keys.store(min_keys);
+}
+void set_attn_stream_tuning(int wg_target, int min_keys) {
+  if (wg_target > 0) g_attn_wg_target_s.store(wg_target);
+  if (min_keys > 0) g_attn_min_keys_s.store(min_keys);
+}
+static AttnKnobs attn_knobs() {
+  static const AttnKnobs env = [] {  // the switches only the environment sets (diagnostics, A/B runs)
+    AttnKnobs k;
+    k.no_mfma = getenv("NS_ATTN_NO_MFMA") != nullptr;
+    k.pipe = env_int("NS_ATTN_PIPE", 1);
+    k.pvar = env_int("NS_ATTN_PVAR", -1);
+    k.no_xcd_map = getenv("NS_ATTN_NO_XCD_MAP") != nullptr;
+    k.v1 = getenv("NS_ATTN_V1") != nullptr;
+    k.dyn_ranges = env_int("NS_ATTN_DYN_RANGES", 1) != 0;
+    return k;
+  }();
+  AttnKnobs k = env;
+  k.attn_stream = g_attn_stream.load(std::memory_order_relaxed);
+  k.attn_mfma2_rows = g_attn_mfma2_rows.load(std::memory_order_relaxed);
+  k.attn_inlaunch = g_attn_inlaunch.load(std::memory_order_relaxed);
+  k.attn_heads_first = g_attn_heads_first.load();
+  k.wg_target = g_attn_wg_target.load(), k.min_keys = g_attn_min_keys.load();
+  k.wg_target_s = g_attn_wg_target_s.load(), k.min_keys_s = g_attn_min_keys_s.load();
+  k.alibi_heads = g_alibi_heads.load(), k.alibi_off = g_alibi_off.load();
+  return k;
+}
+
+// plan, take scratch, launch
+static hipError_t launch_attn(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, hipStream_t st, std::string* why, bool device_tmp, void* dst16) {
+  AttnKnobs kn = attn_knobs();
+  AttnPlan pl = attn_plan(a, dst16, kn, g_affine, why);
+  if (pl.path == AP_REFUSED) return hipErrorInvalidValue;
+  if (pl.path == AP_ROWS64 || pl.path == AP_ROWS128 || pl.path == AP_PIPELINED) return launch_attn_rows(pl, st);
+  float* ws = nullptr;
+  if (pl.partial_bytes) {
+    // partials go to the caller's workspace (`tmp`, sized by bestla_fusion_attn_workspace_size: the reference's own contract, and the only choice
+    // that works on a stream being captured for the first time); without one, to a grow-only per-stream scratch
+    ws = device_tmp ? reinterpret_cast<float*>(a.tmp) : nullptr;
+    if (!ws) ws = static_cast<float*>(stream_scratch(st, pl.partial_bytes, 1));
+    if (!ws) {  // scratch allocation failed: planned again as one range, still correct
+      kn.no_partials = true;
+      pl = attn_plan(a, dst16, kn, g_affine, why);
+    }
+  }
+  // (nullptr, e.g. first use on a capturing stream: the merge launch)
+  uint32_t* tickets = pl.want_tickets ? static_cast<uint32_t*>(stream_scratch_zeroed(st, kAttnTicketCap * 4, 22)) : nullptr;
+  return launch_attn_onerow(pl, ws, tickets, st);
+}
+
+// scratch a moving-length decode launch needs (partials for the longest context, the merge tickets): allocated BEFORE the route's capture
+bool attn_prepare_moving(hipStream_t st, int batch, int heads, int heads_kv, int head_size, int cap) {
+  const size_t b = attn_ws_bytes(attn_knobs(), batch, heads, heads_kv, head_size, 1, cap);
+  if (b && !stream_scratch(st, b, 1)) return false;
+  return stream_scratch_zeroed(st, kAttnTicketCap * 4, 22) != nullptr;
+}
+
+bool attn_device_visible(const char* who) {
+  int count = 0;
+  if (hipGetDeviceCount(&count) == hipSuccess && count > 0) return true;
+  (void)hipGetLastError();
+  if (who) {
+    set_error("no HIP device visible: libns_hip.so has no CPU fallback");
+    fprintf(stderr, "Err: invalid parameters (%s: no HIP device visible: libns_hip.so has no CPU fallback)\n", who);
+  }
+  return false;
+}
+
+}  // namespace ns
+
+using namespace ns;  // NOLINT
+
+extern "C" {
+
+int ns_hip_attn_set_head_partition(int global_head_num, int head_offset) {
+  if (global_head_num < 0 || head_offset < 0 || (global_head_num > 0 && head_offset >= global_head_num)) {
+    set_error("ns_hip_attn_set_head_partition: need 0 <= head_offset < global_head_num (or 0, 0 to clear)");
+    return -1;
+  }
+  g_alibi_heads.store(global_head_num), g_alibi_off.store(global_head_num > 0 ? head_offset : 0);
+  return 0;
+}
+
+size_t bestla_fusion_attn_workspace_size(const attn_shape_t* s) {
+  // (m, l, acc) partials of the context splits; 64 bytes minimum so that callers always get a valid pointer
+  return std::max<size_t>(64, attn_ws_bytes(attn_knobs(), s->batch_size, s->head_num, s->heads_kv, s->head_size, s->sl_q, s->sl_kv));
+}
+
+bool bestla_fusion_attn_fp32_fp16_fp16_fp32_support(const attn_shape_t* s) {
+  std::string why;
+  return attn_device_visible(nullptr) && attn_shape_ok(s->head_num, s->heads_kv, s->head_size, s->sl_q, s->sl_kv, false, &why);
+}
+
+bool bestla_fusion_attn_fp16_support(const attn_shape_t*) { return false; }  // mha_dense.h:106: fp16 Q / dst form, not offered
+
+bool bestla_reordered_attn_fp32_support(const attn_shape_t* params) {
+  // mha_dense.cpp:70-80 answers by CPU features; here: whatever the attention kernels take (fp16 cache, ns_kvcache.hip)
+  std::string why;
+  return params && attn_device_visible(nullptr) &&
+         attn_shape_ok(params->head_num, params->heads_kv, params->head_size, params->sl_q, params->sl_kv, false, &why);
+}
+
+int ns_hip_attn_fp32_fp16_fp16_fp32_forward(const attn_fp32_fp16_fp16_fp32_fwd_args_t* a, void* stream) {
+  return ns_hip_attn_fp32_fp16_fp16_fp32_forward_h(a, nullptr, stream);
+}
+
+int ns_hip_attn_fp32_fp16_fp16_fp32_forward_h(const attn_fp32_fp16_fp16_fp32_fwd_args_t* a, void* dst16, void* stream) {
+  std::string why;
+  // device API: `tmp`, when given, is DEVICE memory of bestla_fusion_attn_workspace_size(shape) bytes
+  const hipError_t e = launch_attn(*a, static_cast<hipStream_t>(stream), &why, a->tmp != nullptr, dst16);
+  if (e != hipSuccess) {
+    set_error(why.empty() ? std::string("attention launch: ") + hipGetErrorString(e) : why);
+    return -1;
+  }
+  return 0;
+}
+
+}  // extern "C"

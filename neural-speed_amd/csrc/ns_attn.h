@@ -1,0 +1,135 @@
+// ns_attn.h — what the attention files share (internal).  Kernels: ns_attn_decode.hip (one query row per workgroup), ns_attn_prefill.hip (matrix
+// cores).  Host: ns_attn_plan.cpp decides which kernel serves a call (attn_plan: a pure function, checked on the CPU by tests/test_attn_plan.py),
+// ns_attn.cpp reads the tunables, takes scratch and launches what the plan says.  ns_kvcache.hip is the library-managed kv-cache on top of them.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "../../include/ns_bestla.h"
+#include "ns_common.h"
+
+namespace ns {
+
+constexpr int kAttnThreads = 256;
+constexpr int kAsSteps = 8;                                     // attn_stream_kernel: steps of a wave's ring
+constexpr size_t kAsLdsBytes = size_t(4) * kAsSteps * 2048;    // ... and its LDS: [4 waves][kAsSteps][K image 1 KiB | V image 1 KiB]
+constexpr int kA2KB = 64;                                       // attn_mfma2 / attn_mfma3_kernel: keys per tile
+constexpr int kA2VSub = kA2KB * 32 + 128;                       // bytes per V subtile: [64 keys][16 dims] fp16 + the bank offset
+template <int HS>
+constexpr int a2_stage_bytes() { return kA2KB * HS * 2 + (HS / 16) * kA2VSub; }
+constexpr size_t kAttnTicketCap = 65536;                        // merge tickets of a stream (scratch slot 22)
+
+struct AttnParams {
+  const float* q;
+  const _Float16* k;
+  const _Float16* v;
+  float* dst;
+  _Float16* dst16;  // optional fp16 shadow of dst (same element strides): the next GEMM's A operand
+  float qk_scale;   // QK_scale * Q_sc * K_sc
+  float out_scale;  // V_sc / dst_sc
+  uint32_t flags;
+  int head_num, heads_kv, head_size, sl_q, sl_kv;
+  long long step_q_bs, step_q_head_num, step_q_sl;
+  long long step_k_bs, step_k_head_num, step_k_sl, step_k_head_size;
+  long long step_v_bs, step_v_head_num, step_v_sl, step_v_head_size;
+  long long step_dst_bs, step_dst_head_num, step_dst_sl;
+  int hs_pad;  // power of two >= head_size (<= 256)
+  float alibi_m0, alibi_m1;
+  int alibi_log2_floor;
+  int alibi_head_off;  // tensor parallel: index of this rank's first head in the full model (0 otherwise)
+};
+
+struct AttnSplitParams {
+  AttnParams a;
+  float* ws;       // [batch][sl_q][head][nsplit][2 + head_size] partial (m, l, acc) when nsplit > 1
+  int nsplit;
+  int keys_per_split;
+  uint32_t* tickets;  // one self-resetting counter per (batch, query row, kv head, chunk): the LAST split to finish merges inside the
+                      // launch (nullptr: attn_merge_kernel does it in a second launch)
+  int heads_first;     // 1: blockIdx.x walks the (kv head, row) pairs and blockIdx.y the context ranges — neighbouring workgroups then read
+                       // neighbouring 256-byte pieces of a position-major cache ([position][head][dim]); 0: the ranges of one head first
+  int g_full, chunks;  // query heads per kv head, and in how many workgroups of G heads each they are served (round 4: any head
+                       // group — Falcon's 71 and StarCoder's 48 query heads on one kv head ran on the one-workgroup-per-head kernel)
+  // replayed device route (round 6, ns_common.h Affine): the context length moves with the captured graph's token counter —
+  // sl_kv = a.sl_kv + kdelta * *kmove.  Grid, keys_per_split and the partials' layout are those of the LONGEST context (nsplit ranges);
+  // ranges past the live length leave at once, a single live range writes the output row itself, the merge reads the live ones only.
+  const int* kmove;
+  int kdelta;
+  // ... and the ranges follow the LIVE length (round 6, second half): a plan laid out for n_ctx = 2048 (8 ranges of 256 keys) used to run 1530 cached positions
+  // on 6 of its 8 workgroups per head, 600 positions on 3 — with n_ctx = 4096 half as many again.  Every workgroup applies the host's range rule
+  // (attn_nsplit) to the live length itself: dyn_min_keys / dyn_batch_keys / dyn_single_below are that rule's constants for this launch, nsplit its
+  // upper bound (grid and partials' layout stay those of the longest context).  dyn_min_keys == 0: ranges as laid out (keys_per_split).
+  int dyn_min_keys, dyn_batch_keys, dyn_single_below;
+};
+// live context length / live ranges of a launch (kmove == nullptr: what the host said).  Host and device: tests/test_attn_plan.py walks every live
+// length of a plan through the two range functions.
+__host__ __device__ __forceinline__ int attn_live_kv(const AttnSplitParams& sp) { return sp.kmove ? sp.a.sl_kv + sp.kdelta * *sp.kmove : sp.a.sl_kv; }
+// keys per range at the live length (the host's rule: as many ranges as the launch has workgroups for, at least dyn_min_keys keys each, whole softmax batches)
+__host__ __device__ __forceinline__ int attn_live_kps(const AttnSplitParams& sp, int sl_kv) {
+  if (!sp.kmove || sp.dyn_min_keys <= 0) return sp.keys_per_split;
+  if (sl_kv <= sp.dyn_single_below) return max(sl_kv, 1);
+  const int want = max(1, min(sp.nsplit, (sl_kv + sp.dyn_min_keys - 1) / sp.dyn_min_keys));
+  int kps = (sl_kv + want - 1) / want;
+  if (sp.dyn_batch_keys > 1 && want > 1) kps = (kps + sp.dyn_batch_keys - 1) / sp.dyn_batch_keys * sp.dyn_batch_keys;
+  return kps;
+}
+__host__ __device__ __forceinline__ int attn_live_splits(const AttnSplitParams& sp, int sl_kv) {
+  if (!sp.kmove) return sp.nsplit;
+  const int kps = attn_live_kps(sp, sl_kv);
+  return max(1, (sl_kv + kps - 1) / kps);
+}
+
+// ---- the launch decision as a value (ns_attn_plan.cpp) -------------------------------------------------------------------------------------
+// Every tunable the decision reads.  attn_knobs() (ns_attn.cpp) fills it from ns_hip_set_tuning's atomics and the environment.
+struct AttnKnobs {
+  int attn_stream = 1;         // "attn_stream" / NS_ATTN_STREAM: 1 = head sizes 40 .. 128 stream K / V through LDS rings, 0 = through registers
+  int attn_mfma2_rows = 128;   // "attn_mfma2_rows" / NS_ATTN_MFMA2_ROWS: query rows from which the 128-row kernels serve a prefill
+  int attn_inlaunch = 0;       // "attn_inlaunch" / NS_ATTN_INLAUNCH: 1 = the last context range to finish merges inside the launch
+  int attn_heads_first = -1;   // "attn_heads_first" / NS_ATTN_HEADS_FIRST: dispatch order of a split launch, -1 = by the cache's layout
+  int wg_target = 1024, min_keys = 128;     // "attn_wg_target" / "attn_min_keys": range rule of the register kernel
+  int wg_target_s = 256, min_keys_s = 32;   // "attn_stream_wg_target" / "attn_stream_min_keys": ... of the ring kernel
+  bool no_mfma = false;        // NS_ATTN_NO_MFMA set: no matrix-core kernel (diagnostics)
+  int pipe = 1;                // NS_ATTN_PIPE: 0 = attn_mfma2_kernel where attn_mfma3_kernel would serve
+  int pvar = -1;               // NS_ATTN_PVAR: schedule variant of attn_mfma3_kernel, -1 = by length
+  bool no_xcd_map = false;     // NS_ATTN_NO_XCD_MAP set: plain workgroup order of the 128-row kernels (A/B)
+  bool v1 = false;             // NS_ATTN_V1 set: attn_kernel where a split kernel would serve (diagnostics)
+  bool dyn_ranges = true;      // NS_ATTN_DYN_RANGES=0: a moving context length keeps the ranges as laid out (A/B)
+  int alibi_heads = 0, alibi_off = 0;  // ns_hip_attn_set_head_partition
+  bool no_partials = false;    // not a tunable: launch_attn's second plan when the partials' scratch cannot be had — one range, still correct
+};
+enum AttnPath { AP_REFUSED = 0, AP_GENERIC, AP_SPLIT_REGS, AP_RING, AP_ROWS64, AP_ROWS128, AP_PIPELINED };
+// What a launch needs; nothing is decided after it.  sp.ws and sp.tickets are null: the launcher's scratch.
+struct AttnPlan {
+  AttnPath path = AP_REFUSED;
+  int G = 0, lpk = 0, dpl = 0;       // one-row paths: attn_split_kernel<G, dpl> / attn_stream_kernel<G, lpk>
+  int hs_pad = 0, sb = 0, pad = 0;   // matrix-core paths: attn_mfma_kernel<hs_pad> / attn_mfma2(_hs256)_kernel<hs_pad, sb, pad> / attn_mfma3_kernel<hs_pad>
+  AttnSplitParams sp;                // sp.a: the kernels' AttnParams; the rest (ranges, order, head groups, moving length): one-row paths
+  dim3 grid, block;
+  size_t lds = 0;                    // dynamic LDS bytes
+  bool want_tickets = false;         // ranges merge inside the launch if the stream's ticket buffer can be had
+  bool merge = false;                // attn_merge_kernel follows (also when tickets are wanted and cannot be had)
+  size_t partial_bytes = 0;          // of sp.ws
+  int nqb = 0, aligned = 0, xcd_map = 0;  // 128-row paths: query blocks per head, 16-byte stores of the output, XCD remap | variant << 8
+};
+bool attn_shape_ok(int head_num, int heads_kv, int head_size, int sl_q, int sl_kv, bool causal, std::string* why);
+// dst16: the optional fp16 shadow of dst (its alignment is part of the decision).  AP_REFUSED: *why says what is wrong with the call.
+AttnPlan attn_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst16, const AttnKnobs& knobs, const Affine& aff, std::string* why);
+// what bestla_fusion_attn_workspace_size answers: it knows neither strides nor alignment, so the most any plan of the shape can need
+size_t attn_ws_bytes(const AttnKnobs& knobs, int batch, int head_num, int heads_kv, int head_size, int sl_q, int sl_kv);
+
+// ---- launches of a plan ----------------------------------------------------------------------------------------------------------------------
+hipError_t launch_attn_onerow(const AttnPlan& pl, float* ws, uint32_t* tickets, hipStream_t st);  // ns_attn_decode.hip: AP_GENERIC, AP_SPLIT_REGS, AP_RING (+ merge)
+hipError_t launch_attn_rows(const AttnPlan& pl, hipStream_t st);                                  // ns_attn_prefill.hip: AP_ROWS64, AP_ROWS128, AP_PIPELINED
+// touch_attn_module (ns_common.h) makes the runtime load all three code objects
+inline void touch_kernel(const void* kernel) {
+  hipFuncAttributes fa;
+  (void)hipFuncGetAttributes(&fa, kernel);
+  (void)hipGetLastError();
+}
+void touch_attn_rows_module();  // ns_attn_prefill.hip
+void touch_kvcache_module();    // ns_kvcache.hip
+// Is a HIP device visible?  who != nullptr: if not, the error is set and "Err: invalid parameters (<who>: no HIP device visible ...)" goes to stderr.
+bool attn_device_visible(const char* who);
+
+}  // namespace ns

@@ -1,0 +1,225 @@
+// ns_attn_plan.cpp — which kernel serves an attention call, as a value.  attn_plan is a pure function of the call, the tunables and the moving
+// context length of a replayed route: no HIP call, no environment, no global, no scratch — tests/test_attn_plan.py runs it on the CPU over a grid
+// of cases against the table of docs/kernels/attention.md ("What tests which launch path").  Each rule is stated once, here.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "ns_attn.h"
+
+namespace ns {
+
+bool attn_shape_ok(int head_num, int heads_kv, int head_size, int sl_q, int sl_kv, bool causal, std::string* why) {
+  if (head_size < 1 || head_size > 256) {
+    *why = "attention: head_size must be 1..256";
+    return false;
+  }
+  if (heads_kv < 1 || head_num % heads_kv != 0) {
+    *why = "attention: head_num must be a multiple of heads_kv";
+    return false;
+  }
+  if (causal && sl_q > sl_kv) {
+    *why = "attention: causal needs sl_q <= sl_kv";
+    return false;
+  }
+  if (sl_q < 1 || sl_kv < 1) {
+    *why = "attention: empty sequence";
+    return false;
+  }
+  return true;
+}
+
+// query heads per workgroup of the split kernels (their template argument) and workgroups per kv head for a head group of g_full
+static void attn_groups(int g_full, int* G, int* chunks) {
+  *G = g_full <= 1 ? 1 : (g_full == 2 ? 2 : (g_full <= 4 ? 4 : 8));
+  *chunks = (g_full + *G - 1) / *G;
+}
+
+// ---- context ranges of a one-row launch ------------------------------------------------------------------------------------------------------
+// The register kernel aims at ~4 workgroups per CU with at least 128 keys per range.  The LDS-ring kernel has its own rule
+// (profiles/r05p_attn_stream.txt): a workgroup keeps 64 KiB in flight whatever its range, so ONE workgroup per CU streams best — 32 kv heads at
+// 2048 positions: 8 ranges of 256 keys 12.9 us (split + merge) against 13.7 with 16 x 128 and 15.2 with 32 x 64; 8 kv heads: 32 ranges of 64 keys
+// 13.5 us against 16.6 with 16 x 128 (128 workgroups: half the chip idle).
+// batch_keys (ring kernel): keys one softmax update of a workgroup covers (U steps); a range that is not a multiple of it computes masked key slots,
+// which costs where the update is VALU-heavy (8 query heads per workgroup: Falcon-7B's 71 heads on one kv head at 2048 keys, 29 ranges of 71 keys
+// 32.5 us against 16 x 128 keys 28.5) — ranges are rounded up to it while that leaves at least 128 workgroups.
+// heavy (workgroups that serve 4 or 8 query heads per key: twice the arithmetic per byte): two workgroups per CU overlap better than one once a batch
+// brings 64+ workgroups per range — batch 8 x 32 / 8 heads at 2048 keys 36.7 -> 32.0 us, batch 16 64.0 -> 50.5 (scripts/r05/attn_batch_rule.py).
+// single_below: a range's worth of keys on 32+ workgroups stays one range (the merge launch costs more than it saves, 7.0 vs 7.8 us).
+// min_keys, batch_keys and single_below are also what the workgroups of a moving-length launch apply to the live length (attn_live_kps).
+struct RangeRule {
+  int target, min_keys, batch_keys, single_below;
+};
+static RangeRule range_rule(const AttnKnobs& kn, size_t base_blocks, bool ring, int batch_keys, bool heavy) {  // base_blocks: workgroups per range
+  RangeRule r;
+  r.target = ring ? kn.wg_target_s : kn.wg_target;
+  if (ring && heavy && base_blocks >= 64) r.target *= 2;
+  r.min_keys = ring ? kn.min_keys_s : kn.min_keys;
+  r.batch_keys = ring ? batch_keys : 0;
+  r.single_below = ring && base_blocks >= 32 ? 128 : 0;
+  return r;
+}
+static int attn_nsplit(const RangeRule& r, size_t base_blocks, int sl_kv) {
+  if (sl_kv <= r.single_below) return 1;
+  int nsplit = int((r.target + base_blocks - 1) / base_blocks);
+  nsplit = std::min(nsplit, std::max(1, (sl_kv + r.min_keys - 1) / r.min_keys));
+  nsplit = std::min(nsplit, 64);
+  if (r.batch_keys > 0 && nsplit > 1) {
+    const int kps = ((sl_kv + nsplit - 1) / nsplit + r.batch_keys - 1) / r.batch_keys * r.batch_keys;
+    const int rounded = (sl_kv + kps - 1) / kps;
+    if (size_t(rounded) * base_blocks >= 128) nsplit = rounded;
+  }
+  return nsplit;
+}
+// partials of nsplit ranges: [batch][sl_q][head][nsplit][2 + head_size] floats
+static size_t attn_partial_bytes(int batch, int sl_q, int head_num, int head_size, int nsplit) {
+  return nsplit > 1 ? size_t(batch) * sl_q * head_num * nsplit * (2 + head_size) * 4 : 0;
+}
+size_t attn_ws_bytes(const AttnKnobs& kn, int batch, int head_num, int heads_kv, int head_size, int sl_q, int sl_kv) {
+  int G, chunks;
+  attn_groups(head_num / std::max(1, heads_kv), &G, &chunks);
+  const size_t bb = size_t(heads_kv) * chunks * sl_q * batch;
+  int ns = 1;  // any rule a plan of this shape can take
+  for (int rule = 0; rule < 3; rule++) ns = std::max(ns, attn_nsplit(range_rule(kn, bb, rule > 0, 0, rule == 2), bb, sl_kv));
+  return attn_partial_bytes(batch, sl_q, head_num, head_size, ns);
+}
+
+// K / V rows of a head lie inside a 32-bit buffer descriptor (the DMA kernels: attn_stream_kernel, attn_mfma3_kernel)
+static bool attn_in32(int sl_kv, long long step_k_sl, long long step_v_sl) {
+  return (size_t(sl_kv) * size_t(step_k_sl) + 256) * 2 < (size_t(1) << 32) && (size_t(sl_kv) * size_t(step_v_sl) + 256) * 2 < (size_t(1) << 32);
+}
+
+AttnPlan attn_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst16, const AttnKnobs& kn, const Affine& aff, std::string* why) {
+  AttnPlan pl;
+  memset(&pl.sp, 0, sizeof(pl.sp));
+  auto refuse = [&](const char* text) {
+    *why = text;
+    return pl;
+  };
+  if (a.Q_layout != ATTN_FWD_LAYOUT_PLAIN || a.K_layout != ATTN_FWD_LAYOUT_PLAIN || a.V_layout != ATTN_FWD_LAYOUT_PLAIN ||
+      a.dst_layout != ATTN_FWD_LAYOUT_PLAIN)
+    return refuse("attention: only ATTN_FWD_LAYOUT_PLAIN tensors are supported");
+  if (!attn_shape_ok(a.head_num, a.heads_kv, a.head_size, a.sl_q, a.sl_kv, (a.attn_flags & NS_ATTN_FLAG_IS_CAUSAL) != 0, why)) return pl;
+  AttnParams& p = pl.sp.a;
+  p.q = a.Q;
+  p.k = reinterpret_cast<const _Float16*>(a.K);
+  p.v = reinterpret_cast<const _Float16*>(a.V);
+  p.dst = a.dst;
+  p.dst16 = static_cast<_Float16*>(const_cast<void*>(dst16));
+  p.qk_scale = a.QK_scale * a.Q_sc * a.K_sc;
+  p.out_scale = a.V_sc / a.dst_sc;
+  p.flags = a.attn_flags;
+  p.head_num = a.head_num, p.heads_kv = a.heads_kv, p.head_size = a.head_size, p.sl_q = a.sl_q, p.sl_kv = a.sl_kv;
+  p.step_q_bs = a.step_q_bs, p.step_q_head_num = a.step_q_head_num, p.step_q_sl = a.step_q_sl;
+  p.step_k_bs = a.step_k_bs, p.step_k_head_num = a.step_k_head_num, p.step_k_sl = a.step_k_sl;
+  p.step_k_head_size = a.step_k_head_size;
+  p.step_v_bs = a.step_v_bs, p.step_v_head_num = a.step_v_head_num, p.step_v_sl = a.step_v_sl;
+  p.step_v_head_size = a.step_v_head_size;
+  p.step_dst_bs = a.step_dst_bs, p.step_dst_head_num = a.step_dst_head_num, p.step_dst_sl = a.step_dst_sl;
+  p.hs_pad = a.head_size <= 64 ? 64 : (a.head_size <= 128 ? 128 : 256);
+  // mha_dense_wrapper.h:1418-1447: under tensor parallelism the slopes follow the FULL model's head count and this
+  // rank's first head (the reference takes world/rank from parallel_context; here ns_hip_attn_set_head_partition)
+  const int all_heads = kn.alibi_heads > 0 ? kn.alibi_heads : a.head_num;
+  p.alibi_head_off = kn.alibi_heads > 0 ? kn.alibi_off : 0;
+  if (p.alibi_head_off < 0 || p.alibi_head_off + a.head_num > all_heads)
+    return refuse("attention: head partition (ns_hip_attn_set_head_partition) does not contain this call's heads");
+  const int lf = 1 << int(floor(log2(double(all_heads))));
+  p.alibi_log2_floor = lf;
+  p.alibi_m0 = powf(2.0f, -8.f / float(lf));
+  p.alibi_m1 = powf(2.0f, -4.f / float(lf));
+  if (a.head_num > 65535 || a.batch_size > 65535) return refuse("attention: head_num / batch_size above the grid limit");
+  // replayed device route (ns_route.cpp): the context length of a captured decode step moves with the graph's token counter
+  if (aff.k && (a.sl_q != 1 || aff.cap < a.sl_kv))
+    return refuse("attention: a moving context length is served for decode steps (one query row) within the cache's capacity");
+  // what every kernel but attn_kernel asks of K and V: a contiguous head dimension and 16-byte aligned rows
+  const bool rows_ok = a.step_k_head_size == 1 && a.step_v_head_size == 1 && a.step_k_sl % 8 == 0 && a.step_v_sl % 8 == 0 &&
+                       a.step_k_head_num % 8 == 0 && a.step_v_head_num % 8 == 0 && a.step_k_bs % 8 == 0 &&
+                       a.step_v_bs % 8 == 0 && (reinterpret_cast<uintptr_t>(a.K) & 15) == 0 &&
+                       (reinterpret_cast<uintptr_t>(a.V) & 15) == 0;
+
+  // ---- several query rows: matrix cores ----
+  const bool biased = (a.attn_flags & (NS_ATTN_FLAG_IS_ALIBI8 | NS_ATTN_FLAG_IS_TANH30)) != 0;
+  const size_t nqb = (size_t(a.sl_q) + 127) / 128, wgs2 = nqb * a.head_num * a.batch_size;
+  // the 128-row kernels pad any head size that is a multiple of 8 to 64 / 128 / 256; the 64-row kernel takes 64 and 128 as they are and has no biased
+  // form.  Shapes it cannot take use the 128-row kernels from 16 rows on: a workgroup with idle waves is still far from the one-row-per-workgroup
+  // kernel they would fall to.  The 128-row kernels take the maximum of RAW scores: other score scales than positive ones go to the 64-row kernel.
+  const bool exact = a.head_size == 64 || a.head_size == 128;
+  const bool only128 = biased || !exact;
+  const bool rows128 = a.sl_q >= (only128 ? 16 : kn.attn_mfma2_rows) && wgs2 < (size_t(1) << 31) && (biased || p.qk_scale > 0.f);
+  if (!kn.no_mfma && a.sl_q >= 16 && a.head_size % 8 == 0 && a.head_size <= 256 && rows_ok && (!only128 || rows128)) {
+    pl.block = dim3(256);
+    pl.hs_pad = p.hs_pad;
+    if (!rows128) {  // 64-row workgroups, 16x16x32 MFMA (attn_mfma_kernel)
+      pl.path = AP_ROWS64;
+      pl.grid = dim3(unsigned((a.sl_q + 63) / 64), unsigned(a.head_num), unsigned(a.batch_size));
+      return pl;
+    }
+    // 128-row workgroups, 32x32x16 MFMA, K / V tiles shared through LDS
+    pl.nqb = int(nqb);
+    pl.grid = dim3(unsigned(wgs2));
+    pl.aligned = (reinterpret_cast<uintptr_t>(a.dst) & 15) == 0 && a.step_dst_sl % 4 == 0 && a.step_dst_head_num % 4 == 0 &&
+                 a.step_dst_bs % 4 == 0 && (!dst16 || (reinterpret_cast<uintptr_t>(dst16) & 7) == 0);
+    pl.sb = biased;
+    pl.pad = !exact && a.head_size != 256;
+    pl.lds = size_t(2) * (pl.hs_pad == 64 ? a2_stage_bytes<64>() : pl.hs_pad == 128 ? a2_stage_bytes<128>() : a2_stage_bytes<256>());
+    pl.xcd_map = !kn.no_xcd_map && (size_t(a.heads_kv) * a.batch_size) % 8 == 0;
+    // round 6: K / V tiles by DMA (attn_mfma3_kernel) for the exact head sizes without score bias, rows inside a 32-bit buffer descriptor; NS_ATTN_PIPE=0:
+    // attn_mfma2_kernel.  Variant (NS_ATTN_PVAR): bit 0 = the next tile is requested behind K.Q^T instead of in front of it, bit 1 = raised priority while
+    // K.Q^T issues — both gain from 4096 keys on (601-611 vs 558-585 TFLOPS causal, 742-751 vs 722 at 8192) and lose below (519-525 vs 529-530 at 2048)
+    if (kn.pipe && !biased && exact && attn_in32(a.sl_kv, a.step_k_sl, a.step_v_sl)) {
+      pl.path = AP_PIPELINED;
+      pl.xcd_map |= (kn.pvar >= 0 ? kn.pvar : (a.sl_kv >= 3072 ? 3 : 0)) << 8;
+    } else {
+      pl.path = AP_ROWS128;
+    }
+    return pl;
+  }
+
+  // ---- one query row per workgroup ----
+  pl.block = dim3(kAttnThreads);
+  int G, chunks;
+  attn_groups(a.head_num / a.heads_kv, &G, &chunks);
+  const int dpl = a.head_size <= 128 ? 8 : 16;  // head dims per lane of the register kernel
+  const size_t base_blocks = size_t(a.heads_kv) * a.sl_q * chunks;  // workgroups per range and batch entry
+  if (kn.v1 || !rows_ok || a.head_size % dpl != 0 || base_blocks > 65535) {
+    pl.path = AP_GENERIC;
+    pl.grid = dim3(unsigned(a.sl_q), unsigned(a.head_num), unsigned(a.batch_size));
+    return pl;
+  }
+  AttnSplitParams& sp = pl.sp;
+  sp.g_full = a.head_num / a.heads_kv, sp.chunks = chunks;
+  const int rule_kv = aff.k ? int(aff.cap) : a.sl_kv;  // (moving length: ranges, partials and descriptors laid out for the longest context)
+  // the LDS rings: head sizes 40 .. 128 (72 .. 128: sixteen lanes per key; 40 .. 64: eight — with sixteen, half of a request's lanes would carry
+  // nothing: measured slower from 4096 positions on), row offsets inside a 32-bit buffer descriptor, 16-byte query loads
+  const bool q16 = (reinterpret_cast<uintptr_t>(a.Q) & 15) == 0 && a.step_q_bs % 4 == 0 && a.step_q_head_num % 4 == 0 && a.step_q_sl % 4 == 0;
+  const bool stream = a.head_size > 32 && a.head_size <= 128 && attn_in32(rule_kv, a.step_k_sl, a.step_v_sl) && q16 && kn.attn_stream != 0;
+  const int lpk = a.head_size > 64 ? 16 : 8;
+  const int batch_keys = (G * 8 <= 16 ? 4 : 2) * 4 * (64 / lpk);  // attn_stream_kernel's U x keys per workgroup step
+  // head sizes above 128 (register kernel, 16 dims per lane) take the ring kernel's range rule too: 16 x 256 heads 14.6 -> 10.4 us at 512 keys,
+  // 51.8 -> 36.5 at 8192; 8 heads on one kv head 51 -> 40 at 2048 (scripts/r05/attn_regs_rule.py; head sizes <= 32 lose with it at 2048+ keys)
+  const RangeRule rule = range_rule(kn, base_blocks * a.batch_size, stream || a.head_size > 128, stream ? batch_keys : 0, stream && G >= 4);
+  const int nsplit = kn.no_partials ? 1 : attn_nsplit(rule, base_blocks * a.batch_size, rule_kv);
+  sp.nsplit = nsplit;
+  sp.keys_per_split = (rule_kv + nsplit - 1) / nsplit;
+  sp.kmove = aff.k, sp.kdelta = int(aff.delta);
+  if (aff.k && nsplit > 1 && kn.dyn_ranges && a.sl_q == 1)  // the rule's constants, for the workgroups to apply to the live length
+    sp.dyn_min_keys = rule.min_keys, sp.dyn_batch_keys = rule.batch_keys, sp.dyn_single_below = rule.single_below;
+  // partials go to the caller's workspace (`tmp`, sized by bestla_fusion_attn_workspace_size) or the stream's scratch
+  pl.partial_bytes = attn_partial_bytes(a.batch_size, a.sl_q, a.head_num, a.head_size, nsplit);
+  // (the replayed route merges inside the launch: one launch less per layer of a token that is all launches — profiles/r05r_*)
+  pl.want_tickets = nsplit > 1 && (kn.attn_inlaunch != 0 || (aff.k && aff.inlaunch)) && base_blocks * a.batch_size <= kAttnTicketCap;
+  pl.merge = nsplit > 1 && !pl.want_tickets;
+  // dispatch order (round 5, profiles/r05m_attn_layout_order_ab.txt): on a position-major cache ([position][head][dim]: a head's rows are
+  // pieces one position stride apart) neighbouring workgroups should be neighbouring HEADS of one context range — split + merge 14.3 -> 13.7 us
+  // at 2048 positions, 22.0 -> 19.9 at 4096 (Llama-2-7B shape); on a head-major cache (one slab per head) the ranges of one head first
+  // (20.7 vs 23.4 us at 4096).  ns_hip_set_tuning("attn_heads_first", 0 / 1) forces one, -1 = by layout.
+  sp.heads_first = kn.attn_heads_first < 0 ? a.step_k_head_num < a.step_k_sl : kn.attn_heads_first != 0;
+  pl.grid = sp.heads_first ? dim3(unsigned(base_blocks), unsigned(nsplit), unsigned(a.batch_size))
+                           : dim3(unsigned(nsplit), unsigned(base_blocks), unsigned(a.batch_size));
+  pl.path = stream ? AP_RING : AP_SPLIT_REGS;
+  pl.G = G, pl.lpk = stream ? lpk : 16, pl.dpl = stream ? 8 : dpl;
+  pl.lds = stream ? kAsLdsBytes : size_t(4) * G * 16 * dpl * 4;  // the ring / attn_split_finish's acc_s: [4 waves][G][16 * dpl] floats
+  return pl;
+}
+
+}  // namespace ns

@@ -212,7 +212,7 @@ hipError_t launch_smallm(const SmallMArgs& a, hipStream_t st);
 // ns_gemm.hip: second-generation prefill GEMM; hipErrorNotSupported = use the first-generation gemm_kernel
 hipError_t launch_gemm2(const SmallMArgs& a, hipStream_t st);
 void gemm_scratch_release();  // frees the per-stream scratch buffers
-// grow-only device scratch per (stream, slot): slot 0 = fp16 copy of A (prefill GEMM), 1 = attention partials, (4, 6, 7: ns_i8ref.hip; 10-13: ns_attn.hip host entries; 21: ns_gemvs.hip split-K tickets;)
+// grow-only device scratch per (stream, slot): slot 0 = fp16 copy of A (prefill GEMM), 1 = attention partials, (4, 6, 7: ns_i8ref.hip; 10-13: ns_kvcache.hip host entries; 21: ns_gemvs.hip split-K tickets;)
 // 2 = split-K partials, 3 = shuffled activations.  Safe under stream capture (buffers handed out while capturing are
 // never freed or moved until gemm_scratch_release()); nullptr only when the allocation itself fails.
 void* stream_scratch(hipStream_t st, size_t bytes, int slot);
@@ -228,7 +228,7 @@ void set_gemv_mode(int mode);  // 0 off (first-generation kernel), 1 on, -1 re-r
 hipError_t launch_gemvs(const SmallMArgs& a, hipStream_t st);
 void set_gemvs_tuning(int what, int value);  // what: 0 mode (0 off, 1 from 2 rows, 2 from 1 row), 1 slices, 2 waves, 3 workgroups
 void set_attn_tuning(int wg_target, int min_keys);
-void set_attn_heads_first(int on);  // ns_attn.hip: dispatch order of the decode attention's workgroups (AttnSplitParams::heads_first)
+void set_attn_heads_first(int on);  // ns_attn.cpp: dispatch order of the decode attention's workgroups (AttnSplitParams::heads_first)
 void set_gemv_planes(int on);  // 1 (default): bit-plane formats stream their native records at decode (ns_weight::native); 0: the widened ones
 void set_attn_mfma2_rows(int rows);  // query rows from which the 128-row prefill attention kernel is used (default 128; huge = never)
 void set_attn_stream_tuning(int wg_target, int min_keys);  // context-range rule of the LDS-ring kernel (defaults 256 workgroups, >= 32 keys)
@@ -242,7 +242,7 @@ struct HostScope {
   explicit HostScope(const char* n);
   ~HostScope();
 };
-void kv_mirrors_clear();  // ns_attn.hip: drops the device mirrors of library-managed kv caches (ns_hip_cache_clear)
+void kv_mirrors_clear();  // ns_kvcache.hip: drops the device mirrors of library-managed kv caches (ns_hip_cache_clear)
 void set_i8_tile(int tile);     // ns_i8ref.hip: workgroup tile of i8mfma2_kernel (0 = by size)
 void set_i8_mfma_gen(int gen);  // ns_i8ref.hip: 2 = i8mfma2_kernel for nibble containers (default), 1 = i8mfma_kernel everywhere
 void set_moe_tuning(int what, int value);  // ns_moe.hip: row threshold of what = 0 the decode kernel (m <= value), 1 the grouped path (m >= value); 0 = default, < 0 = off
@@ -253,7 +253,7 @@ bool gemm3_f8_on();
 // may this weight's prompt-size GEMMs run on the tiled kernel (ns_gemm.hip)?  Every integer / f4 weight; fp8 ones while "g3_f8" is on and the
 // load found range factors for them (ns_weight::g2_ok)
 bool gemm3_takes(const ns_weight* w);
-void set_gemm3_bm(int bm);  // ns_gemm.hip: force gemm3_kernel's row-tile height (tests / A-B runs); 0 = automatic  // ns_attn.hip: context-split rule of the decode attention kernel
+void set_gemm3_bm(int bm);  // ns_gemm.hip: force gemm3_kernel's row-tile height (tests / A-B runs); 0 = automatic  // ns_attn.cpp: context-split rule of the decode attention kernel
 void set_decode_waves(int nw);  // 0 = by shape
 void set_gemv_rows1(int on);    // 1 (default): one-row launches of gemv_kernel take its one-row instantiation; 0: the general one (same bits)
 int decode_waves(int grid, int ks, bool dual);  // waves per workgroup of a decode launch (both kernel generations)
@@ -309,10 +309,10 @@ struct Affine {
   const int* k = nullptr;
   long long delta = 0;
   long long delta2 = 0;  // launch_dup2: the second copy's destination
-  long long cap = 0;     // decode attention (ns_attn.hip): the largest value the moving context length can take (the cache's n_ctx)
+  long long cap = 0;     // decode attention (ns_attn_plan.cpp): the largest value the moving context length can take (the cache's n_ctx)
   int inlaunch = 1;      // decode attention: the context ranges merge inside the launch (tickets)
 };
-// ns_attn.hip: per-stream scratch of a moving-length decode attention, allocated before the capture that uses it
+// ns_attn.cpp: per-stream scratch of a moving-length decode attention, allocated before the capture that uses it
 bool attn_prepare_moving(hipStream_t st, int batch, int heads, int heads_kv, int head_size, int cap);
 // One function per translation unit with kernels of the hot paths: asks the runtime for one kernel's attributes, which makes it load that unit's code object
 // for the device NOW (HIP loads a code object at the first launch from it: 36 ms for the tiled GEMM's, 21 ms for the decode GEMV's — otherwise paid by the first

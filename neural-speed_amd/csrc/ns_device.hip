@@ -13,7 +13,7 @@
 //                       V [batch][heads][head_size][n_ctx] (ne_bestla_sycl.cpp:592-880; llama.cpp:241-285 lays the cache
 //                       out like that).  One workgroup per (head, query row, batch): scores, soft-max in LDS, P*V.
 //                       HBM-bound on the kv stream; written for correctness first — the tuned kernels of this library
-//                       (ns_attn.hip) read an fp16 cache, which the reference's device path does not create.
+//                       (ns_attn_decode.hip, ns_attn_prefill.hip) read an fp16 cache, which the reference's device path does not create.
 // "queue" is a hipStream_t throughout.
 #include <hip/hip_runtime.h>
 #include <vector>
@@ -150,7 +150,7 @@ __global__ __launch_bounds__(256) void mha_f32_kernel(const float* q, const floa
 // TRANSPOSED V (8 consecutive per lane).  Partials (max, sum, unnormalised output) go to a per-stream workspace,
 // mha_f32_merge_kernel combines them (one launch more; a single range writes the output itself).
 constexpr int kMhaKS = 128;  // keys per workgroup
-// stores / loads past every cache (sc0 sc1): partial results cross XCDs inside one launch (as ns_attn.hip st_through / ld_through)
+// stores / loads past every cache (sc0 sc1): partial results cross XCDs inside one launch (as ns_attn_decode.hip st_through / ld_through)
 __device__ __forceinline__ void dev_st_through(float* p, float v) {
   __hip_atomic_store(reinterpret_cast<uint32_t*>(p), __builtin_bit_cast(uint32_t, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }

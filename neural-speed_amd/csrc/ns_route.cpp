@@ -1068,7 +1068,7 @@ bool make_plan() {
       const size_t nsplit_max = size_t((i[6] + 127) / 128);
       if (!stream_scratch(R.st, size_t(i[0]) * i[1] * i[3] * nsplit_max * (2 + i[5]) * sizeof(float), 24)) return false;
       if (!stream_scratch_zeroed(R.st, 65536 * 4, 25)) return false;  // the tickets of the merge inside the launch (ns_device.hip)
-      // ... and what the fp16-mirror form needs (ns_attn.hip, moving context length)
+      // ... and what the fp16-mirror form needs (ns_attn.cpp, moving context length)
       if (kv16_enabled() && !attn_prepare_moving(R.st, int(i[0]), int(i[3]), int(i[4]), int(i[5]), int(i[6]))) return false;
     }
   // the launches (fused where possible), then segments of about seg_ops() of them.  A segment may end only where the launches so far

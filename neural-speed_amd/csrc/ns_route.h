@@ -5,7 +5,7 @@
 // V transposed [batch][heads_kv][head_size][n_ctx] (/root/reference/neural_speed/models/llama/llama.cpp:241-285, core/layers/ne_bestla_sycl.cpp:592-880).
 // At 1500 cached positions a decode step streams 49 MB of K / V per layer from it.  The reference's own DEFAULT caches are fp16
 // (models/model_utils/model_types.h:96-100 KV_MEM_TYPE_AUTO: the BesTLA-managed cache, else fp16; model_utils.cpp:252, :1072-1076), and this library's
-// tuned attention kernels (ns_attn.hip: LDS-ring decode kernel, matrix-core prefill kernels) read fp16 rows [head][position][head_size].  The mirror is that:
+// tuned attention kernels (ns_attn_decode.hip: LDS-ring decode kernel, ns_attn_prefill.hip: matrix-core prefill kernels) read fp16 rows [head][position][head_size].  The mirror is that:
 // an fp16 copy of the cache in ONE layout for K and V, kept beside the fp32 tensors, which stay the reference's (every cell is still written as the
 // graph asks: whoever copies the cache out sees what the reference's device build would have put there).  Attention reads the mirror on EVERY path —
 // prompt, eager decode step, replayed decode step — so a chunked prompt and a token-by-token evaluation see the same K / V (round 5 rounded

@@ -451,7 +451,7 @@ void ns_hip_cache_clear(void) {
     g_cache.clear();
     g_cache_bytes = 0;
   }
-  kv_mirrors_clear();  // ns_attn.hip: device mirrors of library-managed kv caches
+  kv_mirrors_clear();  // ns_kvcache.hip: device mirrors of library-managed kv caches
 }
 
 int ns_hip_blob_validate(const void* host_blob, size_t avail_bytes) {

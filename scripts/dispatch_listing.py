@@ -7,7 +7,9 @@ selects one) dispatch alike when their listings are identical:
 
 Kernel names per case: run it under `rocprofv3 --kernel-trace --output-format csv -d DIR -o t -- python scripts/dispatch_listing.py`
 and print the trace with `python scripts/dispatch_listing.py --trace DIR/.../t_kernel_trace.csv` (a one-element silu launch in front of
-every case is the separator; the line's index is the listing's)."""
+every case is the separator; the line's index is the listing's; per kernel: name, grid in work-items, LDS bytes).  `--only PREFIX` runs
+the cases whose name starts with PREFIX, e.g. `--only attn` (a trace of such a run numbers the cases it ran from 000); NS_ATTN_PIPE=0 in the environment moves the "attn pipelined" cases to the
+register-staged 128-row kernel."""
 import ctypes as C, csv, hashlib, os, re, sys
 
 if "--trace" in sys.argv:
@@ -25,8 +27,8 @@ if "--trace" in sys.argv:
             if cur is not None:
                 print("%03d %s" % (idx, " | ".join(cur)))
             idx, cur = idx + 1, []
-        elif cur is not None:
-            cur.append(n)
+        elif cur is not None:  # name, grid in work-items, LDS bytes of a workgroup
+            cur.append("%s grid %s,%s,%s lds %s" % (n, r.get("Grid_Size_X"), r.get("Grid_Size_Y"), r.get("Grid_Size_Z"), r.get("LDS_Block_Size")))
     if cur is not None:
         print("%03d %s" % (idx, " | ".join(cur)))
     sys.exit(0)
@@ -123,8 +125,14 @@ mark = torch.zeros(4, device="cuda")
 count = [0]
 
 
+ONLY = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else ""  # run the cases whose name starts so (the indices stay)
+
+
 def case(name, fn):
     """fn() -> (rc, output tensors)"""
+    if not name.startswith(ONLY):
+        count[0] += 1
+        return
     L.ns_hip_reset_error()
     L.ns_hip_silu_f32(mark.data_ptr(), mark.data_ptr(), 1, ST)
     try:
@@ -356,6 +364,68 @@ case("refuse ffn2 no tmp1", ffn2("s4_C", "s4_D", 4, no_tmp=True))
 case("refuse compute mode 7", lambda: (L.ns_hip_set_compute_mode(7), []))
 case("refuse tuning key", lambda: (L.ns_hip_set_tuning(b"no_such_key", 1), []))
 case("refuse tuning gv_nw 3", lambda: (L.ns_hip_set_tuning(b"gv_nw", 3), []))
+# ---- attention (ns_hip_attn_fp32_fp16_fp16_fp32_forward_h): two cases or more per row of the path table of docs/kernels/attention.md
+arng = np.random.default_rng(77)
+
+
+def attn(bs, hn, hkv, hs, slq, slkv, flags=0, kt=False, shadow=False, scale=None, head_major=False, q_off=0, tuning=()):
+    def fn():
+        q = dev(arng.standard_normal(bs * slq * hn * hs + 4, dtype=np.float32))
+        k = dev(arng.standard_normal(bs * slkv * hkv * hs, dtype=np.float32).astype(np.float16))
+        v = dev(arng.standard_normal(bs * slkv * hkv * hs, dtype=np.float32).astype(np.float16))
+        d, d16 = out32(bs * slq * hn * hs), out16(bs * slq * hn * hs) if shadow else None
+        a = pkg.attn_args(q.data_ptr() + 4 * q_off, k.data_ptr(), v.data_ptr(), d.data_ptr(), bs, hn, hkv, hs, slq, slkv,
+                          hs ** -0.5 if scale is None else scale, flags, kt)
+        if head_major:  # K / V [bs][hkv][sl_kv][hs]: one slab per head
+            a.step_k_head_num = a.step_v_head_num = slkv * hs
+            a.step_k_sl = a.step_v_sl = hs
+        for key, value, _ in tuning:
+            L.ns_hip_set_tuning(key, value)
+        try:
+            rc = L.ns_hip_attn_fp32_fp16_fp16_fp32_forward_h(C.byref(a), ptr(d16), ST)
+        finally:
+            for key, _, restore in tuning:
+                L.ns_hip_set_tuning(key, restore)
+        del keep[-3:]
+        return rc, [d, d16]
+    return fn
+
+
+CAUSAL, ALIBI, TANH = 1, 2, 8
+case("attn generic transposed K (1,8,8,128,4,260)", attn(1, 8, 8, 128, 4, 260, kt=True))
+case("attn generic head size 20", attn(1, 4, 4, 20, 2, 70, CAUSAL))
+case("attn regs head size 32 300 keys", attn(1, 8, 8, 32, 1, 300))
+case("attn regs head size 256 520 keys", attn(1, 8, 8, 256, 1, 520, shadow=True))
+case("attn regs attn_stream=0 (1,8,2,64,1,600)", attn(1, 8, 2, 64, 1, 600, tuning=((b"attn_stream", 0, 1),)))
+case("attn regs unaligned Q", attn(1, 8, 8, 128, 1, 300, q_off=1))
+case("attn ring (1,32,32,128,1,2048)", attn(1, 32, 32, 128, 1, 2048, shadow=True))
+case("attn ring (1,8,2,64,1,600)", attn(1, 8, 2, 64, 1, 600))
+case("attn ring 71 heads on one kv head", attn(1, 71, 1, 64, 1, 520))
+case("attn ring alibi 3 rows", attn(1, 8, 4, 128, 3, 300, ALIBI | CAUSAL))
+case("attn ring one range (1,4,4,128,3,2)", attn(1, 4, 4, 128, 3, 2))
+case("attn ring batch 2 with a head group", attn(2, 8, 2, 128, 1, 700))
+case("attn ring attn_inlaunch=1", attn(1, 8, 8, 128, 1, 2048, tuning=((b"attn_inlaunch", 1, 0),)))
+case("attn regs attn_inlaunch=1 head size 256", attn(1, 8, 8, 256, 1, 1024, tuning=((b"attn_inlaunch", 1, 0),)))
+for hf in (0, 1):
+    case("attn ring attn_heads_first=%d" % hf, attn(1, 8, 8, 128, 1, 1024, tuning=((b"attn_heads_first", hf, -1),)))
+    case("attn ring head-major cache attn_heads_first=%d" % hf, attn(1, 8, 8, 128, 1, 1024, head_major=True, tuning=((b"attn_heads_first", hf, -1),)))
+case("attn ring head-major cache", attn(1, 8, 8, 128, 1, 1024, head_major=True))
+case("attn 64-row (1,4,4,64,40,40)", attn(1, 4, 4, 64, 40, 40, CAUSAL))
+case("attn 64-row (1,8,8,128,64,64)", attn(1, 8, 8, 128, 64, 64, CAUSAL, shadow=True))
+case("attn 64-row negative scale, 150 rows", attn(1, 4, 4, 128, 150, 150, scale=-0.1))
+case("attn 128-row biased alibi 16 rows", attn(1, 8, 8, 128, 16, 16, ALIBI | CAUSAL))
+case("attn 128-row biased tanh head size 64", attn(1, 4, 2, 64, 40, 200, TANH))
+case("attn 128-row padded head size 80", attn(1, 4, 4, 80, 40, 40, CAUSAL))
+case("attn 128-row padded head size 160 alibi", attn(1, 4, 4, 160, 130, 130, ALIBI | CAUSAL, shadow=True))
+case("attn 128-row head size 256", attn(1, 4, 4, 256, 40, 40, CAUSAL))
+case("attn 128-row head size 256 tanh", attn(1, 4, 2, 256, 130, 300, TANH))
+case("attn pipelined 40 rows with attn_mfma2_rows=16 (NS_ATTN_PIPE=0: 128-row plain)",attn(1, 8, 8, 128, 40, 40, CAUSAL, tuning=((b"attn_mfma2_rows", 16, 128),)))
+case("attn pipelined (1,8,8,128,128,128)", attn(1, 8, 8, 128, 128, 128, CAUSAL, shadow=True))
+case("attn pipelined head size 64, 257 rows, batch 2, head group", attn(2, 8, 4, 64, 257, 300, CAUSAL))
+case("attn pipelined variant 3 (1,2,2,64,128,3072)", attn(1, 2, 2, 64, 128, 3072))
+case("attn pipelined variant 3 causal 3100 keys", attn(1, 2, 1, 128, 130, 3100, CAUSAL))
+case("attn refuse causal with more rows than keys", attn(1, 4, 4, 64, 8, 4, CAUSAL))
+case("attn refuse head group", attn(1, 6, 4, 64, 1, 64))
 L.ns_hip_silu_f32(mark.data_ptr(), mark.data_ptr(), 1, ST)
 torch.cuda.synchronize()
 for w in W.values():

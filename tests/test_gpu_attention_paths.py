@@ -1,4 +1,4 @@
-"""The branches of launch_attn (neural-speed_amd/csrc/ns_attn.hip) that no other attention test lands on, each against nso.attn_ref:
+"""The branches of launch_attn (neural-speed_amd/csrc/ns_attn.cpp) that no other attention test lands on, each against nso.attn_ref:
 the long-key schedule of attn_mfma3_kernel (sl_kv >= 3072: the next tile requested behind K.Q^T, idle waves requesting in a branch of
 their own) and its bit-equality with the short-key schedule, the 128-row kernels over the library-managed head-major cache with NaN
 bytes behind the appended rows, tensor scales and a non-positive score scale on the matrix-core kernels, unmasked attention with more
