@@ -16,6 +16,7 @@
 
 #include "ns_api_int.h"
 #include "ns_route.h"
+#include "ns_route_op.h"
 
 using namespace ns;  // NOLINT
 
@@ -261,12 +262,7 @@ int ns_hip_rope_f32(const float* dSrc, float* dDst, int batch, int seq, int head
                     int mode, float freq_base, float freq_scale, float ext_factor, float attn_factor, void* stream) {
   if (!have_device()) return -1;
   if (route_hook(stream)) {  // the reference's device route: described, verified against the plan, replayed (ns_route.cpp)
-    RouteOp op;
-    memset(&op, 0, sizeof(op));
-    op.kind = RK_ROPE, op.p[0] = dSrc, op.p[1] = dDst;
-    op.i[0] = batch, op.i[1] = seq, op.i[2] = heads, op.i[3] = head_size, op.i[4] = n_past, op.i[5] = n_dims, op.i[6] = mode;
-    op.f[0] = freq_base, op.f[1] = freq_scale, op.f[2] = ext_factor, op.f[3] = attn_factor;
-    return route_submit(op);
+    return route_submit(route_op_rope(dSrc, dDst, batch, seq, heads, head_size, n_past, n_dims, mode, freq_base, freq_scale, ext_factor, attn_factor));
   }
   if (!dSrc || !dDst || batch < 0 || seq < 0 || heads < 0 || head_size <= 0 || (head_size & 1) || n_dims <= 0 ||
       (n_dims & 1) || n_dims > head_size || n_past < 0) {
@@ -331,12 +327,8 @@ int ns_hip_rope_f32_yarn(const float* dSrc, float* dDst, int batch, int seq, int
                          int n_dims, int mode, float freq_base, float freq_scale, int n_orig_ctx, float ext_factor,
                          float attn_factor, float beta_fast, float beta_slow, void* stream) {
   if (route_hook(stream)) {
-    RouteOp op;
-    memset(&op, 0, sizeof(op));
-    op.kind = RK_ROPE_YARN, op.p[0] = dSrc, op.p[1] = dDst;
-    op.i[0] = batch, op.i[1] = seq, op.i[2] = heads, op.i[3] = head_size, op.i[4] = n_past, op.i[5] = n_dims, op.i[6] = mode, op.i[7] = n_orig_ctx;
-    op.f[0] = freq_base, op.f[1] = freq_scale, op.f[2] = ext_factor, op.f[3] = attn_factor, op.f[4] = beta_fast, op.f[5] = beta_slow;
-    return route_submit(op);
+    return route_submit(route_op_rope_yarn(dSrc, dDst, batch, seq, heads, head_size, n_past, n_dims, mode, freq_base, freq_scale, n_orig_ctx, ext_factor, attn_factor,
+                                           beta_fast, beta_slow));
   }
   if (mode & 0x10) {
     set_error("rope: long-rope needs ns_hip_rope_f32_longrope (factor array)");
@@ -394,14 +386,7 @@ int ns_hip_dup_f32(const float* dSrc, void* dDst, const long long ne[4], const l
       set_error("dup: negative extent");
       return -1;
     }
-  if (route_hook(stream)) {
-    RouteOp op;
-    memset(&op, 0, sizeof(op));
-    op.kind = RK_DUP, op.p[0] = dSrc, op.p[1] = dDst;
-    for (int i = 0; i < 4; i++) op.i[i] = ne[i], op.i[4 + i] = src_nb[i], op.i[8 + i] = dst_nb[i];
-    op.i[12] = dst_is_f16 ? 1 : 0;
-    return route_submit(op);
-  }
+  if (route_hook(stream)) return route_submit(route_op_dup(dSrc, dDst, ne, src_nb, dst_nb, dst_is_f16));
   return hip_ok(launch_dup(dSrc, dDst, ne, src_nb, dst_nb, dst_is_f16, (hipStream_t)stream), "dup launch") ? 0 : -1;
 }
 

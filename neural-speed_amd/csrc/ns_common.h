@@ -328,7 +328,7 @@ extern thread_local Affine g_affine;
 extern thread_local void* g_mha_out16;
 // ns_dispatch.cpp: may this weight's decode launch carry an RMS norm (ns_norm_link)?  (what link_ok() refuses, without setting an error)
 bool route_link_weight_ok(const ns_weight* w);
-// ns_route.cpp: one launch of the reference's device route as plain data (compared bytewise: zero-initialise before filling)
+// ns_route.cpp: one launch of the reference's device route as plain data (compared bytewise).  Which field holds what, a constructor and a view per kind: ns_route_op.h
 enum RouteKind : uint32_t { RK_GEMM = 1, RK_ADD, RK_MUL, RK_SILU, RK_RMSNORM, RK_ROPE, RK_ROPE_YARN, RK_DUP, RK_MHA };
 struct RouteOp {
   uint32_t kind, flags;

@@ -34,6 +34,7 @@
 #include "ns_common.h"
 #include "ns_launch.h"
 #include "ns_route.h"
+#include "ns_route_op.h"
 
 namespace ns {
 
@@ -394,16 +395,6 @@ struct Device {
   hipStream_t stream;
   int id;
 };
-
-// a strided binary node of the device route as plain data (ns_route.cpp)
-inline RouteOp binary_op(uint32_t kind, const float* a, const float* b, float* d, const long long ne0[4], const long long nb0[4], const long long ne1[4],
-                         const long long nb1[4], const long long nbd[4]) {
-  RouteOp op;
-  memset(&op, 0, sizeof(op));
-  op.kind = kind, op.p[0] = a, op.p[1] = b, op.p[2] = d;
-  for (int i = 0; i < 4; i++) op.i[i] = ne0[i], op.i[4 + i] = nb0[i], op.i[8 + i] = ne1[i], op.i[12 + i] = nb1[i], op.i[16 + i] = nbd[i];
-  return op;
-}
 
 // ---- the fp16 mirror of the reference's fp32 device kv cache (round 6; ns_route.h says why and how it stays coherent) ----
 namespace {
@@ -872,12 +863,7 @@ void bestla_device_f32f32_forward(float* activation, void* weiptr, float* output
   }
   int rc;
   if (ns::route_hook(queue)) {
-    ns::RouteOp op;
-    memset(&op, 0, sizeof(op));
-    op.kind = ns::RK_GEMM;
-    op.p[0] = activation, op.p[1] = s->w, op.p[2] = output;
-    op.i[0] = _m, op.i[1] = _n, op.i[2] = _k, op.i[3] = lda, op.i[4] = ldo;
-    rc = ns::route_submit(op);
+    rc = ns::route_submit(ns::route_op_gemm(activation, s->w, output, _m, _n, _k, lda, ldo));
   } else {
     rc = ns_hip_f32f32_forward(activation, s->w, output, _m, lda, ldo, NS_EPI_NONE, nullptr, 0, queue);
   }
@@ -953,12 +939,7 @@ int lazy_flush_impl() {
 }  // extern "C++"
 int ns_hip_lazy_flush(void) { return ns::g_lazy.kind ? ns::lazy_flush_impl() : 0; }
 int ns_hip_lazy_rms_norm(int rows, int cols, float eps, const float* dIn, float* dOut, void* stream) {
-  if (ns::route_hook(stream)) {
-    ns::RouteOp op;
-    memset(&op, 0, sizeof(op));
-    op.kind = ns::RK_RMSNORM, op.p[0] = dIn, op.p[1] = dOut, op.i[0] = rows, op.i[1] = cols, op.f[0] = eps;
-    return ns::route_submit(op);
-  }
+  if (ns::route_hook(stream)) return ns::route_submit(ns::route_op_rms_norm(dIn, dOut, rows, cols, eps));
   if (ns_hip_lazy_flush() != 0) return -1;
   if (!dIn || !dOut || rows < 1 || cols < 1) {
     ns::set_error("lazy rms_norm: invalid argument");
@@ -968,12 +949,7 @@ int ns_hip_lazy_rms_norm(int rows, int cols, float eps, const float* dIn, float*
   return ns::lazy_on() ? 0 : ns_hip_lazy_flush();
 }
 int ns_hip_lazy_silu(const float* dSrc, float* dDst, size_t n, void* stream) {
-  if (ns::route_hook(stream)) {
-    ns::RouteOp op;
-    memset(&op, 0, sizeof(op));
-    op.kind = ns::RK_SILU, op.p[0] = dSrc, op.p[1] = dDst, op.i[0] = (long long)n;
-    return ns::route_submit(op);
-  }
+  if (ns::route_hook(stream)) return ns::route_submit(ns::route_op_silu(dSrc, dDst, (long long)n));
   if (ns_hip_lazy_flush() != 0) return -1;
   if (n && (!dSrc || !dDst)) {
     ns::set_error("lazy silu: null argument");
@@ -988,7 +964,7 @@ int ns_hip_binary_nd_f32(int is_mul, const float* dA, const float* dB, float* dD
 /* the multiply node: fused with the recorded node when it consumes it, else the recorded node first and the plain kernel */
 int ns_hip_lazy_mul(const float* dA, const float* dB, float* dDst, const long long ne0[4], const long long nb0[4], const long long ne1[4],
                     const long long nb1[4], const long long nbd[4], void* stream) {
-  if (ns::route_hook(stream)) return ns::route_submit(ns::binary_op(ns::RK_MUL, dA, dB, dDst, ne0, nb0, ne1, nb1, nbd));
+  if (ns::route_hook(stream)) return ns::route_submit(ns::route_op_binary(ns::RK_MUL, dA, dB, dDst, ne0, nb0, ne1, nb1, nbd));
   const ns::LazyNode n = ns::g_lazy;
   auto packed = [](const long long ne[4], const long long nb[4]) {
     return nb[0] == 4 && nb[1] == 4 * ne[0] && nb[2] == nb[1] * ne[1] && nb[3] == nb[2] * ne[2];
@@ -1023,7 +999,7 @@ int ns_hip_lazy_mul(const float* dA, const float* dB, float* dDst, const long lo
 /* ---- kernels behind the tensor-level functions of glue/ne_bestla_hip_device.c ---- */
 int ns_hip_binary_nd_f32(int is_mul, const float* dA, const float* dB, float* dDst, const long long ne0[4], const long long nb0[4],
                          const long long ne1[4], const long long nb1[4], const long long nbd[4], void* stream) {
-  if (ns::route_hook(stream)) return ns::route_submit(ns::binary_op(is_mul ? ns::RK_MUL : ns::RK_ADD, dA, dB, dDst, ne0, nb0, ne1, nb1, nbd));
+  if (ns::route_hook(stream)) return ns::route_submit(ns::route_op_binary(is_mul ? ns::RK_MUL : ns::RK_ADD, dA, dB, dDst, ne0, nb0, ne1, nb1, nbd));
   if (ns_hip_lazy_flush() != 0) return -1;
   if (!dA || !dB || !dDst) {
     ns::set_error("binary_nd: null argument");
@@ -1077,14 +1053,7 @@ int ns_hip_mha_f32_device_layout(const float* dQ, const float* dK, const float* 
     ns::set_error("mha_f32: invalid argument");
     return -1;
   }
-  if (ns::route_hook(stream)) {
-    ns::RouteOp op;
-    memset(&op, 0, sizeof(op));
-    op.kind = ns::RK_MHA, op.p[0] = dQ, op.p[1] = dK, op.p[2] = dV, op.p[3] = dO;
-    op.i[0] = batch, op.i[1] = seq, op.i[2] = seq_all, op.i[3] = heads, op.i[4] = heads_kv, op.i[5] = head_size, op.i[6] = n_ctx, op.i[7] = masked;
-    op.f[0] = scale;
-    return ns::route_submit(op);
-  }
+  if (ns::route_hook(stream)) return ns::route_submit(ns::route_op_mha(dQ, dK, dV, dO, batch, seq, seq_all, heads, heads_kv, head_size, n_ctx, scale, masked));
   if (ns_hip_lazy_flush() != 0) return -1;
   ns::g_mha_out16_written = false;
   const ns::Affine aff = ns::g_affine;

@@ -1,4 +1,4 @@
-// ns_route.h — what the device route's pieces share (ns_route.cpp, ns_device.hip, the operator kernels of ns_quant.hip): the fp16
+// ns_route.h — what the device route's pieces share (ns_route*.cpp, ns_device.hip, the operator kernels of ns_quant.hip): the fp16
 // mirror of the reference's fp32 device kv cache (round 6) and the per-token bookkeeping around it.
 //
 // Why a mirror: a reference tree built with its device switch keeps its kv cache in fp32 on the device — K [batch][heads_kv][n_ctx][head_size],
@@ -43,7 +43,7 @@ struct KvMirrorPair {
 };
 extern thread_local KvMirrorPair g_kvm;  // set around a captured cache-write launch (like g_affine), zero otherwise
 
-bool route_executing();  // ns_route.cpp: the calling thread is inside a launch the route issues (its cache protocol is known)
+bool route_executing();  // ns_route_exec.cpp (ExecGuard): the calling thread is inside a launch the route issues (its cache protocol is known)
 
 // ---- ns_device.hip ----
 bool kv16_enabled();          // NS_DEVICE_KV / ns_hip_set_tuning("device_kv_f16")
