@@ -242,6 +242,8 @@ int ns_hip_get_compute_mode(void);
  *                     in the environment, else 8; negative = never)
  *   "moe_grouped_rows" ns_hip_mul_mat_id: token rows from which a call outside a capture groups its rows by expert on the host, one tiled
  *                     GEMM per expert (0 = default: NS_MOE_GROUPED_ROWS in the environment, else 32; negative = never)
+ *   "moe_ffn_fused"   ns_hip_moe_ffn_silu: 0 = every call takes the composition (three ns_hip_mul_mat_id calls per selection + the weighted
+ *                     sum), 1 = the fused launches inside their envelope, -1 = back to the default (1)
  * Returns 0, or -1 for an unknown key. */
 int ns_hip_set_tuning(const char* key, int value);
 /* Loads the code objects of the hot kernels (tiled GEMM, decode GEMV, attention, the operators between them) for the current device now instead of at the
@@ -640,7 +642,7 @@ int ns_hip_attn_set_head_partition(int global_head_num, int head_offset);
  * the reference asserts — produces a zero product for that row: dC[t] = epi(0, dD[t]) on every path (NS_EPI_ADD leaves dD[t],
  * NS_EPI_ADD_GELU gelu(dD[t]), the others zero).  fp16-activation numerics like every default forward.
  * The `ffn_id_*` nodes (ne_layers.c:8053-8170) are three such calls (gate with NS_EPI_SILU, up with NS_EPI_MUL and
- * dD = gate output, down).
+ * dD = gate output, down); ns_hip_moe_ffn_silu below is the whole block in 1 + n_used launches.
  * A call is served by row count: up to "moe_gemv_rows" rows one decode-kernel launch per row, from "moe_grouped_rows" rows (outside a
  * stream capture) the rows grouped by expert and one tiled GEMM per expert, otherwise — and wherever those two refuse — a per-row
  * loop kernel (docs/kernels/other.md).  ns_hip_moe_stats (process-wide sums): calls served by [0] the grouped path, [1] the decode
@@ -652,6 +654,44 @@ void ns_hip_expert_group_free(ns_expert_group* g);
 int ns_hip_mul_mat_id(const float* dA, const int32_t* dIds, int ids_stride, int id, const ns_expert_group* g, float* dC,
                       int m, int lda, int ldc, int epilogue, const float* dD, int ldd, void* stream);
 void ns_hip_moe_stats(uint64_t out[4]);
+
+/* The MoE decode block around that operator (docs/kernels/other.md, "MoE decode block").
+ *
+ * ns_hip_moe_route — the router's tail in one launch: device twin of soft_max -> top_k -> get_rows -> sum_rows -> repeat -> div
+ * (models/llama/llama.cpp:631-638).  Per row t of dLogits [m][ld_logits] (n_expert columns used):
+ *     p = soft_max(logits[t])                       optional output dProbs [m][ld_logits] (NULL: not written)
+ *     dIds[t * ids_stride + i]     = expert with the i-th largest p           i = 0 .. n_used-1
+ *     dWeights[t * w_stride + i]   = p[that expert] / sum_i p[selected i]
+ * with the reference's arithmetic operation by operation (ne_compute_forward_soft_max_f32, ne_layers.c:8887-8954): x - max rounded to fp16,
+ * looked up in the fp16 exponential table (built on the host with the host's expf like the reference's table_exp_f16, uploaded once:
+ * at the first expert group's creation, in ns_hip_warm_up, or by the first call outside a stream capture - a call inside a capture before
+ * any of those is refused), summed in double, float(1 / sum) multiplied in fp32; the selected values summed in double in selection order,
+ * stored as float and divided in fp32.  -inf logits get probability 0.  Selection order is descending probability; among EQUAL
+ * probabilities the lower expert index comes first (the reference's std::sort leaves that order unspecified).  Rows with a NaN or with
+ * all logits -inf are outside the contract: their ids are still distinct and in range.
+ * 1 <= n_used <= 8, n_used <= n_expert <= 64, m >= 1, every stride at least its row's length; anything else: -1, nothing written.
+ * Asynchronous on `stream`, capturable.
+ *
+ * ns_hip_moe_ffn_silu — the expert feed-forward block of a token batch: device twin of n_used x { ne_mul_id_ffn_silu ; mul(weights) ;
+ * add } (llama.cpp:641-679, ne_layers.c:8053-8075):
+ *     dOut[t] = sum_{i < n_used} w[t][i] * down_e( silu(gate_e(dA[t])) * up_e(dA[t]) ),    e = dIds[t * ids_stride + i],
+ *     w[t][i] = dWeights[t * w_stride + i]  (dWeights NULL: 1)
+ * summed in selection order; an id outside the groups contributes zero.  gate and up are groups of [ff x d] experts, down of [d_out x ff]
+ * ones, all with the same number of experts.  Up to "moe_gemv_rows" rows, with experts other than fp8 and gate / up groups of one format,
+ * the call is 1 + n_used launches of the decode kernel whatever m is: one fused gate / up launch over all (row, selection) pairs with
+ * silu(gate) * up formed in registers, then one down launch per selection over all rows, which multiplies by w and adds into dOut (every
+ * element read and written by the same lane, selections in order: deterministic, no atomics).  Every other call - and whatever those
+ * launches refuse - is the composition: three ns_hip_mul_mat_id calls per selection and a weighted sum; the entry serves every shape
+ * ns_hip_mul_mat_id serves.  The intermediate results live in per-stream scratch.  Asynchronous on `stream`, capturable; a replayed
+ * graph follows the ids and weights in device memory.  ns_hip_set_tuning("moe_ffn_fused", 0) keeps every call on the composition.
+ * ns_hip_moe_ffn_stats (process-wide sums): [0] calls served by the fused launches, [1] calls served by the composition, [2] launches
+ * issued for the calls of [0], [3] reserved (0). */
+int ns_hip_moe_route(const float* dLogits, int ld_logits, int m, int n_expert, int n_used, int32_t* dIds, int ids_stride,
+                     float* dWeights, int w_stride, float* dProbs, void* stream);
+int ns_hip_moe_ffn_silu(const float* dA, int lda, int m, const int32_t* dIds, int ids_stride, const float* dWeights, int w_stride,
+                        int n_used, const ns_expert_group* gate, const ns_expert_group* up, const ns_expert_group* down,
+                        float* dOut, int ldo, void* stream);
+void ns_hip_moe_ffn_stats(uint64_t out[4]);
 
 /* ----------------------------------------------------------------------------------------------
  * Part 5 — tensor-parallel all-reduce over peer-mapped HBM.  The decode-sized fast path of

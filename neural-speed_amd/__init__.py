@@ -174,6 +174,10 @@ def lib():
         L.ns_hip_mul_mat_id.argtypes = [vp, vp, i, i, vp, vp, i, i, i, i, vp, i, vp]
         L.ns_hip_moe_stats.restype = None
         L.ns_hip_moe_stats.argtypes = [vp]
+        L.ns_hip_moe_route.argtypes = [vp, i, i, i, i, vp, i, vp, i, vp, vp]
+        L.ns_hip_moe_ffn_silu.argtypes = [vp, i, i, vp, i, vp, i, i, vp, vp, vp, vp, i, vp]
+        L.ns_hip_moe_ffn_stats.restype = None
+        L.ns_hip_moe_ffn_stats.argtypes = [vp]
         L.ns_hip_p2p_create.restype = vp
         L.ns_hip_p2p_create.argtypes = [i, i, sz, vp]
         L.ns_hip_p2p_connect.argtypes = [vp, vp]

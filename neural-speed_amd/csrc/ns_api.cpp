@@ -103,6 +103,7 @@ const TuningKey kTuning[] = {
     // row thresholds of ns_hip_mul_mat_id's paths; 0 = default, < 0 = off
     {"moe_gemv_rows", [](int v) { set_moe_tuning(0, v); }},
     {"moe_grouped_rows", [](int v) { set_moe_tuning(1, v); }},
+    {"moe_ffn_fused", set_moe_ffn_fused},  // ns_hip_moe_ffn_silu: 0 = always the composition, 1 / -1 = the fused launches inside their envelope
     {"g3_min_m", set_gemm3_min_m},
     {"i8_tile", set_i8_tile},
     {"i8_mfma", set_i8_mfma_gen},
@@ -187,6 +188,7 @@ int ns_hip_warm_up(void) {
       touch_gemv_module();
       touch_attn_module();
       touch_quant_module();
+      (void)moe_exp_table();  // the router's exponential table (ns_hip_moe_route): uploaded here, outside any capture
       ns_hip_reset_error();
     });
   return 0;

@@ -179,6 +179,15 @@ struct MoeRoute {
   const void* table;   // device: rows {codes, scales, zps} of the group's experts (ns_moe.hip)
   const int32_t* id;   // device: &ids[token][id]
   int n_as;
+  // one launch over several (token row, selection) pairs, pair y = row * nsel + sel along grid.y (ns_hip_moe_ffn_silu): the pair's id is
+  // id[row * ids_stride + sel], its activation row a + row * a_stride, its output (epilogue operand) row seg[0].c + y * c_stride (d + y * d_stride)
+  // — strides in floats — and w[row * w_stride + sel] (w == nullptr: 1) is multiplied into its product in front of the epilogue.
+  // SmallMArgs::dual: seg[0] / seg[1] describe the gate / up groups (equal shape and format), table1 is the up group's table
+  const void* table1 = nullptr;
+  int pairs = 1, nsel = 1, ids_stride = 0;
+  const float* w = nullptr;
+  int w_stride = 0;
+  long long a_stride = 0, c_stride = 0, d_stride = 0;
 };
 // replayed device route (ns_route.cpp XK_QKV_ROPE; gemv_kernel only, one row): the fused QKV launch's RoPE epilogue (ns_qkv_rope) also stores k (rotated)
 // and v into the reference's fp32 cache cells, and its position — RoPE angle table aside, which a captured launch of its own fills — follows the graph's counter
@@ -246,6 +255,11 @@ void kv_mirrors_clear();  // ns_kvcache.hip: drops the device mirrors of library
 void set_i8_tile(int tile);     // ns_i8ref.hip: workgroup tile of i8mfma2_kernel (0 = by size)
 void set_i8_mfma_gen(int gen);  // ns_i8ref.hip: 2 = i8mfma2_kernel for nibble containers (default), 1 = i8mfma_kernel everywhere
 void set_moe_tuning(int what, int value);  // ns_moe.hip: row threshold of what = 0 the decode kernel (m <= value), 1 the grouped path (m >= value); 0 = default, < 0 = off
+void set_moe_ffn_fused(int on);  // ns_moe.hip: ns_hip_moe_ffn_silu takes 1 the fused launches inside their envelope, 0 always the composition, -1 the default
+// ns_moe.hip: the router's fp16 exponential table (ns_hip_moe_route) on the current device, built on the host and uploaded at the first call
+// (an expert group's creation, ns_hip_warm_up, a route call outside a stream capture); nullptr + error string when it cannot be made.
+// build = false: the table if it exists already, else nullptr (a caller inside a capture: the upload is synchronous)
+const uint16_t* moe_exp_table(bool build = true);
 void set_gemm3_min_m(int m);  // ns_gemm.hip: rows from which gemm3_kernel is used (0 = default)
 void set_gemm3_wide(int on);  // ns_gemm.hip: 1 the cross-wave output epilogue of gemm3_kernel's 1 x 4 wave tiles, 0 (default) the per-wave one, -1 = environment / default
 void set_gemm3_f8(int on);  // ns_gemm.hip: 1 (default) fp8 weights take gemm3_kernel at prompt size, 0 they stay on the first-generation kernel, -1 = NS_G3_F8 / default

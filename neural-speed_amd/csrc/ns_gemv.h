@@ -90,6 +90,16 @@ struct GemvParams {
   const MoeExpertRow* moe_table;
   const int32_t* moe_id;
   int moe_n;
+  // ... and its (row, selection) pairs along grid.y (ns_hip_moe_ffn_silu; a ns_hip_mul_mat_id launch is the single pair 0): pair y is
+  // row = (y * moe_sel_mul) >> 16 (= y / moe_nsel, exact while y * moe_nsel < 65536), sel = y - row * moe_nsel; its id is
+  // moe_id[row * moe_ids_stride + sel], its activations a + row * moe_a_stride, its output (and D operand) row y * moe_c_stride
+  // (moe_d_stride) floats behind mat[0].c (d); moe_w (nullptr: 1) holds a factor per pair, [row * moe_w_stride + sel], multiplied into the
+  // product in front of the epilogue.  GV_DUAL: the second matrix is moe_table1[id].codes (the up group; same shape and format)
+  const MoeExpertRow* moe_table1;
+  const float* moe_w;
+  uint32_t moe_sel_mul, moe_nsel;
+  int moe_ids_stride, moe_w_stride;
+  uint32_t moe_a_stride, moe_c_stride, moe_d_stride;
   // native bit-plane records (PL = true: ns_weight::native): the format's bit width and the lanes of a record request
   // (record bytes / 16; the record's planes are contiguous, so a k-step is still ONE request)
   uint32_t pl_bits, pl_lanes;
@@ -131,12 +141,13 @@ bool gemv_rows1();  // ns_gemv_host.cpp: the "gv_rows1" tuning value — launche
 
 // One object per slice X(weight kind, scales per record), each with its own device code object.  Per slice:
 //   launch_gemv_<KIND>_<SPS>: launches the instantiation for (scale type, sym / asym, mode bits) on a prepared GemvParams;
-//     hipErrorNotSupported: no such instantiation (the caller falls back to smallm_kernel)
+//     hipErrorNotSupported: no such instantiation (the caller falls back to smallm_kernel); grid_y: the (row, selection) pairs of an
+//     expert-indexed launch
 //   touch_gemv_<KIND>_<SPS>: makes the runtime load the slice's code object (touch_gemv_module, ns_common.h)
 #define NS_GEMV_SLICES(X) X(INT4, 4) X(INT4, 2) X(INT4, 1) X(INT8, 2) X(INT8, 1) X(F4, 4) X(F4, 2) X(F4, 1) X(F8, 2) X(F8, 1)
 #define NS_GEMV_DECLARE(KIND, SPS)                                                                                      \
   hipError_t launch_gemv_##KIND##_##SPS(const GemvParams& p, uint32_t scale_dt, bool asym, int mode, int grid, int nw, \
-                                        size_t lds, hipStream_t st);                                                   \
+                                        size_t lds, hipStream_t st, int grid_y = 1);                                   \
   void touch_gemv_##KIND##_##SPS();
 NS_GEMV_SLICES(NS_GEMV_DECLARE)
 #undef NS_GEMV_DECLARE

@@ -107,7 +107,9 @@ __device__ __forceinline__ void neox_rotate(float x0, float x1, float c, float s
 // XV = 4 (MOE): A32 + the weight picked on the DEVICE: ne_compute_forward_mul_mat_id_q_f32_bestla (ne_layers.c:7783-7916) reads
 // ids[token][id] on the host and calls bestla_f32f32_forward per (token, expert); here the id stays where the router's top-k left
 // it — one scalar load of the id, one of the expert's base pointer, in front of the first weight request (two dependent round
-// trips, ~1 us, instead of a host synchronisation) — and the token's row streams the expert at this kernel's rate.
+// trips, ~1 us, instead of a host synchronisation) — and the token's row streams the expert at this kernel's rate.  These launches alone
+// read blockIdx.y: a (token row, selection) pair with its own id, activation row, output row and factor (GemvParams::moe_*), each
+// workgroup still staging ONE row; with GV_DUAL the gate and up matrices of the pair's expert come from two tables (ns_hip_moe_ffn_silu).
 // XV = 3 (I8S): the REFERENCE'S int8-compute numerics (its default for Q4_0: gemv_4bit_u8s8_fp32, kernel_ref.h:2371-2429) on the
 // same streaming skeleton: A arrives as the u8 codes / scales / zero points of quantize_fp_u8_colblock (aquant_u8_kernel,
 // bit-exact), a lane (column nn, k-slot g) takes exact integer dots of its eight codes per 32-deep slice with v_dot4 on the
@@ -180,7 +182,38 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
   uint32_t so[NQ], zo[NQ];
   int sg = 0;       // matrix of the fused launch the tile belongs to (QKV)
   uint32_t tl = T;  // tile inside that matrix
-  if constexpr (DUAL) {
+  uint32_t moe_y = 0, moe_row = 0;  // MOE: this workgroup's (row, selection) pair and its token row
+  float moe_wsc = 1.f;              // MOE: the pair's factor (routing weight)
+  if constexpr (MOE) {
+    moe_y = blockIdx.y;
+    moe_row = (moe_y * p.moe_sel_mul) >> 16;
+    const uint32_t sel = moe_y - moe_row * p.moe_nsel;
+    const int e = p.moe_id[(long long)moe_row * p.moe_ids_stride + sel];  // wave-uniform: scalar loads
+    if (p.moe_w) moe_wsc = p.moe_w[(long long)moe_row * p.moe_w_stride + sel];
+    if (e < 0 || e >= p.moe_n) {  // an out-of-range id: a zero PRODUCT for the row (the reference would assert), through the epilogue of section 6
+      const KArgs cz = late_args();
+      const int colz = int(T) * 16 + nn;
+      if (w == 0 && g == 0 && colz < cz->mat[0].n) {
+        float v = 0.f;
+        if constexpr (!DUAL) {  // (fused gate / up: silu(0) * up = 0)
+          const float dv = cz->d ? cz->d[size_t(moe_y) * cz->moe_d_stride + colz] : 0.f;
+          v = epi_apply(v, dv, cz->epilogue);
+        }
+        float* cr = cz->mat[0].c + size_t(moe_y) * cz->moe_c_stride;
+        cr[colz] = v;
+        if (cz->mat[0].c16) cz->mat[0].c16[colz] = (_Float16)v;
+      }
+      return;
+    }
+    rw[0] = make_rsrc(p.moe_table[e].codes, 0x80000000u);
+    so[0] = p.s_off0;
+    zo[0] = p.z_off0;
+    if constexpr (DUAL) {  // gate and up of the SAME expert, out of the two groups' tables
+      rw[1] = make_rsrc(p.moe_table1[e].codes, 0x80000000u);
+      so[1] = p.s_off1;
+      zo[1] = p.z_off1;
+    }
+  } else if constexpr (DUAL) {
     rw[0] = make_rsrc(p.wbase0, 0x80000000u);
     rw[1] = make_rsrc(p.wbase1, 0x80000000u);
     so[0] = p.s_off0, so[1] = p.s_off1;
@@ -199,23 +232,6 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
       tl += (tl / p.pair_tiles) * p.pair_tiles;
       rw[1] = rw[0], so[1] = so[0], zo[1] = zo[0];
     }
-  } else if constexpr (MOE) {
-    const int e = *p.moe_id;  // wave-uniform: scalar loads
-    if (e < 0 || e >= p.moe_n) {  // an out-of-range id: a zero PRODUCT for the row (the reference would assert), through the epilogue of section 6
-      const KArgs cz = late_args();
-      const int colz = int(T) * 16 + nn;
-      if (w == 0 && g == 0 && colz < cz->mat[0].n) {
-        float v = 0.f;
-        const float dv = cz->d ? cz->d[colz] : 0.f;
-        v = epi_apply(v, dv, cz->epilogue);
-        cz->mat[0].c[colz] = v;
-        if (cz->mat[0].c16) cz->mat[0].c16[colz] = (_Float16)v;
-      }
-      return;
-    }
-    rw[0] = make_rsrc(p.moe_table[e].codes, 0x80000000u);
-    so[0] = p.s_off0;
-    zo[0] = p.z_off0;
   } else {
     rw[0] = make_rsrc(p.wbase0, 0x80000000u);
     so[0] = p.s_off0;
@@ -280,7 +296,8 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
   if constexpr (A32) {
     // fp32 rows: 1 KiB pieces (256 columns) by wave (r * pieces + c) % NW again, at most kGvA32Regs per wave (host)
     // the descriptor make_rsrc() builds, as four words for the asm operand: base, stride 0, bytes, flags
-    const uint64_t abase = reinterpret_cast<uint64_t>(p.a);
+    uint64_t abase = reinterpret_cast<uint64_t>(p.a);
+    if constexpr (MOE) abase += uint64_t(moe_row) * p.moe_a_stride * 4u;  // the pair's token row (the workgroup stages this one row)
     const uint4v ra_words = {uint32_t(abase), uint32_t(abase >> 32) & 0xffffu,
                              uint32_t(rows - 1) * uint32_t(p.lda) * 4u + uint32_t(p.k) * 4u, 0x00020000u};
     const uint32_t row_bytes = ks * uint32_t(KSTEP) * 4u;
@@ -822,6 +839,10 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
   _Float16* c16 = mp->c16;
   const int ldc = cold->ldc, ldd = cold->ldd, epi = cold->epilogue;
   const float* dptr = cold->d;
+  if constexpr (MOE) {  // the pair's output row (and the row of its epilogue operand)
+    cbase += size_t(moe_y) * cold->moe_c_stride;
+    if (dptr) dptr += size_t(moe_y) * cold->moe_d_stride;
+  }
   float* c2 = cold->c2;
   float in_eps = 0.f, in_inv = 0.f;
   const float* ogamma = nullptr;
@@ -969,6 +990,7 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
           v = sum[1][rr] * rscale[rr] * t1;
         } else {
           const float dv = dvp[rr];
+          if constexpr (MOE) v *= moe_wsc;  // the routing weight: out (+)= w * (h . W_down)
           v = epi_apply(v, dv, epi);
         }
         cbase[size_t(row) * ldc + col] = v;
@@ -1036,9 +1058,9 @@ constexpr bool gemv_has_rows1(int kind, int mode, int xv) {
 }
 
 template <int KIND, int SPS, int SK, bool ASYM>
-static hipError_t launch_gemv_k(const GemvParams& p, int mode, int grid, int nw, size_t lds, hipStream_t st) {
+static hipError_t launch_gemv_k(const GemvParams& p, int mode, int grid, int nw, size_t lds, hipStream_t st, int grid_y) {
   if (mode & kGvModePlanes) return launch_gemv_planes<KIND, SPS, SK, ASYM>(p, mode & ~kGvModePlanes, grid, nw, lds, st);
-  const dim3 g(grid), b(nw * 64);
+  const dim3 g(grid, grid_y), b(nw * 64);  // (grid_y > 1: expert-indexed launches only, launch_gemv)
   const bool r1 = p.m == 1 && gemv_rows1();
   const bool ext = p.in_ssq || p.out_gamma || p.out_ssq || p.rope.on;
   const bool a32 = (mode & kGvModeA32) != 0;  // never together with ext (launch_gemv)
@@ -1047,7 +1069,7 @@ static hipError_t launch_gemv_k(const GemvParams& p, int mode, int grid, int nw,
   mode &= ~(kGvModeA32 | kGvModeI8 | kGvModeMoe);
   if (moe) {
     if constexpr (KIND == WK_F8) return hipErrorNotSupported;
-    if (mode != GV_PLAIN) return hipErrorNotSupported;
+    if (mode != GV_PLAIN && mode != GV_DUAL) return hipErrorNotSupported;
   }
   if constexpr (KIND != WK_INT4 && KIND != WK_INT8)
     if (i8s) return hipErrorNotSupported;
@@ -1058,7 +1080,7 @@ static hipError_t launch_gemv_k(const GemvParams& p, int mode, int grid, int nw,
   }
 #define NS_GV_LAUNCH_MOE(MODEV)                                                                                  \
   {                                                                                                             \
-    if constexpr (KIND != WK_F8 && MODEV == GV_PLAIN) NS_GV_LAUNCH_E(GV_PLAIN, 4)                               \
+    if constexpr (KIND != WK_F8 && (MODEV == GV_PLAIN || MODEV == GV_DUAL)) NS_GV_LAUNCH_E(MODEV, 4)            \
   }
 #define NS_GV_LAUNCH_I8Q(MODEV)                                                                                  \
   {                                                                                                             \
@@ -1098,9 +1120,9 @@ static hipError_t launch_gemv_k(const GemvParams& p, int mode, int grid, int nw,
 constexpr int kGvSliceKind = NS_GV_PASTE(WK_, NS_GEMV_KIND);
 
 hipError_t NS_GV_SLICE_FN(launch_gemv_)(const GemvParams& p, uint32_t scale_dt, bool asym, int mode, int grid, int nw, size_t lds,
-                                        hipStream_t st) {
+                                        hipStream_t st, int grid_y) {
   return with_scales<kGvSliceKind>(scale_dt, asym, [&](auto sk_c, auto asym_c) {
-    return launch_gemv_k<kGvSliceKind, NS_GEMV_SPS, sk_c, asym_c>(p, mode, grid, nw, lds, st);
+    return launch_gemv_k<kGvSliceKind, NS_GEMV_SPS, sk_c, asym_c>(p, mode, grid, nw, lds, st, grid_y);
   });
 }
 void NS_GV_SLICE_FN(touch_gemv_)() {  // (an instantiation every slice has)

@@ -164,7 +164,20 @@ hipError_t launch_gemv(const SmallMArgs& a, hipStream_t st) {
   // fp32-only callers: converted while staging (XV = 2); not together with a carried norm / fused RoPE, whose producers
   // always leave a shadow
   const bool moe = a.moe != nullptr;
-  if (moe && (a.m != 1 || nmat != 1 || a.dual || a.link || a.rope || i8s || a.a16 || !a.moe->table || !a.moe->id)) return hipErrorNotSupported;
+  if (moe && (a.m != 1 || nmat != (a.dual ? 2 : 1) || a.link || a.rope || i8s || a.a16 || !a.moe->table || !a.moe->id)) return hipErrorNotSupported;
+  if (moe) {  // its (row, selection) pairs along grid.y; fused gate / up: the second table, the kernel's one set of strides for both matrices
+    const MoeRoute& r = *a.moe;
+    if (r.pairs < 1 || r.pairs > 65535 || r.nsel < 1 || int64_t(r.pairs) * r.nsel >= 65536 || (r.a_stride & 3) || r.a_stride < 0 || r.c_stride < 0 ||
+        r.d_stride < 0 || std::max({r.a_stride, r.c_stride, r.d_stride}) >= (1ll << 32))
+      return hipErrorNotSupported;
+    if (a.dual) {
+      const ns_weight* w1 = a.seg[1].w;
+      if (!r.table1 || a.c2 || w1->n != w0->n || w1->k != w0->k || w1->kind != w0->kind || w1->qtype != w0->qtype || w1->blocksize != w0->blocksize ||
+          w1->scale_dt != w0->scale_dt || w1->asym != w0->asym || w1->qstride != w0->qstride || w1->sstride != w0->sstride ||
+          w1->zstride != w0->zstride || w1->sps != w0->sps || w1->ksteps != w0->ksteps || w1->srows != w0->srows)
+        return hipErrorNotSupported;
+    }
+  }
   const bool a32 = i8q || (!i8s && !a16 && a.a != nullptr && !a.link && !a.rope && (a.lda & 3) == 0 && (w0->k & 3) == 0 &&
                    (reinterpret_cast<uintptr_t>(a.a) & 15) == 0);
   if (moe && !a32) return hipErrorNotSupported;
@@ -271,13 +284,20 @@ hipError_t launch_gemv(const SmallMArgs& a, hipStream_t st) {
     p.moe_table = static_cast<const MoeExpertRow*>(a.moe->table);
     p.moe_id = a.moe->id;
     p.moe_n = a.moe->n_as;
+    p.moe_table1 = static_cast<const MoeExpertRow*>(a.moe->table1);
+    p.moe_w = a.moe->w;
+    p.moe_nsel = uint32_t(a.moe->nsel);
+    p.moe_sel_mul = (65536u + p.moe_nsel - 1u) / p.moe_nsel;
+    p.moe_ids_stride = a.moe->ids_stride, p.moe_w_stride = a.moe->w_stride;
+    p.moe_a_stride = uint32_t(a.moe->a_stride), p.moe_c_stride = uint32_t(a.moe->c_stride), p.moe_d_stride = uint32_t(a.moe->d_stride);
   }
   p.pl_bits = planes ? uint32_t(w0->pl_bits) : 0u;
   p.pl_lanes = planes ? w0->code_rec / 16u : 64u;
   const int mode_x = mode | (a32 && !moe ? kGvModeA32 : 0) | (i8s ? kGvModeI8 : 0) | (moe ? kGvModeMoe : 0) | (planes ? kGvModePlanes : 0);
 
   // the weight's slice (a slice the build leaves out is an undefined symbol when the library is linked)
-#define NS_SLICE(KIND, SPS) launch_gemv_##KIND##_##SPS(p, w0->scale_dt, w0->asym, mode_x, grid, nw, lds, st)
+  const int grid_y = moe ? a.moe->pairs : 1;
+#define NS_SLICE(KIND, SPS) launch_gemv_##KIND##_##SPS(p, w0->scale_dt, w0->asym, mode_x, grid, nw, lds, st, grid_y)
   switch (w0->kind) {
     case WK_INT4: return w0->sps == 4 ? NS_SLICE(INT4, 4) : w0->sps == 2 ? NS_SLICE(INT4, 2) : NS_SLICE(INT4, 1);
     case WK_INT8: return w0->sps == 2 ? NS_SLICE(INT8, 2) : NS_SLICE(INT8, 1);

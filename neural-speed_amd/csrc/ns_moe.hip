@@ -14,15 +14,24 @@
 // scale for the 4-bit float types), fp32 accumulation — evaluated with VALU FMAs: a token row is an M = 1 product, the
 // matrix cores have nothing to add and the kernel is bound by the expert's weight stream.  First version: plain
 // streaming loop with four records in flight per wave, not tuned like smallm_kernel.
+//
+// Around that operator, the rest of a Mixtral-style layer's MoE block (docs/kernels/other.md, "MoE decode block"): ns_hip_moe_route, the
+// router's soft_max -> top_k -> weights tail in one launch (moe_route_kernel), and ns_hip_moe_ffn_silu, the expert feed-forward block of all
+// rows and selections in 1 + n_used launches of the decode kernel (ns_gemv.hip, XV = 4) or, outside their envelope, as the composition of
+// ns_hip_mul_mat_id calls with moe_weighted_add_kernel.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/ns_bestla.h"
+#include "ns_api_int.h"
 #include "ns_common.h"
 #include "ns_dev.h"
 
@@ -220,6 +229,77 @@ __global__ __launch_bounds__(kMoeThreads) void moe_gemv_kernel(const MoeParams p
   }
 }
 
+// ---- the router's tail (ns_hip_moe_route): soft_max -> top_k -> get_rows -> sum_rows -> div of the reference graph in one launch ----
+// One wave per token row, lane e holds expert e (n_expert <= 64).  The arithmetic is the reference's operation by operation
+// (ne_compute_forward_soft_max_f32, ne_layers.c:8887-8954): fp16(x - max) looked up in table_exp_f16, the values summed in double (at most
+// 64 fp16 values: exact, so the butterfly's order does not matter), float(1.0 / sum) multiplied in fp32; the selected probabilities summed in
+// double in selection order, the sum stored as float (sum_rows) and divided in fp32 (ne_vec_div_f32).  Selection: n_used rounds of a wave-wide
+// arg-max on (probability, lower index first) — the reference's std::sort leaves ties unspecified, here the lower expert index wins.
+constexpr int kRouteWaves = 4;
+__global__ __launch_bounds__(kRouteWaves * 64) void moe_route_kernel(const float* __restrict__ logits, int ld, int m, int n_expert, int n_used,
+                                                                     const uint16_t* __restrict__ exp_table, int32_t* __restrict__ ids, int ids_stride,
+                                                                     float* __restrict__ weights, int w_stride, float* __restrict__ probs) {
+  const int row = blockIdx.x * kRouteWaves + int(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= m) return;  // (wave-uniform)
+  const bool on = lane < n_expert;
+  const float ninf = -__builtin_inff();
+  const float x = on ? logits[size_t(row) * ld + lane] : ninf;
+  float mx = x;  // ne_vec_max_f32
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float y = __shfl_xor(mx, o, 64);
+    mx = y > mx ? y : mx;
+  }
+  float val = 0.f;
+  if (on && x != ninf) {
+    const _Float16 h = (_Float16)__fsub_rn(x, mx);  // NE_FP32_TO_FP16: round to nearest even
+    val = f16_bits_to_f32(exp_table[__builtin_bit_cast(unsigned short, h)]);
+  }
+  double sum = double(val);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+  if (mx == ninf) sum = double(n_expert);  // (all logits -inf: the reference's start value; every probability is 0)
+  const float inv = float(1.0 / sum);
+  const float pr = __fmul_rn(val, inv);  // ne_vec_scale_f32
+  if (probs && on) probs[size_t(row) * ld + lane] = pr;
+  // top-k: key = (probability bits, 63 - lane) — non-negative floats order like their bits; a NaN (outside the contract) counts as 0,
+  // lanes beyond n_expert and lanes already taken as -1, so the ids are distinct and in range whatever the row holds
+  long long key = on ? ((long long)(pr != pr ? 0u : (__builtin_bit_cast(uint32_t, pr) & 0x7fffffffu)) << 32) | (long long)(63 - lane) : -1ll;
+  int my_id = 0;
+  float my_p = 0.f;
+  for (int r = 0; r < n_used; r++) {
+    long long best = key;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const long long y = __shfl_xor(best, o, 64);
+      best = y > best ? y : best;
+    }
+    const int win = 63 - int(best & 63);
+    const float pw = __shfl(pr, win, 64);
+    if (lane == r) my_id = win, my_p = pw;
+    if (lane == win) key = -1ll;
+  }
+  double wsum = 0.0;  // sum_rows: double accumulator, in selection order
+  for (int r = 0; r < n_used; r++) wsum += double(__shfl(my_p, r, 64));
+  const float wsf = float(wsum);
+  if (lane < n_used) {
+    ids[size_t(row) * ids_stride + lane] = my_id;
+    weights[size_t(row) * w_stride + lane] = __fdiv_rn(my_p, wsf);
+  }
+}
+
+// the composition's tail (ns_hip_moe_ffn_silu outside the fused launches): out = (first ? 0 : out) + w[t][sel] * x — mul(weights) and add of
+// llama.cpp:669-679
+__global__ void moe_weighted_add_kernel(float* __restrict__ out, int ldo, const float* __restrict__ x, int ldx, const float* __restrict__ w,
+                                        int w_stride, int m, int n, int first) {
+  const size_t gid = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (gid >= size_t(m) * n) return;
+  const int t = int(gid / n), col = int(gid % n);
+  const float v = (w ? w[size_t(t) * w_stride] : 1.f) * x[size_t(t) * ldx + col];
+  float* o = out + size_t(t) * ldo + col;
+  *o = first ? v : *o + v;
+}
+
 }  // namespace
 }  // namespace ns
 
@@ -237,6 +317,75 @@ static std::atomic<int> g_moe_gemv_rows{0}, g_moe_grouped_rows{0};
 void set_moe_tuning(int what, int value) { (what == 0 ? g_moe_gemv_rows : g_moe_grouped_rows).store(value); }
 // calls served by [0] the grouped path, [1] the decode kernel, [2] the loop kernel; [3] grouped attempts that returned "not taken" (ns_hip_moe_stats)
 static std::atomic<uint64_t> g_moe_stats[4];
+
+// ns_hip_moe_ffn_silu: "moe_ffn_fused" (-1 = default: on) and its counters (ns_hip_moe_ffn_stats)
+static std::atomic<int> g_moe_ffn_fused{-1};
+void set_moe_ffn_fused(int on) { g_moe_ffn_fused.store(on < 0 ? -1 : (on != 0)); }
+static std::atomic<uint64_t> g_moe_ffn_stats[4];
+
+// the router's exponential table: table_exp_f16 of the reference (ne_layers.c:745), fp16(expf(fp16 -> fp32(code))) for every code, made by
+// the HOST's expf like the reference's and uploaded once per device
+static uint16_t f32_to_f16_bits(float f) {  // round to nearest even, subnormals kept (what F16C's conversion and ne_compute_fp32_to_fp16 do)
+  uint32_t x;
+  memcpy(&x, &f, 4);
+  const uint32_t sign = (x >> 16) & 0x8000u;
+  x &= 0x7fffffffu;
+  if (x >= 0x7f800000u) return uint16_t(sign | (x > 0x7f800000u ? 0x7e00u : 0x7c00u));
+  if (x >= 0x477ff000u) return uint16_t(sign | 0x7c00u);  // rounds to 65536 and beyond
+  if (x < 0x38800000u) {                                   // below 2^-14: a subnormal half, in units of 2^-24
+    if (x < 0x33000000u) return uint16_t(sign);          // below 2^-25: zero (2^-25 itself is a tie to even = zero)
+    const int e = int(x >> 23);                           // 102 .. 112
+    const uint32_t man = (x & 0x7fffffu) | 0x800000u;     // value = man * 2^(e - 150)
+    const int shift = 126 - e;                            // half units: man >> shift
+    uint32_t h = man >> shift;
+    const uint32_t rem = man & ((1u << shift) - 1u), halfway = 1u << (shift - 1);
+    if (rem > halfway || (rem == halfway && (h & 1u))) h++;
+    return uint16_t(sign | h);
+  }
+  uint32_t h = ((x - 0x38000000u) >> 13);
+  const uint32_t rem = x & 0x1fffu;
+  if (rem > 0x1000u || (rem == 0x1000u && (h & 1u))) h++;
+  return uint16_t(sign | h);
+}
+static float f16_bits_to_f32_host(uint16_t h) {
+  const uint32_t sign = uint32_t(h & 0x8000u) << 16, e = (h >> 10) & 31u, man = h & 0x3ffu;
+  uint32_t x;
+  if (e == 31u) {
+    x = sign | 0x7f800000u | (man << 13);
+  } else if (e) {
+    x = sign | ((e + 112u) << 23) | (man << 13);
+  } else {
+    float f = float(man) * 5.9604644775390625e-8f;  // man * 2^-24, exact
+    memcpy(&x, &f, 4);
+    x |= sign;
+  }
+  float f;
+  memcpy(&f, &x, 4);
+  return f;
+}
+static std::mutex g_exp_table_mutex;
+static uint16_t* g_exp_table[64];
+const uint16_t* moe_exp_table(bool build) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
+    (void)hipGetLastError();
+    set_error("moe_route: no current device for the exponential table");
+    return nullptr;
+  }
+  std::lock_guard<std::mutex> lock(g_exp_table_mutex);
+  if (g_exp_table[dev] || !build) return g_exp_table[dev];
+  std::vector<uint16_t> host(65536);
+  for (uint32_t i = 0; i < 65536u; i++) host[i] = f32_to_f16_bits(expf(f16_bits_to_f32_host(uint16_t(i))));
+  uint16_t* d = nullptr;
+  if (hipMalloc((void**)&d, host.size() * 2) != hipSuccess || hipMemcpy(d, host.data(), host.size() * 2, hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipGetLastError();
+    if (d) (void)hipFree(d);
+    set_error("moe_route: allocating the exponential table failed");
+    return nullptr;
+  }
+  g_exp_table[dev] = d;
+  return d;
+}
 
 // 0 = done, -1 = error (set_error), 1 = not taken (the caller's per-row path serves the call)
 static int mul_mat_id_grouped(const float* dA, const int32_t* dIds, int ids_stride, int id, const ns_expert_group* g, float* dC, int m, int lda,
@@ -349,6 +498,7 @@ ns_expert_group* ns_hip_expert_group_create(const ns_weight* const* experts, int
     set_error("expert group: S1..S8, the 4-bit float types and fp8 are supported");
     return nullptr;
   }
+  (void)moe_exp_table();  // the router's table, made outside any capture (ns_hip_moe_route); a failure is reported by that entry
   ns_expert_group* g = new ns_expert_group;
   g->experts.assign(experts, experts + n_as);
   if (hipMalloc((void**)&g->table, sizeof(MoeExpert) * n_as) != hipSuccess ||
@@ -466,6 +616,147 @@ int ns_hip_mul_mat_id(const float* dA, const int32_t* dIds, int ids_stride, int 
 
 void ns_hip_moe_stats(uint64_t out[4]) {
   for (int i = 0; i < 4; i++) out[i] = g_moe_stats[i].load();
+}
+
+int ns_hip_moe_route(const float* dLogits, int ld_logits, int m, int n_expert, int n_used, int32_t* dIds, int ids_stride, float* dWeights,
+                     int w_stride, float* dProbs, void* stream) {
+  if (!have_device()) return -1;
+  if (n_used < 1 || n_used > 8 || n_expert < n_used || n_expert > 64 || m < 1) {
+    set_error("moe_route: need 1 <= n_used <= 8, n_used <= n_expert <= 64 and at least one row");
+    return -1;
+  }
+  if (!dLogits || !dIds || !dWeights || ld_logits < n_expert || ids_stride < n_used || w_stride < n_used) {
+    set_error("moe_route: bad argument (null pointer, or a row stride shorter than its row)");
+    return -1;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  const bool capturing = hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+  (void)hipGetLastError();
+  const uint16_t* table = moe_exp_table(!capturing);  // (a synchronous upload: never inside a capture)
+  if (!table) {
+    if (capturing) set_error("moe_route: the exponential table is not built yet - call ns_hip_warm_up, create an expert group or route once before capturing");
+    return -1;
+  }
+  hipLaunchKernelGGL(moe_route_kernel, dim3(unsigned((m + kRouteWaves - 1) / kRouteWaves)), dim3(kRouteWaves * 64), 0, st, dLogits, ld_logits, m,
+                     n_expert, n_used, table, dIds, ids_stride, dWeights, w_stride, dProbs);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    set_error(std::string("moe_route launch: ") + hipGetErrorString(e));
+    return -1;
+  }
+  return 0;
+}
+
+// the composition: per selection three ns_hip_mul_mat_id calls (gate with SiLU, up with Mul, down) and the weighted sum
+static int moe_ffn_composition(const float* dA, int lda, int m, const int32_t* dIds, int ids_stride, const float* dWeights, int w_stride, int n_used,
+                               const ns_expert_group* gate, const ns_expert_group* up, const ns_expert_group* down, float* dOut, int ldo,
+                               hipStream_t st) {
+  const int ff = gate->experts[0]->n, dn = down->experts[0]->n;
+  float* t1 = static_cast<float*>(stream_scratch(st, size_t(m) * ff * 4, 35));
+  float* t2 = static_cast<float*>(stream_scratch(st, size_t(m) * ff * 4, 36));
+  float* t3 = static_cast<float*>(stream_scratch(st, size_t(m) * dn * 4, 37));
+  if (!t1 || !t2 || !t3) {
+    set_error("moe_ffn_silu: scratch allocation failed");
+    return -1;
+  }
+  for (int i = 0; i < n_used; i++) {
+    if (ns_hip_mul_mat_id(dA, dIds, ids_stride, i, gate, t1, m, lda, ff, NS_EPI_SILU, nullptr, 0, st) != 0 ||
+        ns_hip_mul_mat_id(dA, dIds, ids_stride, i, up, t2, m, lda, ff, NS_EPI_MUL, t1, ff, st) != 0 ||
+        ns_hip_mul_mat_id(t2, dIds, ids_stride, i, down, t3, m, ff, dn, NS_EPI_NONE, nullptr, 0, st) != 0)
+      return -1;
+    const size_t total = size_t(m) * dn;
+    hipLaunchKernelGGL(moe_weighted_add_kernel, dim3(unsigned((total + 255) / 256)), dim3(256), 0, st, dOut, ldo, t3, dn,
+                       dWeights ? dWeights + i : nullptr, w_stride, m, dn, i == 0 ? 1 : 0);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+      set_error(std::string("moe_ffn_silu (weighted sum): ") + hipGetErrorString(e));
+      return -1;
+    }
+  }
+  g_moe_ffn_stats[1]++;
+  return 0;
+}
+
+// the fused launches: 0 = done, -1 = error, 1 = not taken (nothing written to dOut yet: the composition serves the call)
+static int moe_ffn_fused(const float* dA, int lda, int m, const int32_t* dIds, int ids_stride, const float* dWeights, int w_stride, int n_used,
+                         const ns_expert_group* gate, const ns_expert_group* up, const ns_expert_group* down, float* dOut, int ldo, hipStream_t st) {
+  const ns_weight *wg = gate->experts[0], *wu = up->experts[0], *wd = down->experts[0];
+  const int ff = wg->n, n_as = int(gate->experts.size());
+  if (wg->kind == WK_F8 || wd->kind == WK_F8 || !wg->single_span || !wu->single_span || !wd->single_span || (ff & 3)) return 1;
+  if (int64_t(m) * n_used >= 65536 / std::max(n_used, 1)) return 1;  // (pairs along grid.y, launch_gemv)
+  // fp32 intermediate silu(gate) * up, [m][n_used][ff]: the down launches round it to fp16 while staging, like every fp32 activation row
+  float* inter = static_cast<float*>(stream_scratch(st, size_t(m) * n_used * ff * 4, 34));
+  if (!inter) return 1;
+  {
+    MoeRoute route{gate->table, dIds, n_as};
+    route.table1 = up->table;
+    route.pairs = m * n_used, route.nsel = n_used, route.ids_stride = ids_stride;
+    route.a_stride = lda, route.c_stride = ff;
+    SmallMArgs a{};
+    a.a = dA, a.lda = lda, a.m = 1, a.ldc = ff, a.nseg = 2;
+    a.seg[0] = {wg, inter, nullptr};
+    a.seg[1] = {wu, nullptr, nullptr};
+    a.epilogue = NS_EPI_SILU, a.dual = true;
+    a.moe = &route;
+    const hipError_t e = launch_gemv(a, st);
+    if (e == hipErrorNotSupported) return 1;
+    if (e != hipSuccess) {
+      set_error(std::string("moe_ffn_silu (gate / up launch): ") + hipGetErrorString(e));
+      return -1;
+    }
+  }
+  for (int i = 0; i < n_used; i++) {
+    MoeRoute route{down->table, dIds + i, n_as};
+    route.pairs = m, route.nsel = 1, route.ids_stride = ids_stride;
+    route.w = dWeights ? dWeights + i : nullptr, route.w_stride = w_stride;
+    route.a_stride = (long long)n_used * ff, route.c_stride = ldo, route.d_stride = ldo;
+    SmallMArgs a{};
+    a.a = inter + size_t(i) * ff, a.lda = n_used * ff, a.m = 1, a.ldc = ldo, a.nseg = 1;
+    a.seg[0] = {wd, dOut, nullptr};
+    a.epilogue = i ? NS_EPI_ADD : NS_EPI_NONE, a.d = i ? dOut : nullptr, a.ldd = ldo;
+    a.moe = &route;
+    const hipError_t e = launch_gemv(a, st);
+    if (e == hipErrorNotSupported && i == 0) {
+      g_moe_ffn_stats[2]++;  // (the gate / up launch went out; its result is dropped)
+      return 1;
+    }
+    if (e != hipSuccess) {
+      set_error(std::string("moe_ffn_silu (down launch): ") + hipGetErrorString(e));
+      return -1;
+    }
+  }
+  g_moe_ffn_stats[0]++;
+  g_moe_ffn_stats[2] += uint64_t(1 + n_used);
+  return 0;
+}
+
+int ns_hip_moe_ffn_silu(const float* dA, int lda, int m, const int32_t* dIds, int ids_stride, const float* dWeights, int w_stride, int n_used,
+                        const ns_expert_group* gate, const ns_expert_group* up, const ns_expert_group* down, float* dOut, int ldo, void* stream) {
+  if (!have_device()) return -1;
+  if (!dA || !dIds || !gate || !up || !down || !dOut || m < 1 || m > 65535 || n_used < 1 || n_used > ids_stride || (dWeights && w_stride < n_used)) {
+    set_error("moe_ffn_silu: bad argument");
+    return -1;
+  }
+  const ns_weight *wg = gate->experts[0], *wu = up->experts[0], *wd = down->experts[0];
+  if (wu->n != wg->n || wu->k != wg->k || wd->k != wg->n || gate->experts.size() != up->experts.size() || gate->experts.size() != down->experts.size() ||
+      lda < wg->k || ldo < wd->n) {
+    set_error("moe_ffn_silu: the gate, up and down groups do not form one feed-forward block (shapes, expert counts), or a row stride is too short");
+    return -1;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  static const int gemv_env = getenv("NS_MOE_GEMV_ROWS") ? atoi(getenv("NS_MOE_GEMV_ROWS")) : 8;
+  const int gemv_set = g_moe_gemv_rows.load();
+  const int moe_gemv_rows = gemv_set ? gemv_set : gemv_env;
+  if (g_moe_ffn_fused.load() != 0 && m <= moe_gemv_rows) {
+    const int rc = moe_ffn_fused(dA, lda, m, dIds, ids_stride, dWeights, w_stride, n_used, gate, up, down, dOut, ldo, st);
+    if (rc <= 0) return rc;
+  }
+  return moe_ffn_composition(dA, lda, m, dIds, ids_stride, dWeights, w_stride, n_used, gate, up, down, dOut, ldo, st);
+}
+
+void ns_hip_moe_ffn_stats(uint64_t out[4]) {
+  for (int i = 0; i < 4; i++) out[i] = g_moe_ffn_stats[i].load();
 }
 
 }  // extern "C"

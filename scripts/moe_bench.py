@@ -3,6 +3,8 @@
 int4 g32 bf16): the three expert-indexed matmuls of ffn_id_silu (ne_layers.c:8053-8170: gate with SiLU, up with Mul, down) per
 selected expert, ids on the device, one HIP graph; parity of one token's rows against the oracle's fp64 product.  Prints us per
 MoE FFN layer, the HBM rate over the expert weights a token really touches, and tokens/s of 32 such layers.
+Below 32 tokens a second leg times the whole block through ns_hip_moe_ffn_silu (routing weights and the sum over the selections included)
+in the same graph form, on its fused launches and - "moe_ffn_fused" = 0 - on its composition: medians of interleaved replay batches.
 usage: moe_bench.py [tokens=1]"""
 import ctypes as C, json, os, sys
 import numpy as np
@@ -80,6 +82,58 @@ else:
         g.replay()
     e1.record(); torch.cuda.synchronize()
 us = e0.elapsed_time(e1) * 1e3 / reps / nlay
+# the fused entry beside that composition, same graph form: out = sum_sel w * down(silu(gate) * up) per layer
+block = {}
+if m < 32:
+    wts = torch.rand((m, topk), device="cuda") + 0.25
+    out = torch.empty((m, d), device="cuda")
+
+    def block_chain(s):
+        for (wg, gg), (wu, gu), (wd, gd) in layers:
+            pkg.check(L.ns_hip_moe_ffn_silu(a.data_ptr(), d, m, ids.data_ptr(), topk, wts.data_ptr(), topk, topk, gg, gu, gd, out.data_ptr(), d, s))
+
+    def stats():
+        v = (C.c_uint64 * 4)()
+        L.ns_hip_moe_ffn_stats(v)
+        return [int(x) for x in v]
+
+    graphs = {}
+    for name, fused_on in (("fused", 1), ("entry_composition", 0)):
+        L.ns_hip_set_tuning(b"moe_ffn_fused", fused_on)
+        block_chain(st)
+        torch.cuda.synchronize()
+        s0 = stats()
+        gb = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gb):
+            block_chain(C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        s1 = stats()
+        block[name + "_calls"] = [s1[0] - s0[0], s1[1] - s0[1]]   # [on the fused launches, on the composition] while capturing
+        if fused_on:
+            block["fused_launches_per_layer"] = (s1[2] - s0[2]) // nlay
+        graphs[name] = gb
+    L.ns_hip_set_tuning(b"moe_ffn_fused", -1)
+    graphs["three_calls"] = g   # the 3 * topk calls timed above (no weighting, no sum)
+    times = {k: [] for k in graphs}
+    for _ in range(7):
+        for k, gb in graphs.items():
+            gb.replay(); torch.cuda.synchronize()
+            e0.record()
+            for _ in range(reps):
+                gb.replay()
+            e1.record(); torch.cuda.synchronize()
+            times[k].append(e0.elapsed_time(e1) * 1e3 / reps / nlay)
+    for k, v in times.items():
+        block["us_per_layer_" + k] = {"median": round(float(np.median(v)), 2), "min": round(min(v), 2), "max": round(max(v), 2)}
+    # the block's parity: token 0 against the fp64 oracle over both selections
+    graphs["fused"].replay(); torch.cuda.synchronize()
+    hostb = lambda t: (lambda b: (b.__setitem__(slice(None), t.cpu().numpy()), b)[1])(nso.aligned_bytes(t.numel()))
+    a0b, refb = a[:1].cpu().numpy(), np.zeros((1, d))
+    for sel in range(topk):
+        ex = int(ids_np[0, sel])
+        (wg, _), (wu, _), (wd, _) = layers[-1]
+        hg, hu = nso.gemm_f64(a0b, hostb(wg[ex][1])), nso.gemm_f64(a0b, hostb(wu[ex][1]))
+        refb += float(wts[0, sel]) * nso.gemm_f64((hg / (1.0 + np.exp(-hg)) * hu).astype(np.float32), hostb(wd[ex][1]))
+    block["fused_parity_rel_l2_vs_fp64_oracle_token0"] = float("%.3g" % nso.rel_l2(out[:1].cpu().numpy(), refb))
 # parity of the last layer's last selection (token 0): silu(a Wg) * (a Wu) then Wd, fp64 over the oracle's blobs
 (wg, _), (wu, _), (wd, _) = layers[-1]
 e = int(ids_np[0, topk - 1])
@@ -97,4 +151,4 @@ print(json.dumps({"what": "Mixtral-8x7B-shaped MoE FFN (8 x {14336x4096 gate, up
                   "hbm_GBps_over_touched_weights": round(touched / us / 1e3, 1), "tokens_per_s_of_32_moe_ffn_layers": round(m * 1e6 / (32 * us), 1),
                   "parity_rel_l2_vs_fp64_oracle_token0": float("%.3g" % par), "launches_per_layer": 3 * topk,
                   "grouped_by_expert": m >= 32 and os.environ.get("NS_MOE_GROUPED_ROWS", "32") != "0",
-                  "tflops": round(m * topk * 3 * 2.0 * d * ff / us / 1e6, 1)}))
+                  "tflops": round(m * topk * 3 * 2.0 * d * ff / us / 1e6, 1), "moe_ffn_silu": block}))
