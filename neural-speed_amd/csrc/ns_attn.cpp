@@ -66,22 +66,22 @@ static hipError_t launch_attn(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, hipS
     // partials go to the caller's workspace (`tmp`, sized by bestla_fusion_attn_workspace_size: the reference's own contract, and the only choice
     // that works on a stream being captured for the first time); without one, to a grow-only per-stream scratch
     ws = device_tmp ? reinterpret_cast<float*>(a.tmp) : nullptr;
-    if (!ws) ws = static_cast<float*>(stream_scratch(st, pl.partial_bytes, 1));
+    if (!ws) ws = static_cast<float*>(stream_scratch(st, pl.partial_bytes, SLOT_ATTN_PARTIALS));
     if (!ws) {  // scratch allocation failed: planned again as one range, still correct
       kn.no_partials = true;
       pl = attn_plan(a, dst16, kn, g_affine, why);
     }
   }
   // (nullptr, e.g. first use on a capturing stream: the merge launch)
-  uint32_t* tickets = pl.want_tickets ? static_cast<uint32_t*>(stream_scratch_zeroed(st, kAttnTicketCap * 4, 22)) : nullptr;
+  uint32_t* tickets = pl.want_tickets ? static_cast<uint32_t*>(stream_scratch_zeroed(st, kAttnTicketCap * 4, SLOT_ATTN_TICKETS)) : nullptr;
   return launch_attn_onerow(pl, ws, tickets, st);
 }
 
 // scratch a moving-length decode launch needs (partials for the longest context, the merge tickets): allocated BEFORE the route's capture
 bool attn_prepare_moving(hipStream_t st, int batch, int heads, int heads_kv, int head_size, int cap) {
   const size_t b = attn_ws_bytes(attn_knobs(), batch, heads, heads_kv, head_size, 1, cap);
-  if (b && !stream_scratch(st, b, 1)) return false;
-  return stream_scratch_zeroed(st, kAttnTicketCap * 4, 22) != nullptr;
+  if (b && !stream_scratch(st, b, SLOT_ATTN_PARTIALS)) return false;
+  return stream_scratch_zeroed(st, kAttnTicketCap * 4, SLOT_ATTN_TICKETS) != nullptr;
 }
 
 bool attn_device_visible(const char* who) {

@@ -18,7 +18,7 @@ constexpr int kA2KB = 64;                                       // attn_mfma2 / 
 constexpr int kA2VSub = kA2KB * 32 + 128;                       // bytes per V subtile: [64 keys][16 dims] fp16 + the bank offset
 template <int HS>
 constexpr int a2_stage_bytes() { return kA2KB * HS * 2 + (HS / 16) * kA2VSub; }
-constexpr size_t kAttnTicketCap = 65536;                        // merge tickets of a stream (scratch slot 22)
+constexpr size_t kAttnTicketCap = 65536;                        // merge tickets of a stream (SLOT_ATTN_TICKETS)
 
 struct AttnParams {
   const float* q;

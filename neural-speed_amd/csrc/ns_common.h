@@ -120,7 +120,7 @@ struct ns_weight {
   bool single_span = false;  // the allocation is < 4 GiB, i.e. the offsets above are usable as 32-bit soffsets
   uint64_t stream_bytes = 0;  // algorithmic bytes (reference formula)
   int device = 0;
-  // gemm2 (ns_gemm.hip) rounds `scale * g2_pre` to fp16 and multiplies its accumulators by g2_post = 1 / g2_pre: a
+  // the tiled prefill GEMM (ns_gemm2.hip, ns_gemm3.hip) rounds `scale * g2_pre` to fp16 and multiplies its accumulators by g2_post = 1 / g2_pre: a
   // power of two chosen at load time from the largest |scale| so that dequantised weights stay in fp16's normal range
   float g2_pre = 1.f, g2_post = 1.f;
   // fp8 weights (a code spans 2^-7 .. 480 or 2^-15 .. 57344 before its scale): false when no power of two keeps the largest scaled code
@@ -218,14 +218,53 @@ struct SmallMArgs {
   const MoeRoute* moe = nullptr;       // expert picked on the device (m = 1, fp32 activations); gemv_kernel only: launch_gemv() directly
 };
 hipError_t launch_smallm(const SmallMArgs& a, hipStream_t st);
-// ns_gemm.hip: second-generation prefill GEMM; hipErrorNotSupported = use the first-generation gemm_kernel
+// ns_gemm.cpp: the tiled prefill GEMM (gemm3_kernel / gemm2_kernel as ns_gemm_plan.cpp decides); hipErrorNotSupported = use the
+// first-generation gemm_kernel or the caller's general path
 hipError_t launch_gemm2(const SmallMArgs& a, hipStream_t st);
-void gemm_scratch_release();  // frees the per-stream scratch buffers
-// grow-only device scratch per (stream, slot): slot 0 = fp16 copy of A (prefill GEMM), 1 = attention partials, (4, 6, 7: ns_i8ref.hip; 10-13: ns_kvcache.hip host entries; 21: ns_gemvs.hip split-K tickets;)
-// 2 = split-K partials, 3 = shuffled activations.  Safe under stream capture (buffers handed out while capturing are
-// never freed or moved until gemm_scratch_release()); nullptr only when the allocation itself fails.
+// ---- ns_scratch.cpp: grow-only device scratch per (stream, slot) ------------------------------------------------------------------------------
+// Safe under stream capture (buffers handed out while capturing are never freed or moved until gemm_scratch_release()); nullptr only when
+// the allocation itself fails.  A slot with several owners is safe to share because all of them are launchers on ONE stream (the key), each
+// fills the buffer and has it read by launches it issues before it returns — the contents are dead between calls — and a buffer only
+// grows (a larger request waits for the stream before the old buffer is freed, or retires it when a graph may point at it).
+enum ScratchSlot : int {
+  SLOT_A16 = 0,               // fp16 copy of the activations: prefill GEMM (ns_gemm.cpp), ns_gemvs.hip, ns_dispatch.cpp (wide decode) — shared, see above
+  SLOT_ATTN_PARTIALS = 1,     // ns_attn.cpp: (m, l, acc) partials of the context ranges
+  SLOT_SPLITK_PARTIALS = 2,   // split-K partial tiles: prefill GEMM (ns_gemm.cpp) and ns_gemvs.hip's slab — shared, see above
+  SLOT_GATHERED_A = 3,        // ns_dispatch.cpp: activations gathered by an act-order weight's shuffle
+  SLOT_I8_GEMM_AQ = 4,        // ns_i8ref.hip: u8 activation codes + scales + zero points of the int8-reference GEMM
+  SLOT_FFN_TMP1 = 5,          // ns_dispatch.cpp: act(gate) of an FFN whose caller gave no buffer
+  SLOT_I8_DECODE_AQ = 6,      // ns_i8ref.hip: the same for a decode launch (I8Act)
+  SLOT_I8_GEMM_AP = 7,        // ns_i8ref.hip: fp16 operand slices of the int8-reference GEMM
+  SLOT_FFN_TMP2_16 = 8,       // ns_dispatch.cpp: fp16 shadow of act(gate) * up
+  SLOT_FFN_TMP2 = 9,          // ns_dispatch.cpp: act(gate) * up
+  SLOT_KV_HOST_A = 10,        // ns_kvcache.hip host-tensor entries (null stream): staging of host operands, four at most per call
+  SLOT_KV_HOST_B = 11,
+  SLOT_KV_HOST_C = 12,
+  SLOT_KV_HOST_D = 13,
+  SLOT_GEMVS_TICKETS = 21,    // ns_gemvs.hip: split-K tickets (zeroed, self-resetting)
+  SLOT_ATTN_TICKETS = 22,     // ns_attn.cpp: merge tickets (zeroed, self-resetting)
+  SLOT_ROPE_TAB = 23,         // ns_quant.hip: cos / sin table of launch_rope_qkv_append
+  SLOT_MHA_PARTIALS = 24,     // ns_device.hip device-layout attention (allocated ahead of a capture by ns_route.cpp): partials
+  SLOT_MHA_TICKETS = 25,      // ... and its merge tickets (zeroed, self-resetting)
+  // 30 .. 32: two owners.  ns_moe.hip's grouped mul_mat_id (ids / gathered fp16 rows / raw products) and the device route's prompt-sized
+  // window (fp16 shadows of a norm's, the attention's, the FFN's output; ns_route_fuse.cpp).  Shared safely, see above: the grouped path
+  // synchronises its stream and is never captured, a window's shadows are written and read by launches of that one window
+  // (the route's four keep the names its planner and tests/tools/route_fuse_main.cpp have always used)
+  SLOT_MOE_IDS = 30,
+  kSlotNorm16 = 30,
+  SLOT_MOE_ROWS16 = 31,
+  kSlotAttn16 = 31,
+  SLOT_MOE_PRODUCTS = 32,
+  kSlotFfn16 = 32,
+  kSlotRopeTab = 33,   // ns_route_exec.cpp: RoPE angle table of XK_QKV_ROPE launches
+  SLOT_MOE_INTER = 34,        // ns_moe.hip ns_hip_moe_ffn_silu: the fused launches' intermediate
+  SLOT_MOE_T1 = 35,           // ... and its composition's three temporaries
+  SLOT_MOE_T2 = 36,
+  SLOT_MOE_T3 = 37,
+};
 void* stream_scratch(hipStream_t st, size_t bytes, int slot);
 void* stream_scratch_zeroed(hipStream_t st, size_t bytes, int slot);  // zero-filled when (re)allocated: self-resetting counters
+void gemm_scratch_release();  // frees every stream's scratch buffers
 // fp32 [m][lda] -> fp16 [m][ld16] (ld16 a multiple of 8, columns k..ld16-1 zero)
 hipError_t launch_cvt_a16(const float* a, void* out16, int m, int k, int lda, int ld16, hipStream_t st);
 // ns_gemv_host.cpp: second-generation decode kernel (m <= 16; gemv_kernel, ns_gemv.hip — compiled once per weight kind and scales-per-record
@@ -260,18 +299,17 @@ void set_moe_ffn_fused(int on);  // ns_moe.hip: ns_hip_moe_ffn_silu takes 1 the 
 // (an expert group's creation, ns_hip_warm_up, a route call outside a stream capture); nullptr + error string when it cannot be made.
 // build = false: the table if it exists already, else nullptr (a caller inside a capture: the upload is synchronous)
 const uint16_t* moe_exp_table(bool build = true);
-void set_gemm3_min_m(int m);  // ns_gemm.hip: rows from which gemm3_kernel is used (0 = default)
-void set_gemm3_wide(int on);  // ns_gemm.hip: 1 the cross-wave output epilogue of gemm3_kernel's 1 x 4 wave tiles, 0 (default) the per-wave one, -1 = environment / default
-void set_gemm3_f8(int on);  // ns_gemm.hip: 1 (default) fp8 weights take gemm3_kernel at prompt size, 0 they stay on the first-generation kernel, -1 = NS_G3_F8 / default
-bool gemm3_f8_on();
-// may this weight's prompt-size GEMMs run on the tiled kernel (ns_gemm.hip)?  Every integer / f4 weight; fp8 ones while "g3_f8" is on and the
+void set_gemm3_min_m(int m);  // ns_gemm.cpp: rows from which gemm3_kernel is used (0 = default)
+void set_gemm3_wide(int on);  // ns_gemm.cpp: 1 the cross-wave output epilogue of gemm3_kernel's 1 x 4 wave tiles, 0 (default) the per-wave one, -1 = environment / default
+void set_gemm3_f8(int on);  // ns_gemm.cpp: 1 (default) fp8 weights take gemm3_kernel at prompt size, 0 they stay on the first-generation kernel, -1 = NS_G3_F8 / default
+// may this weight's prompt-size GEMMs run on the tiled kernel (ns_gemm_plan.cpp)?  Every integer / f4 weight; fp8 ones while "g3_f8" is on and the
 // load found range factors for them (ns_weight::g2_ok)
 bool gemm3_takes(const ns_weight* w);
-void set_gemm3_bm(int bm);  // ns_gemm.hip: force gemm3_kernel's row-tile height (tests / A-B runs); 0 = automatic  // ns_attn.cpp: context-split rule of the decode attention kernel
+void set_gemm3_bm(int bm);  // ns_gemm.cpp: force gemm3_kernel's row-tile height (tests / A-B runs); 0 = automatic  // ns_attn.cpp: context-split rule of the decode attention kernel
 void set_decode_waves(int nw);  // 0 = by shape
 void set_gemv_rows1(int on);    // 1 (default): one-row launches of gemv_kernel take its one-row instantiation; 0: the general one (same bits)
 int decode_waves(int grid, int ks, bool dual);  // waves per workgroup of a decode launch (both kernel generations)
-void srow_rule(const ns_weight* w, int* num, int* den);          // scale row of k-step s = s * num / den
+void srow_rule(const ns_weight* w, int* num, int* den);          // ns_gemm_plan.cpp (host only): scale row of k-step s = s * num / den
 // the same rule as a branch-free (s * mul) >> shift, verified for every k-step; false = not expressible
 bool srow_params(const ns_weight* w, int* mul, int* shift);
 hipError_t launch_gemm(const SmallMArgs& a, hipStream_t st);  // large-M tiled MFMA GEMM (single segment)

@@ -1134,7 +1134,7 @@ int ns_hip_mha_f32_device_layout(const float* dQ, const float* dK, const float* 
     const size_t per_row = size_t(heads) * nsplit * (2 + head_size) * sizeof(float);
     int chunk = seq;
     if (batch == 1 && masked && size_t(seq) * per_row > (size_t(64) << 20)) chunk = int(std::max<size_t>(1, (size_t(64) << 20) / per_row));
-    float* ws = static_cast<float*>(ns::stream_scratch(st, size_t(batch) * chunk * per_row, 24));
+    float* ws = static_cast<float*>(ns::stream_scratch(st, size_t(batch) * chunk * per_row, ns::SLOT_MHA_PARTIALS));
     if (ws) {
       for (int r0 = 0; r0 < seq; r0 += chunk) {
         const int nr = std::min(chunk, seq - r0);
@@ -1148,7 +1148,7 @@ int ns_hip_mha_f32_device_layout(const float* dQ, const float* dK, const float* 
         static const bool inl_off = getenv("NS_MHA_INLAUNCH") && atoi(getenv("NS_MHA_INLAUNCH")) == 0;
         uint32_t* tickets = nullptr;
         if (aff.k && seq == 1 && !inl_off && size_t(batch) * heads <= 65536)
-          tickets = static_cast<uint32_t*>(ns::stream_scratch_zeroed(st, 65536 * 4, 25));
+          tickets = static_cast<uint32_t*>(ns::stream_scratch_zeroed(st, 65536 * 4, ns::SLOT_MHA_TICKETS));
         _Float16* o16 = (aff.k && seq == 1) ? static_cast<_Float16*>(ns::g_mha_out16) : nullptr;
         if (tickets) {
           if (head_size == 64)

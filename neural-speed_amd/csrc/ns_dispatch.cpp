@@ -160,7 +160,7 @@ int forward_impl(const float* dA, const ns_weight* w, float* dC, int m, int lda,
     return -1;
   }
   if (w->shuf) {  // GPTQ act-order blob: gather A'[j] = A[shuf[j]] into scratch first (prologue_a.h:322-330)
-    float* ga = static_cast<float*>(stream_scratch(st, size_t(m) * w->k * 4, 3));
+    float* ga = static_cast<float*>(stream_scratch(st, size_t(m) * w->k * 4, SLOT_GATHERED_A));
     if (!ga) {
       set_error("forward: no scratch for the activation shuffle (out of device memory)");
       return -1;
@@ -213,7 +213,7 @@ int forward_impl(const float* dA, const ns_weight* w, float* dC, int m, int lda,
   // fp32 activations, several rows, many column tiles: one conversion pass to fp16 (about 2 us) halves what every
   // workgroup of the streaming kernel stages (14336 x 4096 at 16 rows: 39 -> 24 us; at 8 rows: 25 -> 18 us)
   if (small && !dA16 && m >= 6 && staging > 60e6 && lda == w->k && w->k % 8 == 0) {
-    void* sc = stream_scratch(st, size_t(m) * w->k * 2, 0);
+    void* sc = stream_scratch(st, size_t(m) * w->k * 2, SLOT_A16);
     if (sc && hip_ok(launch_cvt_a16(dA, sc, m, w->k, lda, w->k, st), "activation fp16 pass")) a.a16 = sc;
   }
   if (!hip_ok(small ? launch_smallm(a, st) : launch_gemm(a, st), "gemm launch")) return -1;
@@ -442,7 +442,7 @@ int ns_hip_fusion_ffn3_gateup_x(const float* dA, const void* dA16, const ns_weig
     return -1;
   }
   if (!dTmp2) {  // the paths below produce the fp32 product
-    dTmp2 = static_cast<float*>(stream_scratch(st, size_t(seq) * fmid * 4, 9));
+    dTmp2 = static_cast<float*>(stream_scratch(st, size_t(seq) * fmid * 4, SLOT_FFN_TMP2));
     if (!dTmp2) {
       set_error("ffn3 gate/up: no scratch for tmp2 (out of device memory)");
       return -1;
@@ -466,7 +466,7 @@ int ns_hip_fusion_ffn3_gateup_x(const float* dA, const void* dA16, const ns_weig
       if (launched(launch_gemv_i8(a, &q, st), "int8-reference gate/up launch", &rc)) return rc;
     }
   }
-  if (!dTmp1) dTmp1 = static_cast<float*>(stream_scratch(st, size_t(seq) * fmid * 4, 5));
+  if (!dTmp1) dTmp1 = static_cast<float*>(stream_scratch(st, size_t(seq) * fmid * 4, SLOT_FFN_TMP1));
   if (!dTmp1) {
     set_error("ffn3: no scratch for tmp1 on the unfused path (out of device memory)");
     return -1;
@@ -494,7 +494,7 @@ int ns_hip_fusion_ffn3_forward_h(const float* dA, const void* dA16, const ns_wei
   // GEMM size, no fp32 tmp2 asked for: the intermediate exists as fp16 only (the down projection multiplies fp16 activations anyway);
   // it lives in the caller's dTmp2_16 or in per-stream scratch
   if (!dTmp2 && seq > 16 && !w2->shuf && !ref_int8_for(w2) && (w2->kind != WK_F8 || (gemm3_takes(w2) && (seq > 64 || !dA))) && fmid % 64 == 0) {
-    void* t16 = dTmp2_16 ? dTmp2_16 : stream_scratch(st, size_t(seq) * fmid * 2, 8);
+    void* t16 = dTmp2_16 ? dTmp2_16 : stream_scratch(st, size_t(seq) * fmid * 2, SLOT_FFN_TMP2_16);
     int rc;
     if (t16 && ns_hip_fusion_ffn3_gateup_h(dA, dA16, w1, w3, dTmp1, nullptr, t16, seq, act, stream) == 0 &&
         launched(launch_gemm2(single_args(nullptr, t16, fmid, seq, w2->n, w2, dOut, dOut16, NS_EPI_NONE, nullptr, 0), st),
@@ -502,7 +502,7 @@ int ns_hip_fusion_ffn3_forward_h(const float* dA, const void* dA16, const ns_wei
       return rc;
     // (outside the tiled kernel's envelope: the general path below, on an fp32 intermediate)
   }
-  if (!dTmp2) dTmp2 = static_cast<float*>(stream_scratch(st, size_t(seq) * fmid * 4, 9));
+  if (!dTmp2) dTmp2 = static_cast<float*>(stream_scratch(st, size_t(seq) * fmid * 4, SLOT_FFN_TMP2));
   if (!dTmp2) {
     set_error("ffn3: no scratch for tmp2 (out of device memory)");
     return -1;

@@ -999,7 +999,7 @@ hipError_t launch_gemvs(const SmallMArgs& a, hipStream_t st) {
   const size_t slab_bytes = size_t(S) * tiles * nq * 256 * sizeof(float);
   if (S > 1) {
     if (slab_bytes >= (size_t(1) << 31)) return hipErrorNotSupported;
-    slab = static_cast<float*>(stream_scratch(st, slab_bytes, 2));
+    slab = static_cast<float*>(stream_scratch(st, slab_bytes, SLOT_SPLITK_PARTIALS));
     if (!slab) return hipErrorNotSupported;
     // Who adds the slices: a second launch (gemvs_finalize_kernel, the default) or — "gvs_finalize" 0 — the tile's owner inside
     // the launch, behind one self-resetting ticket per tile unit.  Measured equal (profiles/r04u_split_k_finish.txt: 4096 x 14336
@@ -1008,12 +1008,12 @@ hipError_t launch_gemvs(const SmallMArgs& a, hipStream_t st) {
     // spins on tickets other workgroups draw), which a second launch does not — hence the default.
     static const int kTicketCap = 1 << 16;
     const int force_fin = gvs_knob(g_gvs_fin, "NS_GVS_FINALIZE", 1);
-    if (!force_fin && tiles <= uint32_t(kTicketCap)) tickets = static_cast<uint32_t*>(stream_scratch_zeroed(st, size_t(kTicketCap) * 4, 21));
+    if (!force_fin && tiles <= uint32_t(kTicketCap)) tickets = static_cast<uint32_t*>(stream_scratch_zeroed(st, size_t(kTicketCap) * 4, SLOT_GEMVS_TICKETS));
   }
 
   const void* a16 = a.a16;
   if (!shadow) {
-    void* sc = stream_scratch(st, size_t(a.m) * w0->k * 2, 0);
+    void* sc = stream_scratch(st, size_t(a.m) * w0->k * 2, SLOT_A16);
     if (!sc) return hipErrorNotSupported;
     const hipError_t ce = launch_cvt_a16(a.a, sc, a.m, w0->k, a.lda, w0->k, st);
     if (ce != hipSuccess) return ce;

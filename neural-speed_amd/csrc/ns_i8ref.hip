@@ -522,7 +522,7 @@ hipError_t i8_quantize_for_decode(const float* a, int lda, const ns_weight* w, i
   const int nblk = (w->k + bs - 1) / bs;
   const int ldq = (w->k + 15) & ~15;
   const size_t aq_bytes = size_t(m) * ldq;
-  uint8_t* base = static_cast<uint8_t*>(stream_scratch(st, aq_bytes + size_t(m) * nblk * 5 + 16, 6));
+  uint8_t* base = static_cast<uint8_t*>(stream_scratch(st, aq_bytes + size_t(m) * nblk * 5 + 16, SLOT_I8_DECODE_AQ));
   if (!base) return hipErrorOutOfMemory;
   float* as = reinterpret_cast<float*>(base + aq_bytes);
   uint8_t* az = base + aq_bytes + size_t(m) * nblk * 4;
@@ -569,7 +569,7 @@ hipError_t launch_i8ref(const float* a, int lda, const ns_weight* w, float* c, v
   // scratch: u8 codes [m][k] | fp32 scales [m][nblk] | u8 zero points [m][nblk]
   const size_t aq_bytes = (size_t(m) * w->k + 15) & ~size_t(15);
   const size_t sc_bytes = size_t(m) * nblk * 4;
-  uint8_t* base = static_cast<uint8_t*>(stream_scratch(st, aq_bytes + sc_bytes + size_t(m) * nblk + 16, 4));
+  uint8_t* base = static_cast<uint8_t*>(stream_scratch(st, aq_bytes + sc_bytes + size_t(m) * nblk + 16, SLOT_I8_GEMM_AQ));
   if (!base) return hipErrorOutOfMemory;
   uint8_t* aq = base;
   float* as = reinterpret_cast<float*>(base + aq_bytes);
@@ -589,7 +589,7 @@ hipError_t launch_i8ref(const float* a, int lda, const ns_weight* w, float* c, v
   const int want = four ? 1 : 2;               // the form of A' this weight multiplies
   uint8_t* pa = nullptr;
   if (v2) {
-    pa = static_cast<uint8_t*>(stream_scratch(st, size_t(m) * nsl * 64, 7));
+    pa = static_cast<uint8_t*>(stream_scratch(st, size_t(m) * nsl * 64, SLOT_I8_GEMM_AP));
     if (!pa) return hipErrorOutOfMemory;
   }
   if (!reuse_aq) {

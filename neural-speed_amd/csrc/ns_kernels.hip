@@ -258,7 +258,7 @@ hipError_t launch_scale_absmax(const void* scales, size_t count, uint32_t scale_
   return hipGetLastError();
 }
 
-// fp8 weights on the tiled GEMM (ns_gemm.hip): does any non-zero finite |scale| lie below 2^(e - drop), smax = f * 2^e with f in [0.5, 1)?
+// fp8 weights on the tiled GEMM (ns_gemm3.hip): does any non-zero finite |scale| lie below 2^(e - drop), smax = f * 2^e with f in [0.5, 1)?
 // `info[0]` = the largest |scale| (scale_absmax_kernel, earlier on the same stream); bit 1 of info[1] is set when one does.
 __global__ void scale_spread_kernel(const uint8_t* __restrict__ s, size_t count, uint32_t scale_dt, int drop, uint32_t* info, int cstep, int n) {
   const int e = int((info[0] >> 23) & 0xffu) - 126;
@@ -999,30 +999,6 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmParams p) {
     }
 }
 
-bool srow_params(const ns_weight* w0, int* mul, int* shift) {
-  int num, den;
-  srow_rule(w0, &num, &den);
-  if (num == 0) {
-    *mul = 0;
-    *shift = 0;
-  } else if (num == den) {
-    *mul = 1;
-    *shift = 0;
-  } else {
-    const int ratio = den / num;
-    if ((ratio & (ratio - 1)) == 0) {
-      *mul = 1;
-      *shift = __builtin_ctz(ratio);
-    } else {
-      *shift = 20;
-      *mul = ((1 << 20) + ratio - 1) / ratio;
-      for (int s = 0; s < w0->ksteps; s++)
-        if (((s * *mul) >> 20) != s / ratio) return false;
-    }
-  }
-  return true;
-}
-
 hipError_t launch_gemm(const SmallMArgs& a, hipStream_t st) {
   {
     const hipError_t e = launch_gemm2(a, st);
@@ -1107,19 +1083,6 @@ __global__ void unpack_kernel(const uint8_t* __restrict__ codes, const uint8_t* 
     v = (kind == WK_INT4) ? float(u - 8 - zp) : lut.v[u];
   }
   out[size_t(kk) * ld + col] = v * sc;
-}
-
-void srow_rule(const ns_weight* w, int* num, int* den) {
-  if (w->blocksize >= w->k) {
-    *num = 0;
-    *den = 1;
-  } else if (w->sps > 1 || w->blocksize == w->kstep_len) {
-    *num = 1;
-    *den = 1;
-  } else {
-    *num = w->kstep_len;
-    *den = w->blocksize;
-  }
 }
 
 hipError_t launch_unpack_fp32(const ns_weight* w, float* out, int ld, hipStream_t st) {

@@ -130,7 +130,6 @@ static char* kv_mirror_get(const char* p, size_t bytes) {
   return m.dev;
 }
 
-constexpr int kScratchHostA = 10, kScratchHostB = 11, kScratchHostC = 12, kScratchHostD = 13;
 // pinned, device-mapped staging for the decode-sized host calls (guarded by g_attn_host_mu): the kernels read / write host
 // memory over PCIe, a call is memcpy + launches + ONE synchronisation instead of blocking hipMemcpy round trips
 struct AttnPinned {
@@ -205,8 +204,8 @@ static void kv_update(const bestla_fusion_attn_fp32_update_kv_args_t* pp, const 
     }
   }
   // staging in the grow-only per-stream scratch (a hipMalloc / hipFree pair per call synchronises the whole device twice)
-  float* dsrc = static_cast<float*>(stream_scratch(nullptr, nsrc * 4, kScratchHostA));
-  _Float16* dout = static_cast<_Float16*>(stream_scratch(nullptr, total * 2, kScratchHostB));
+  float* dsrc = static_cast<float*>(stream_scratch(nullptr, nsrc * 4, SLOT_KV_HOST_A));
+  _Float16* dout = static_cast<_Float16*>(stream_scratch(nullptr, total * 2, SLOT_KV_HOST_B));
   bool ok = dsrc && dout && hipMemcpy(dsrc, a.src, nsrc * 4, hipMemcpyHostToDevice) == hipSuccess;
   if (ok) {
     // [batch x head] chunks of seq_size rows land at row seq_off of their seq_max-row slab
@@ -244,8 +243,8 @@ void bestla_reordered_attn_fp32_shift_rope_k(char* cache, const uint16_t* cossin
   const size_t row = size_t(head_size) * 2, slabs = size_t(batch_size) * heads_kv, n = size_t(seq_max - seq_keep);
   if (slabs == 0 || n == 0) return;
   std::lock_guard<std::mutex> host_lock(g_attn_host_mu);
-  _Float16* drows = static_cast<_Float16*>(stream_scratch(nullptr, slabs * n * row, kScratchHostA));
-  _Float16* dcs = static_cast<_Float16*>(stream_scratch(nullptr, row, kScratchHostB));
+  _Float16* drows = static_cast<_Float16*>(stream_scratch(nullptr, slabs * n * row, SLOT_KV_HOST_A));
+  _Float16* dcs = static_cast<_Float16*>(stream_scratch(nullptr, row, SLOT_KV_HOST_B));
   bool ok = drows && dcs && hipMemcpy(dcs, cossin, row, hipMemcpyHostToDevice) == hipSuccess &&
             hipMemcpy2D(drows, n * row, cache + size_t(seq_keep) * row, size_t(seq_max) * row, n * row, slabs, hipMemcpyHostToDevice) ==
                 hipSuccess;
@@ -353,10 +352,10 @@ void bestla_fusion_attn_fp32_fp16_fp16_fp32_forward(const attn_fp32_fp16_fp16_fp
       return;
     }
   }
-  void* dq = stream_scratch(nullptr, nq * 4, kScratchHostA);
-  void* dk = mk ? mk : stream_scratch(nullptr, nk * 2, kScratchHostB);
-  void* dv = mv ? mv : stream_scratch(nullptr, nv * 2, kScratchHostC);
-  void* dd = stream_scratch(nullptr, nd * 4, kScratchHostD);
+  void* dq = stream_scratch(nullptr, nq * 4, SLOT_KV_HOST_A);
+  void* dk = mk ? mk : stream_scratch(nullptr, nk * 2, SLOT_KV_HOST_B);
+  void* dv = mv ? mv : stream_scratch(nullptr, nv * 2, SLOT_KV_HOST_C);
+  void* dd = stream_scratch(nullptr, nd * 4, SLOT_KV_HOST_D);
   bool ok = dq && dk && dv && dd;
   ok = ok && hipMemcpy(dq, hp->Q, nq * 4, hipMemcpyHostToDevice) == hipSuccess &&
        (mk || hipMemcpy(dk, hp->K, nk * 2, hipMemcpyHostToDevice) == hipSuccess) &&

@@ -402,9 +402,9 @@ static int mul_mat_id_grouped(const float* dA, const int32_t* dIds, int ids_stri
   const int kpad = k;
   // scratch: ids column + permutation + validity (3 m ints), gathered fp16 rows [m + 1][k], raw products [m + 1][n] (one padding row: a
   // single-row group is launched with two rows — the tiled kernel's minimum — and its second row belongs to the NEXT group, launched later)
-  int32_t* ints = static_cast<int32_t*>(stream_scratch(st, size_t(3) * m * 4, 30));
-  _Float16* ag = static_cast<_Float16*>(stream_scratch(st, size_t(m + 1) * kpad * 2, 31));
-  float* cg = static_cast<float*>(stream_scratch(st, size_t(m + 1) * n * 4, 32));
+  int32_t* ints = static_cast<int32_t*>(stream_scratch(st, size_t(3) * m * 4, SLOT_MOE_IDS));
+  _Float16* ag = static_cast<_Float16*>(stream_scratch(st, size_t(m + 1) * kpad * 2, SLOT_MOE_ROWS16));
+  float* cg = static_cast<float*>(stream_scratch(st, size_t(m + 1) * n * 4, SLOT_MOE_PRODUCTS));
   if (!ints || !ag || !cg) return 1;
   int32_t *d_col = ints, *d_perm = ints + m, *d_valid = ints + 2 * size_t(m);
   hipLaunchKernelGGL(moe_ids_column_kernel, dim3((m + 255) / 256), dim3(256), 0, st, dIds, ids_stride, id, m, d_col);
@@ -653,9 +653,9 @@ static int moe_ffn_composition(const float* dA, int lda, int m, const int32_t* d
                                const ns_expert_group* gate, const ns_expert_group* up, const ns_expert_group* down, float* dOut, int ldo,
                                hipStream_t st) {
   const int ff = gate->experts[0]->n, dn = down->experts[0]->n;
-  float* t1 = static_cast<float*>(stream_scratch(st, size_t(m) * ff * 4, 35));
-  float* t2 = static_cast<float*>(stream_scratch(st, size_t(m) * ff * 4, 36));
-  float* t3 = static_cast<float*>(stream_scratch(st, size_t(m) * dn * 4, 37));
+  float* t1 = static_cast<float*>(stream_scratch(st, size_t(m) * ff * 4, SLOT_MOE_T1));
+  float* t2 = static_cast<float*>(stream_scratch(st, size_t(m) * ff * 4, SLOT_MOE_T2));
+  float* t3 = static_cast<float*>(stream_scratch(st, size_t(m) * dn * 4, SLOT_MOE_T3));
   if (!t1 || !t2 || !t3) {
     set_error("moe_ffn_silu: scratch allocation failed");
     return -1;
@@ -686,7 +686,7 @@ static int moe_ffn_fused(const float* dA, int lda, int m, const int32_t* dIds, i
   if (wg->kind == WK_F8 || wd->kind == WK_F8 || !wg->single_span || !wu->single_span || !wd->single_span || (ff & 3)) return 1;
   if (int64_t(m) * n_used >= 65536 / std::max(n_used, 1)) return 1;  // (pairs along grid.y, launch_gemv)
   // fp32 intermediate silu(gate) * up, [m][n_used][ff]: the down launches round it to fp16 while staging, like every fp32 activation row
-  float* inter = static_cast<float*>(stream_scratch(st, size_t(m) * n_used * ff * 4, 34));
+  float* inter = static_cast<float*>(stream_scratch(st, size_t(m) * n_used * ff * 4, SLOT_MOE_INTER));
   if (!inter) return 1;
   {
     MoeRoute route{gate->table, dIds, n_as};

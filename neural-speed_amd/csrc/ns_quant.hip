@@ -1024,7 +1024,7 @@ hipError_t launch_rope_qkv_append(float* q, const float* k, const float* v, void
   const auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   if (!no_tab && seq >= 16 && head_size % 8 == 0 && npairs % 4 == 0 && (!neox || (n_dims / 2) % 4 == 0) && c_sl % 8 == 0 && c_head % 8 == 0 &&
       al16(q) && al16(k) && al16(v) && al16(kc) && al16(vc)) {
-    float2* tab = static_cast<float2*>(stream_scratch(st, size_t(seq) * npairs * sizeof(float2), 23));
+    float2* tab = static_cast<float2*>(stream_scratch(st, size_t(seq) * npairs * sizeof(float2), SLOT_ROPE_TAB));
     if (tab) {
       const size_t nt = size_t(seq) * npairs;
       hipLaunchKernelGGL(rope_table_kernel, grid1d(nt, 256), dim3(256), 0, st, seq, n_past, int(npairs), neox ? 1 : 0, theta_scale,

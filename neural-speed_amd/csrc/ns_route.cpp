@@ -343,8 +343,8 @@ bool prepare_plan_device(const std::vector<PlanOp>& plan) {
     if (po.op.kind == RK_MHA) {
       const MhaView a{po.op};
       const size_t nsplit_max = size_t((a.n_ctx() + 127) / 128);
-      if (!stream_scratch(R.st, size_t(a.batch()) * a.seq() * a.heads() * nsplit_max * (2 + a.head_size()) * sizeof(float), 24)) return false;
-      if (!stream_scratch_zeroed(R.st, 65536 * 4, 25)) return false;  // the tickets of the merge inside the launch (ns_device.hip)
+      if (!stream_scratch(R.st, size_t(a.batch()) * a.seq() * a.heads() * nsplit_max * (2 + a.head_size()) * sizeof(float), SLOT_MHA_PARTIALS)) return false;
+      if (!stream_scratch_zeroed(R.st, 65536 * 4, SLOT_MHA_TICKETS)) return false;  // the tickets of the merge inside the launch (ns_device.hip)
       // ... and what the fp16-mirror form needs (ns_attn.cpp, moving context length)
       if (kv16_enabled() && !attn_prepare_moving(R.st, int(a.batch()), int(a.heads()), int(a.heads_kv()), int(a.head_size()), int(a.n_ctx()))) return false;
     }

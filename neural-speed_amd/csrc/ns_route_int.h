@@ -81,8 +81,6 @@ struct ExtraRead {
   const char* p = nullptr;
   size_t bytes = 0;
 };
-// per-stream scratch of a window's prompt-sized evaluation (ns_common.h stream_scratch slots)
-constexpr int kSlotNorm16 = 30, kSlotAttn16 = 31, kSlotFfn16 = 32, kSlotRopeTab = 33;
 
 // Every switch and tunable of the route.  env_knobs() (ns_route.cpp) reads the environment once; what can change while the process runs is
 // filled in per call.

@@ -16,6 +16,8 @@ for spec in "$@"; do
       ns_gemv_host) f=ns_gemv; src="-x hip ns_gemv_host.cpp" ;;
       ns_attn_decode|ns_attn_prefill) f=ns_attn ;;  # FILES=ns_attn: the attention kernels (ablation builds: NS_AS_ABL, NS_A2_ABL, NS_ATTN_U ...)
       ns_attn|ns_attn_plan) f=host ;;               # ... not their host code (.cpp, linked from the regular build)
+      ns_gemm2|ns_gemm3) f=ns_gemm ;;               # FILES=ns_gemm: the two prefill GEMM kernel files
+      ns_gemm|ns_gemm_plan|ns_scratch) f=host ;;    # ... not their host code
       ns_route|ns_route_fuse|ns_route_exec) f=host ;;  # the device route: host code
       ns_gemv_*_*) f=ns_gemv; IFS=_ read -r _ _ kind sps <<<"$b"; src="-DNS_GEMV_KIND=$kind -DNS_GEMV_SPS=$sps ns_gemv.hip" ;;
     esac
