@@ -227,9 +227,9 @@ hipError_t launch_gemm2(const SmallMArgs& a, hipStream_t st);
 // fills the buffer and has it read by launches it issues before it returns — the contents are dead between calls — and a buffer only
 // grows (a larger request waits for the stream before the old buffer is freed, or retires it when a graph may point at it).
 enum ScratchSlot : int {
-  SLOT_A16 = 0,               // fp16 copy of the activations: prefill GEMM (ns_gemm.cpp), ns_gemvs.hip, ns_dispatch.cpp (wide decode) — shared, see above
+  SLOT_A16 = 0,               // fp16 copy of the activations: prefill GEMM (ns_gemm.cpp), ns_gemvs.cpp, ns_dispatch.cpp (wide decode) — shared, see above
   SLOT_ATTN_PARTIALS = 1,     // ns_attn.cpp: (m, l, acc) partials of the context ranges
-  SLOT_SPLITK_PARTIALS = 2,   // split-K partial tiles: prefill GEMM (ns_gemm.cpp) and ns_gemvs.hip's slab — shared, see above
+  SLOT_SPLITK_PARTIALS = 2,   // split-K partial tiles: prefill GEMM (ns_gemm.cpp) and ns_gemvs.cpp's slab — shared, see above
   SLOT_GATHERED_A = 3,        // ns_dispatch.cpp: activations gathered by an act-order weight's shuffle
   SLOT_I8_GEMM_AQ = 4,        // ns_i8ref.hip: u8 activation codes + scales + zero points of the int8-reference GEMM
   SLOT_FFN_TMP1 = 5,          // ns_dispatch.cpp: act(gate) of an FFN whose caller gave no buffer
@@ -241,7 +241,7 @@ enum ScratchSlot : int {
   SLOT_KV_HOST_B = 11,
   SLOT_KV_HOST_C = 12,
   SLOT_KV_HOST_D = 13,
-  SLOT_GEMVS_TICKETS = 21,    // ns_gemvs.hip: split-K tickets (zeroed, self-resetting)
+  SLOT_GEMVS_TICKETS = 21,    // ns_gemvs.cpp: split-K tickets (zeroed, self-resetting)
   SLOT_ATTN_TICKETS = 22,     // ns_attn.cpp: merge tickets (zeroed, self-resetting)
   SLOT_ROPE_TAB = 23,         // ns_quant.hip: cos / sin table of launch_rope_qkv_append
   SLOT_MHA_PARTIALS = 24,     // ns_device.hip device-layout attention (allocated ahead of a capture by ns_route.cpp): partials
@@ -268,13 +268,15 @@ void gemm_scratch_release();  // frees every stream's scratch buffers
 // fp32 [m][lda] -> fp16 [m][ld16] (ld16 a multiple of 8, columns k..ld16-1 zero)
 hipError_t launch_cvt_a16(const float* a, void* out16, int m, int k, int lda, int ld16, hipStream_t st);
 // ns_gemv_host.cpp: second-generation decode kernel (m <= 16; gemv_kernel, ns_gemv.hip — compiled once per weight kind and scales-per-record
-// count, ns_gemv.h): lean prologue, one 16-column tile per workgroup; hipErrorNotSupported = outside its envelope (use smallm_kernel)
+// count, ns_gemv.h): lean prologue, one 16-column tile per workgroup; launched as gemv_plan (ns_gemv_plan.cpp) says; hipErrorNotSupported =
+// outside its envelope (use smallm_kernel)
 hipError_t launch_gemv(const SmallMArgs& a, hipStream_t st);
 void set_gemv_mode(int mode);  // 0 off (first-generation kernel), 1 on, -1 re-read NS_GEMV2
-// ns_gemvs.hip: small-batch / narrow-output decode kernel (2 .. 16 rows; activations staged once per workgroup and shared
-// by the tiles it streams, split-K across workgroups); hipErrorNotSupported = outside its envelope (use gemv_kernel)
+// ns_gemvs.cpp: small-batch / narrow-output decode kernel (gemvs_kernel, ns_gemvs.hip; 2 .. 16 rows; activations staged once per workgroup
+// and shared by the tiles it streams, split-K across workgroups); launched as gemvs_plan (ns_gemvs_plan.cpp) says; hipErrorNotSupported =
+// outside its envelope (use gemv_kernel)
 hipError_t launch_gemvs(const SmallMArgs& a, hipStream_t st);
-void set_gemvs_tuning(int what, int value);  // what: 0 mode (0 off, 1 from 2 rows, 2 from 1 row), 1 slices, 2 waves, 3 workgroups
+void set_gemvs_tuning(int what, int value);  // what: 0 mode (0 off, 1 by shape, 2 from 1 row, 3 from 2 rows), 1 slices, 2 waves, 3 workgroups, 4 f4 pair table, 5 finalize launch
 void set_attn_tuning(int wg_target, int min_keys);
 void set_attn_heads_first(int on);  // ns_attn.cpp: dispatch order of the decode attention's workgroups (AttnSplitParams::heads_first)
 void set_gemv_planes(int on);  // 1 (default): bit-plane formats stream their native records at decode (ns_weight::native); 0: the widened ones
@@ -308,7 +310,7 @@ bool gemm3_takes(const ns_weight* w);
 void set_gemm3_bm(int bm);  // ns_gemm.cpp: force gemm3_kernel's row-tile height (tests / A-B runs); 0 = automatic  // ns_attn.cpp: context-split rule of the decode attention kernel
 void set_decode_waves(int nw);  // 0 = by shape
 void set_gemv_rows1(int on);    // 1 (default): one-row launches of gemv_kernel take its one-row instantiation; 0: the general one (same bits)
-int decode_waves(int grid, int ks, bool dual);  // waves per workgroup of a decode launch (both kernel generations)
+int decode_waves(int grid, int ks, bool dual);  // waves per workgroup of a decode launch (both kernel generations; decode_waves_rule, ns_gemv_plan.cpp)
 void srow_rule(const ns_weight* w, int* num, int* den);          // ns_gemm_plan.cpp (host only): scale row of k-step s = s * num / den
 // the same rule as a branch-free (s * mul) >> shift, verified for every k-step; false = not expressible
 bool srow_params(const ns_weight* w, int* mul, int* shift);

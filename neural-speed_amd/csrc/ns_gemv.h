@@ -1,13 +1,16 @@
-// ns_gemv.h — interface between the host logic of the decode kernel (ns_gemv_host.cpp: launch_gemv, its tuning state) and the
-// translation units that hold gemv_kernel's instantiations (ns_gemv.hip, compiled once per weight kind and scales-per-record
-// count — NS_GEMV_SLICES below: the 1169 instantiations in one translation unit took thirteen minutes to compile).
-// Declarations only: the kernel, its device helpers and the launch ladder are in ns_gemv.hip.
+// ns_gemv.h — what the files of the decode kernel share.  ns_gemv.hip holds gemv_kernel, its device helpers and the launch ladder, compiled
+// once per weight kind and scales-per-record count (NS_GEMV_SLICES below: the 1169 instantiations in one translation unit took thirteen
+// minutes to compile).  Host: ns_gemv_plan.cpp decides a launch (gemv_plan: a pure function, checked on the CPU by tests/test_stream_plan.py),
+// ns_gemv_host.cpp holds the tuning state and launches what the plan says.  The last part is what BOTH weight-streaming kernels' plans
+// share (ns_gemvs.h: gemvs_kernel): the matrix table, the ring-slot size, the one-format rule.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 #include <cstdint>
+#include <string>
 
+#include "ns_common.h"
 #include "ns_dev.h"
 
 namespace ns {
@@ -138,6 +141,68 @@ constexpr int kGvModeMoe = 0x400;  // expert picked on the device (XV = 4; fp32 
 constexpr int kGvModePlanes = 0x800;  // native bit-plane records (PL = true)
 
 bool gemv_rows1();  // ns_gemv_host.cpp: the "gv_rows1" tuning value — launches of one row take the one-row form
+
+// ---- the launch decision as a value (ns_gemv_plan.cpp) --------------------------------------------------------------------------------------
+// Every switch the decision reads.  gemv_knobs() (ns_gemv_host.cpp) fills it from ns_hip_set_tuning's atomics and the environment.
+struct GemvKnobs {
+  int gemv2 = 1;            // "gemv2" / NS_GEMV2: 0 = every call is refused, the first-generation kernel serves
+  bool planes = true;       // "planes" / NS_GEMV_PLANES: bit-plane formats stream their native records
+  int forced_nw = 0;        // "gv_nw" / NS_GV_NW: 2 / 4 / 8 / 16 = that many waves per workgroup (diagnostics), else by shape
+  bool i8_inkernel = true;  // NS_I8_INKERNEL: int8-reference numerics quantize inside the launch where they can
+};
+// What a launch needs; nothing is decided after it.  p.out_ovf (when p.out_gamma is set) and p.trace are null: the launcher's.
+struct GemvPlan {
+  // hipSuccess: launch.  hipErrorNotSupported: outside the kernel's envelope, smallm_kernel serves the call; hipErrorNotReady: the caller runs
+  // the quantizer launch (i8_quantize_finish) and comes back; hipErrorInvalidValue: the call itself is wrong
+  hipError_t refusal = hipErrorNotSupported;
+  int kind = 0, sps = 0;  // the weight's slice (NS_GEMV_SLICES) ...
+  uint32_t scale_dt = 0;  // ... and the instantiation inside it
+  bool asym = false;
+  int mode_x = 0;         // GemvMode | kGvMode* bits
+  int grid = 0, grid_y = 1, nw = 0;
+  size_t lds = 0;         // dynamic LDS bytes: [A | carried sums or int8 scales at p.ssq_off | nw rings at p.ring_off]
+  GemvParams p;
+};
+// refused: *why says what the call lacks.  Pointers are only compared with null and looked at for their alignment.
+GemvPlan gemv_plan(const SmallMArgs& a, const GemvKnobs& knobs, std::string* why);
+// waves per workgroup of a decode launch by shape; forced: GemvKnobs::forced_nw.  decode_waves (ns_common.h) asks with the live value
+int decode_waves_rule(int grid, int ks, bool dual, int forced);
+
+// ---- shared by gemv_plan and gemvs_plan (ns_gemvs.h) ------------------------------------------------------------------------------------------
+// the matrices of a launch as both kernels address them: one base per matrix, 32-bit offsets of its scales and zero points, its first tile
+struct StreamTable {
+  GemvMat mat[3];
+  const uint8_t* wb[3] = {nullptr, nullptr, nullptr};
+  uint32_t soff[3] = {0, 0, 0}, zoff[3] = {0, 0, 0};
+  uint32_t tbeg[3] = {0, 0xffffffffu, 0xffffffffu};  // absent matrices begin beyond every tile
+  uint32_t tiles = 0;                                // tile units of the launch (gate/up: tile pairs)
+};
+// pick: the layout of a weight that is streamed (launch_gemv: its native bit-plane clone).  false: a matrix is not one allocation below 2 GiB
+template <class Pick>
+inline bool stream_table(const SmallMArgs& a, Pick pick, StreamTable* t) {
+  for (int i = 0; i < a.nseg; i++) {
+    const ns_weight* w = pick(a.seg[i].w);
+    if (!w->single_span || w->alloc_bytes >= (size_t(1) << 31)) return false;
+    t->wb[i] = reinterpret_cast<const uint8_t*>(w->codes);
+    t->soff[i] = uint32_t(reinterpret_cast<const uint8_t*>(w->scales) - t->wb[i]);
+    t->zoff[i] = w->zps ? uint32_t(reinterpret_cast<const uint8_t*>(w->zps) - t->wb[i]) : 0u;
+    t->tbeg[i] = a.dual ? 0u : t->tiles;
+    if (!a.dual || i == 0) t->tiles += uint32_t(w->ntiles);
+    t->mat[i] = GemvMat{t->wb[i], t->soff[i], t->zoff[i], t->tbeg[i], w->n, a.seg[i].c, static_cast<_Float16*>(a.seg[i].c16)};
+  }
+  return true;
+}
+// bytes of one ring slot: a k-step's code record with its scales and zero points behind it
+inline uint32_t record_slot_bytes(const ns_weight* w) {
+  const uint32_t sbytes = uint32_t(w->sps) * (w->scale_dt == DT_F32 ? 4u : 2u);
+  return 1024u + 16u * sbytes + (w->asym ? 16u * uint32_t(w->sps) : 0u);
+}
+// the matrices of a fused launch share one format and one record layout, so that one set of strides serves all of them
+inline bool same_stream_layout(const ns_weight* w, const ns_weight* w0) {
+  return w->kind == w0->kind && w->sps == w0->sps && w->scale_dt == w0->scale_dt && w->asym == w0->asym && w->k == w0->k &&
+         w->ksteps == w0->ksteps && w->qstride == w0->qstride && w->sstride == w0->sstride && w->zstride == w0->zstride &&
+         w->srows == w0->srows && w->blocksize == w0->blocksize;
+}
 
 // One object per slice X(weight kind, scales per record), each with its own device code object.  Per slice:
 //   launch_gemv_<KIND>_<SPS>: launches the instantiation for (scale type, sym / asym, mode bits) on a prepared GemvParams;

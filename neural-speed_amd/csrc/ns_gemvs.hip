@@ -36,96 +36,24 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <cstddef>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <utility>
-#include <array>
-#include <map>
-#include <mutex>
-#include <vector>
 
 #include "../../include/ns_bestla.h"
 #include "ns_common.h"
 #include "ns_dev.h"
+#include "ns_gemvs.h"
 #include "ns_launch.h"
 
 namespace ns {
 
-#ifndef NS_GVS_PF
-#define NS_GVS_PF 2
-#endif
 // diagnostic builds (scripts/build_variants.sh): 1 = no code -> fp16 conversion (raw bits as operands), 2 = no activation
 // fragment reads, 3 = records are waited for and refilled but not read or multiplied (the structure's streaming rate)
 #ifndef NS_GVS_ABL
 #define NS_GVS_ABL 0
 #endif
-constexpr int kGsPF = NS_GVS_PF;        // records each streaming wave keeps in flight (with up to 15 waves per CU; deeper
-                                        // rings measured no faster from 12 waves on and cost LDS, profiles/r04b_ablation.txt)
-constexpr int kGsR = 2;                 // reduction slots (tiles whose partial sums may be pending in LDS)
-constexpr int kGsMaxRows = 16;
-constexpr int kGsMaxNS = 15;            // streaming waves (+ the service wave = 16 waves = 1024 threads)
-constexpr size_t kGsMaxLds = 160 * 1024;
-constexpr uint32_t kGsCtlBytes = 32;    // LDS control words: cnt[kGsR] at 0, done at 16
-constexpr uint32_t kGsTblBytes = 32 * 1024;  // f4 pair table: 256 entries x 32 bank copies x 4 B, at LDS offset 0
-constexpr uint32_t kGsSpinLimit = 1u << 22;  // polls of an LDS word before a wave gives up (about 0.2 s)
-
-struct GvsMat {
-  const uint8_t* wbase;  // ONE allocation: records at 0, scales at s_off, zero points at z_off
-  uint32_t s_off, z_off;
-  uint32_t tile_begin;
-  int n;
-  float* c;
-  _Float16* c16;
-};
-
-struct GvsParams {
-  // ---- hot: the prologue's words ----
-  const uint8_t* wb0;
-  const uint8_t* wb1;
-  const uint8_t* wb2;
-  const void* a;            // activations, fp16 [m][lda]
-  uint32_t so0, so1, so2;   // scale offsets of the matrices
-  uint32_t zo0, zo1, zo2;   // zero-point offsets (asymmetric only)
-  uint32_t ks;              // k-steps per tile (whole K)
-  uint32_t ksl;             // k-steps per slice
-  uint32_t s_log2;          // log2(slices): workgroup b streams slice b & (S - 1) of tile group b >> s_log2
-  uint32_t qstride, sstride, zstride;
-  uint32_t srows, srow_mul, srow_shift;
-  uint32_t tb1, tb2;        // first tile of matrices 1 and 2 of a fused QKV launch (2^32 - 1: absent)
-  uint32_t ntiles;          // tile units of the launch (dual: tile pairs)
-  uint32_t tg_count;        // tile groups = workgroups per slice; group t streams tiles t, t + tg_count, ...
-  uint32_t tiles_base, tiles_rem;  // ntiles = tiles_base * tg_count + tiles_rem
-  uint32_t ns;              // streaming waves
-  int m, k, lda;
-  uint32_t row_stride;      // halves per staged row
-  uint32_t ctl_off, red_off, ring_off, ring_stride;
-  uint32_t red_wave, red_slot;  // bytes of partial sums per wave / per slot
-  uint32_t a_off;           // LDS offset of the staged activations (behind the f4 pair table when there is one)
-  uint32_t a_bytes;         // bytes of the staged activations (rows x row_stride halves)
-  uint32_t lut16[8];        // f4: the 16 table values as fp16, two per word
-  const void* tbl_img;      // f4: the 32 KB pair table as a device image (round 5: fetched by LDS-DMA beside the activations instead of
-                            // ~1.4 us of VALU per launch); nullptr: the waves build it (the image did not exist yet at capture time)
-  // ---- cold ----
-  GvsMat mat[3];
-  float* c2;
-  const float* d;
-  int ldc, ldd, epilogue;
-  float* slab;              // split-K: [slice][tile unit][q][64 lanes][4] fp32 partial sums
-  uint32_t* tickets;        // split-K finished inside the launch: one counter per tile unit (zero between launches); nullptr:
-                            // the partial sums are added by gemvs_finalize_kernel
-  uint32_t slab_bytes;
-  F4Lut lut;
-  F8Consts f8;
 #ifdef NS_TRACE
-  unsigned long long* trace;
-#endif
-};
-#ifdef NS_TRACE
-unsigned long long* trace_buffer();
 #define NS_SSTAMP(i)                                                                                     \
   do {                                                                                                   \
     __builtin_amdgcn_sched_barrier(0);                                                                   \
@@ -146,39 +74,6 @@ __device__ __forceinline__ GvsKArgs gvs_late_args() {
 template <int N>
 __device__ __forceinline__ void gvs_wait_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-enum GvsMode { GS_PLAIN = 0, GS_DUAL = 1, GS_MSEG = 2 };
-
-// ---- f4 pair-table images (host side): entry e = {value[e & 15], value[e >> 4]} as two fp16, 32 bank copies each — what build_table
-//      writes.  One image per value table (NF4 / FP4-BNB / FP4-E2M1), created on the first launch that wants it OUTSIDE a stream
-//      capture (an allocation + a synchronous copy); a launch that finds none gets nullptr and builds the table with its waves ----
-static std::mutex g_tbl_mu;
-static std::map<std::array<uint16_t, 16>, void*> g_tbl_img;
-static const void* gvs_f4_table_image(const _Float16* lut, hipStream_t st) {
-  static const bool off = getenv("NS_GVS_TABLE_DMA") && atoi(getenv("NS_GVS_TABLE_DMA")) == 0;  // A-B runs
-  if (off) return nullptr;
-  std::array<uint16_t, 16> key;
-  for (int i = 0; i < 16; i++) key[i] = __builtin_bit_cast(uint16_t, lut[i]);
-  std::lock_guard<std::mutex> lk(g_tbl_mu);
-  auto it = g_tbl_img.find(key);
-  if (it != g_tbl_img.end()) return it->second;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
-    (void)hipGetLastError();
-    return nullptr;
-  }
-  std::vector<uint32_t> img(kGsTblBytes / 4);
-  for (uint32_t e = 0; e < 256; e++)
-    for (uint32_t c = 0; c < 32; c++) img[e * 32 + c] = uint32_t(key[e & 15]) | (uint32_t(key[e >> 4]) << 16);
-  void* d = nullptr;
-  if (hipMalloc(&d, kGsTblBytes) != hipSuccess || hipMemcpy(d, img.data(), kGsTblBytes, hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipGetLastError();
-    if (d) (void)hipFree(d);
-    return nullptr;  // (not cached: tried again next time)
-  }
-  g_tbl_img.emplace(key, d);
-  return d;
 }
 
 // epilogue of one tile: lane (nn, g) holds rows 4g .. 4g+3 of column `col` (custom::epilogue::*, bestla_f32f32_forward;
@@ -770,16 +665,6 @@ __global__ __launch_bounds__(1024) void gemvs_kernel(const GvsParams p) {
 }
 
 // split-K, second pass: one wave per tile unit adds the slices' partial sums in slice order and applies the epilogue
-struct GvsFinParams {
-  const float* slab;
-  uint32_t slices, ntiles, nq;
-  uint32_t tb1, tb2;
-  int m;
-  GvsMat mat[3];
-  float* c2;
-  const float* d;
-  int ldc, ldd, epilogue;
-};
 template <int MODE>
 __global__ __launch_bounds__(256) void gemvs_finalize_kernel(const GvsFinParams p) {
   constexpr bool DUAL = MODE == GS_DUAL, MSEG = MODE == GS_MSEG;
@@ -816,284 +701,26 @@ __global__ __launch_bounds__(256) void gemvs_finalize_kernel(const GvsFinParams 
   gvs_epilogue<DUAL>(sum, p.m, col, col_ok, g, mp.c, mp.c16, p.ldc, dvp, p.c2, p.epilogue);
 }
 
-// ============================================================================================================
-// host side
-// ============================================================================================================
-template <int KIND, int SPS, int SK, bool ASYM>
-static hipError_t launch_gvs_k(const GvsParams& p, int mode, int grid, int nwaves, size_t lds, hipStream_t st) {
-  const dim3 g(grid), b(nwaves * 64);
-  if (mode == GS_DUAL) return launch_lds<gemvs_kernel<KIND, SPS, SK, ASYM, GS_DUAL>>(int(kGsMaxLds), g, b, lds, st, p);
-  if (mode == GS_MSEG) return launch_lds<gemvs_kernel<KIND, SPS, SK, ASYM, GS_MSEG>>(int(kGsMaxLds), g, b, lds, st, p);
-  return launch_lds<gemvs_kernel<KIND, SPS, SK, ASYM, GS_PLAIN>>(int(kGsMaxLds), g, b, lds, st, p);
-}
-
-// tuning / diagnostics (ns_hip_set_tuning): "gvs" 0 = off, 1 = from 2 rows (default), 2 = from 1 row;
-// "gvs_slices" / "gvs_waves" / "gvs_grid" force the decomposition (0 = by shape)
-static std::atomic<int> g_gvs_mode{-1};
-static std::atomic<int> g_gvs_slices{-1}, g_gvs_waves{-1}, g_gvs_grid{-1}, g_gvs_tbl{-2}, g_gvs_fin{-1};
-static int env_or(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
-void set_gemvs_tuning(int what, int value) {
-  (what == 0 ? g_gvs_mode : what == 1 ? g_gvs_slices : what == 2 ? g_gvs_waves : what == 3 ? g_gvs_grid : what == 4 ? g_gvs_tbl : g_gvs_fin).store(value);
-}
-static int gvs_knob(std::atomic<int>& k, const char* env, int dflt) {
-  int v = k.load();
-  if (v < (dflt < 0 ? -1 : 0)) {
-    v = env_or(env, dflt);
-    k.store(v);
-  }
-  return v;
-}
-static int gvs_cus() {
-  static const int cus = [] {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-    return prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }();
-  return cus;
-}
-
-struct GvsPlan {
-  int slices_log2 = 0, ns = 8, tg = 0;
-  size_t a_bytes = 0, lds = 0;
-  bool tbl = false;
-  uint32_t ksl = 0, row_stride = 0, red_wave = 0, red_slot = 0, ring_stride = 0;
-  double cost = 0;
-};
-
-// hipErrorNotSupported: outside the kernel's envelope or not the better decomposition — the caller goes on to gemv_kernel
-hipError_t launch_gemvs(const SmallMArgs& a, hipStream_t st) {
-  const int mode_knob = gvs_knob(g_gvs_mode, "NS_GVS", 1);  // 0 off, 1 by shape (below), 2 always from one row, 3 always from two rows
-  if (mode_knob == 0 || a.m < (mode_knob == 2 ? 1 : 2) || a.m > kGsMaxRows) return hipErrorNotSupported;
-  if (a.link || a.rope || a.i8 || a.moe) return hipErrorNotSupported;  // carried norm / fused RoPE / int8-reference numerics: gemv_kernel
-  const ns_weight* w0 = a.seg[0].w;
-  const int nmat = a.nseg;
-  if (nmat < 1 || nmat > 3 || (a.dual && nmat != 2)) return hipErrorNotSupported;
-  // fp16 activations with 16-byte aligned rows; several rows need K to fill whole k-steps (a row's padding columns
-  // would otherwise read the next row through the descriptor).  A caller without the fp16 shadow (the reference's device
-  // graph hands over fp32 tensors) gets one conversion pass into scratch first (round to nearest even, what the shadow's
-  // producers do: bit-identical results either way, tests/test_gpu_fullsize.py)
-  const int kstep = w0->kstep_len;
-  const bool shadow = a.a16 != nullptr;
-  if (shadow ? ((a.lda & 7) || (reinterpret_cast<uintptr_t>(a.a16) & 15)) : (a.a == nullptr)) return hipErrorNotSupported;
-  if ((w0->k & 7) || (a.m > 1 && w0->k % kstep != 0)) return hipErrorNotSupported;
-  const int lda16 = shadow ? a.lda : w0->k;
-  if (uint64_t(a.m) * uint64_t(lda16) * 2 >= (uint64_t(1) << 30)) return hipErrorNotSupported;
-
-  GvsParams p;
-  memset(&p, 0, sizeof(p));
-  uint32_t tiles = 0;
-  uint32_t tbeg[3] = {0, 0xffffffffu, 0xffffffffu};
-  const uint8_t* wb[3] = {nullptr, nullptr, nullptr};
-  uint32_t soff[3] = {0, 0, 0}, zoff[3] = {0, 0, 0};
-  for (int i = 0; i < nmat; i++) {
-    const ns_weight* w = a.seg[i].w;
-    if (!w->single_span || w->alloc_bytes >= (size_t(1) << 31)) return hipErrorNotSupported;
-    if (w->kind != w0->kind || w->sps != w0->sps || w->scale_dt != w0->scale_dt || w->asym != w0->asym || w->k != w0->k ||
-        w->ksteps != w0->ksteps || w->qstride != w0->qstride || w->sstride != w0->sstride || w->zstride != w0->zstride ||
-        w->srows != w0->srows || w->blocksize != w0->blocksize)
-      return hipErrorNotSupported;
-    if (a.dual && w->ntiles != w0->ntiles) return hipErrorNotSupported;
-    wb[i] = reinterpret_cast<const uint8_t*>(w->codes);
-    soff[i] = uint32_t(reinterpret_cast<const uint8_t*>(w->scales) - wb[i]);
-    zoff[i] = w->zps ? uint32_t(reinterpret_cast<const uint8_t*>(w->zps) - wb[i]) : 0u;
-    tbeg[i] = a.dual ? 0u : tiles;
-    if (!a.dual || i == 0) tiles += uint32_t(w->ntiles);
-    p.mat[i] = GvsMat{wb[i], soff[i], zoff[i], tbeg[i], w->n, a.seg[i].c, static_cast<_Float16*>(a.seg[i].c16)};
-  }
-  const bool mseg = !a.dual && nmat > 1;
-  const int mode = a.dual ? GS_DUAL : (mseg ? GS_MSEG : GS_PLAIN);
-  const uint32_t ks = uint32_t(w0->ksteps);
-  if (tiles == 0 || ks == 0) return hipErrorNotSupported;
-
-  const int rows = a.m;
-  const int rows_q = (rows + 3) / 4;
-  const int nq = a.dual ? 2 : 1;
-  if (mode_knob == 1) {
-    // which kernel by shape (profiles/r04n_rows.txt, us, one-tile-per-workgroup gemv_kernel -> this kernel).  This kernel's time
-    // hardly depends on the row count, gemv_kernel's grows with the activations every tile stages; gemv_kernel's prologue is
-    // about 0.7 us leaner, so short launches of a few rows stay there:
-    //   4096 x 4096 int4      2 rows 5.6 -> 6.2    6 rows 6.1 -> 6.8    12 rows 8.5 -> 7.4   16 rows 9.0 -> 7.4
-    //   gate/up 11008 int4    2 rows 13.5 -> 15.2  4 rows 15.3 -> 16.2  6 rows 19.0 -> 16.7  12 rows 20.2 -> 17.6
-    //   gate/up 14336 nf4     2 rows 22.7 -> 20.8  6 rows 27.4 -> 21.4  16 rows 39.2 -> 28.7
-    //   4096 x 11008 int4     2 rows 8.7 -> 9.0    3 rows 11.5 -> 9.3 (66 KB of activations: beyond gemv_kernel)   16 rows 24.8 -> 14.3
-    const bool beyond_gemv = size_t(rows) * (size_t(ks) * kstep + 8) * 2 > 64 * 1024;  // gemv_kernel's activation envelope
-    const bool wide = a.dual || tiles >= 512;
-    const bool f4_wide = w0->kind == WK_F4 && wide;
-    if (!(beyond_gemv || f4_wide || (rows >= 5 && wide) || rows >= 9)) return hipErrorNotSupported;
-  }
-  const uint32_t sbytes = uint32_t(w0->sps) * (w0->scale_dt == DT_F32 ? 4u : 2u);
-  const uint32_t slot = 1024u + 16u * sbytes + (w0->asym ? 16u * uint32_t(w0->sps) : 0u);
-  const int cus = gvs_cus();
-  const int force_s = gvs_knob(g_gvs_slices, "NS_GVS_SLICES", 0);
-  const int force_ns = gvs_knob(g_gvs_waves, "NS_GVS_WAVES", 0);
-  const int force_grid = gvs_knob(g_gvs_grid, "NS_GVS_GRID", 0);
-  const int force_tbl = gvs_knob(g_gvs_tbl, "NS_GVS_TABLE", -1);  // f4 pair table: -1 by size, 0 never, 1 always
-  const int max_wg = force_grid > 0 ? force_grid : cus;
-
-  // ---- the decomposition: slices S (power of two), tile groups, streaming waves ----
-  // cost of a candidate, in bytes a workgroup moves (the launch ends with its slowest workgroup): its weight records +
-  // half its activation slice (L2, about twice the HBM stream's rate per CU) + what the finalize launch of a split costs
-  auto plan_for = [&](int s_log2, GvsPlan* out) -> bool {
-    const uint32_t S = 1u << s_log2;
-    if (S > ks || int(S) > max_wg) return false;
-    GvsPlan pl;
-    pl.slices_log2 = s_log2;
-    pl.ksl = (ks + S - 1) / S;
-    if (uint64_t(pl.ksl) * (S - 1) >= ks) return false;  // an empty last slice
-    pl.row_stride = pl.ksl * uint32_t(kstep) + 8;
-    pl.a_bytes = (size_t(rows) * pl.row_stride * 2 + 15) & ~size_t(15);
-    pl.tg = int(std::min<uint32_t>(tiles, uint32_t(max_wg) / S));
-    if (pl.tg < 1) return false;
-    // f4: the pair table (32 KB of LDS, ~1.5 us to build and to shuffle the activations for) pays from about a hundred
-    // records per workgroup on (4096 x 4096 at 8 rows, 32 records: 8.6 us with it, 8.1 without; 4096 x 14336 in 4 slices, 112
-    // records: 16.4 vs 17.8; fused gate/up 14336, 256 records: 22.9 vs 27.9 — profiles/r04h_ablation.txt, r04y_table_threshold.txt)
-    const uint32_t tiles_max0 = (tiles + uint32_t(pl.tg) - 1) / uint32_t(pl.tg);
-    const bool use_tbl = w0->kind == WK_F4 && force_tbl != 0 && (force_tbl > 0 || uint64_t(tiles_max0) * pl.ksl * nq >= 96u);
-    pl.tbl = use_tbl;
-    const size_t tbl = use_tbl ? size_t(kGsTblBytes) : 0;
-    pl.red_wave = uint32_t(nq) * uint32_t(rows_q) * 256u;
-    // streaming waves: as many as LDS holds and the workgroup has units for (units are dealt round-robin: any count
-    // balances); the time of a workgroup ~ its units / waves, padded when there are fewer units than waves
-    const uint32_t tiles_max = (tiles + uint32_t(pl.tg) - 1) / uint32_t(pl.tg);
-    auto ring_of = [&](int ns) {
-      const size_t items = (size_t(pl.ksl) * tiles_max + ns - 1) / ns * nq;
-      return (std::min<size_t>(items, size_t(kGsPF)) * slot + 15) & ~size_t(15);
-    };
-    int best_ns = 0;
-    for (int ns = kGsMaxNS; ns >= 1; ns--) {
-      if (force_ns > 0 && ns != std::min(force_ns, kGsMaxNS)) continue;
-      if (force_ns <= 0 && uint32_t(ns) > std::max<uint32_t>(1u, pl.ksl * tiles_max)) continue;
-      const size_t need = tbl + pl.a_bytes + kGsCtlBytes + size_t(kGsR) * ns * pl.red_wave + size_t(ns) * ring_of(ns);
-      if (need > kGsMaxLds) continue;
-      best_ns = ns;
-      break;
-    }
-    const double best_t = best_ns ? double(pl.ksl) * (1.0 + 0.5 * std::max(0, 12 - best_ns) / 12.0) : 0.0;
-    if (best_ns == 0) return false;
-    pl.ns = best_ns;
-    pl.ring_stride = uint32_t(ring_of(pl.ns));
-    pl.red_slot = uint32_t(pl.ns) * pl.red_wave;
-    pl.lds = tbl + pl.a_bytes + kGsCtlBytes + size_t(kGsR) * pl.red_slot + size_t(pl.ns) * pl.ring_stride;
-    // + a fixed cost per tile of a workgroup (flush, reduction, epilogue or slab store: about 8 KB of streaming each: the service wave needs ~0.8 us per tile)
-    pl.cost = double(tiles_max) * (best_t * nq * slot + 8e3) + 0.5 * double(pl.a_bytes) + (S > 1 ? 75e3 : 0.0);
-    *out = pl;
-    return true;
-  };
-  GvsPlan best;
-  bool have = false;
-  for (int s_log2 = 0; s_log2 <= 5; s_log2++) {
-    if (force_s > 0 && (1 << s_log2) != force_s) continue;
-    GvsPlan pl;
-    if (!plan_for(s_log2, &pl)) continue;
-    if (!have || pl.cost < best.cost) best = pl, have = true;
-  }
-  if (!have) return hipErrorNotSupported;
-  const uint32_t S = 1u << best.slices_log2;
-
-  float* slab = nullptr;
-  uint32_t* tickets = nullptr;
-  const size_t slab_bytes = size_t(S) * tiles * nq * 256 * sizeof(float);
-  if (S > 1) {
-    if (slab_bytes >= (size_t(1) << 31)) return hipErrorNotSupported;
-    slab = static_cast<float*>(stream_scratch(st, slab_bytes, SLOT_SPLITK_PARTIALS));
-    if (!slab) return hipErrorNotSupported;
-    // Who adds the slices: a second launch (gemvs_finalize_kernel, the default) or — "gvs_finalize" 0 — the tile's owner inside
-    // the launch, behind one self-resetting ticket per tile unit.  Measured equal (profiles/r04u_split_k_finish.txt: 4096 x 14336
-    // at 8 rows 17.1 vs 17.3 us with 2 slices, 17.8 vs 17.8 with 4): what the in-launch finish saves in launch boundary the owner
-    // spends reading the other slices past the caches; it also needs every workgroup of the launch resident at once (an owner
-    // spins on tickets other workgroups draw), which a second launch does not — hence the default.
-    static const int kTicketCap = 1 << 16;
-    const int force_fin = gvs_knob(g_gvs_fin, "NS_GVS_FINALIZE", 1);
-    if (!force_fin && tiles <= uint32_t(kTicketCap)) tickets = static_cast<uint32_t*>(stream_scratch_zeroed(st, size_t(kTicketCap) * 4, SLOT_GEMVS_TICKETS));
-  }
-
-  const void* a16 = a.a16;
-  if (!shadow) {
-    void* sc = stream_scratch(st, size_t(a.m) * w0->k * 2, SLOT_A16);
-    if (!sc) return hipErrorNotSupported;
-    const hipError_t ce = launch_cvt_a16(a.a, sc, a.m, w0->k, a.lda, w0->k, st);
-    if (ce != hipSuccess) return ce;
-    a16 = sc;
-  }
-  p.wb0 = wb[0], p.wb1 = wb[1], p.wb2 = wb[2];
-  p.a = a16;
-  p.so0 = soff[0], p.so1 = soff[1], p.so2 = soff[2];
-  p.zo0 = zoff[0], p.zo1 = zoff[1], p.zo2 = zoff[2];
-  p.ks = ks;
-  p.ksl = best.ksl;
-  p.s_log2 = uint32_t(best.slices_log2);
-  p.qstride = w0->qstride, p.sstride = w0->sstride, p.zstride = w0->zstride;
-  p.srows = uint32_t(w0->srows);
-  {
-    int mul, shift;
-    if (!srow_params(w0, &mul, &shift)) return hipErrorNotSupported;
-    p.srow_mul = uint32_t(mul), p.srow_shift = uint32_t(shift);
-  }
-  p.tb1 = mseg ? tbeg[1] : 0xffffffffu;
-  p.tb2 = (mseg && nmat > 2) ? tbeg[2] : 0xffffffffu;
-  p.ntiles = tiles;
-  p.tg_count = uint32_t(best.tg);
-  p.tiles_base = tiles / uint32_t(best.tg);
-  p.tiles_rem = tiles % uint32_t(best.tg);
-  p.ns = uint32_t(best.ns);
-  p.m = a.m, p.k = w0->k, p.lda = lda16;
-  p.row_stride = best.row_stride;
-  p.a_off = best.tbl ? kGsTblBytes : 0u;
-  p.a_bytes = uint32_t(best.a_bytes);
-  p.ctl_off = p.a_off + uint32_t(best.a_bytes);
-  p.red_off = p.ctl_off + kGsCtlBytes;
-  p.ring_off = p.red_off + uint32_t(kGsR) * best.red_slot;
-  p.ring_stride = best.ring_stride;
-  p.red_wave = best.red_wave, p.red_slot = best.red_slot;
-  p.c2 = a.c2, p.d = a.d, p.ldc = a.ldc, p.ldd = a.ldd, p.epilogue = a.epilogue;
-  p.slab = slab;
-  p.tickets = tickets;
-  p.slab_bytes = uint32_t(slab_bytes);
-  if (w0->kind == WK_F4) {
-    f4_lut_planes(w0->lut, &p.lut);
-    for (int i = 0; i < 8; i++)
-      p.lut16[i] = uint32_t(__builtin_bit_cast(unsigned short, w0->lut[2 * i])) | (uint32_t(__builtin_bit_cast(unsigned short, w0->lut[2 * i + 1])) << 16);
-    p.tbl_img = best.tbl ? gvs_f4_table_image(w0->lut, st) : nullptr;
-  }
-  p.f8 = f8_consts(w0->qtype);
-#ifdef NS_TRACE
-  p.trace = trace_buffer();
-#endif
-  const size_t lds = best.lds;
-  if (lds > kGsMaxLds) return hipErrorNotSupported;
-  const int grid = best.tg * int(S);
-  const int nwaves = best.ns + 1;
-  static const bool dbg = getenv("NS_GVS_DEBUG") != nullptr;
-  if (dbg)
-    fprintf(stderr, "gemvs: m %d tiles %u ks %u mode %d -> slices %u (ksl %u) groups %d waves %d lds %zu (A %zu) cost %.0f\n", a.m, tiles, ks,
-            mode, S, best.ksl, best.tg, best.ns, lds, best.a_bytes, best.cost);
-  if (dbg && w0->kind == WK_F4) fprintf(stderr, "gemvs: f4 pair table %s\n", best.tbl ? "on" : "off");
-
-  const hipError_t e = with_format(w0->kind, w0->sps, w0->scale_dt, w0->asym, [&](auto kind_c, auto sps_c, auto sk_c, auto asym_c) {
-    return launch_gvs_k<kind_c, sps_c, sk_c, asym_c>(p, mode, grid, nwaves, lds, st);
+// ---- the two launches of a plan (ns_gemvs.cpp) ----
+hipError_t launch_gemvs_plan(const GvsPlan& pl, hipStream_t st) {
+  const dim3 g(pl.grid), b(pl.nwaves * 64);
+  return with_format(pl.kind, pl.sps, pl.scale_dt, pl.asym, [&](auto kind_c, auto sps_c, auto sk_c, auto asym_c) {
+    if (pl.mode == GS_DUAL) return launch_lds<gemvs_kernel<kind_c, sps_c, sk_c, asym_c, GS_DUAL>>(int(kGsMaxLds), g, b, pl.lds, st, pl.p);
+    if (pl.mode == GS_MSEG) return launch_lds<gemvs_kernel<kind_c, sps_c, sk_c, asym_c, GS_MSEG>>(int(kGsMaxLds), g, b, pl.lds, st, pl.p);
+    return launch_lds<gemvs_kernel<kind_c, sps_c, sk_c, asym_c, GS_PLAIN>>(int(kGsMaxLds), g, b, pl.lds, st, pl.p);
   });
-  if (e != hipSuccess || S == 1 || tickets) return e;
+}
 
-  GvsFinParams f;
-  memset(&f, 0, sizeof(f));
-  f.slab = slab;
-  f.slices = S, f.ntiles = tiles, f.nq = uint32_t(nq);
-  f.tb1 = p.tb1, f.tb2 = p.tb2;
-  f.m = a.m;
-  for (int i = 0; i < 3; i++) f.mat[i] = p.mat[i];
-  f.c2 = a.c2, f.d = a.d, f.ldc = a.ldc, f.ldd = a.ldd, f.epilogue = a.epilogue;
-  const dim3 fg((tiles + 3) / 4), fb(256);
-  if (mode == GS_DUAL)
-    hipLaunchKernelGGL(gemvs_finalize_kernel<GS_DUAL>, fg, fb, 0, st, f);
-  else if (mode == GS_MSEG)
-    hipLaunchKernelGGL(gemvs_finalize_kernel<GS_MSEG>, fg, fb, 0, st, f);
+hipError_t launch_gemvs_finalize(const GvsPlan& pl, hipStream_t st) {
+  const dim3 fg((pl.f.ntiles + 3) / 4), fb(256);
+  if (pl.mode == GS_DUAL)
+    hipLaunchKernelGGL(gemvs_finalize_kernel<GS_DUAL>, fg, fb, 0, st, pl.f);
+  else if (pl.mode == GS_MSEG)
+    hipLaunchKernelGGL(gemvs_finalize_kernel<GS_MSEG>, fg, fb, 0, st, pl.f);
   else
-    hipLaunchKernelGGL(gemvs_finalize_kernel<GS_PLAIN>, fg, fb, 0, st, f);
+    hipLaunchKernelGGL(gemvs_finalize_kernel<GS_PLAIN>, fg, fb, 0, st, pl.f);
   return hipGetLastError();
 }
+
 
 }  // namespace ns

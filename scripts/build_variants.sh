@@ -13,7 +13,9 @@ for spec in "$@"; do
   for o in $all_objs; do
     b=${o%.o}; f=$b; src="$b.hip"
     case $b in
-      ns_gemv_host) f=ns_gemv; src="-x hip ns_gemv_host.cpp" ;;
+      ns_gemv_host|ns_gemv_plan) f=ns_gemv; src="-x hip $b.cpp" ;;  # (the host files see the kernels' parameter structs: same flags)
+      ns_gemvs_k) f=ns_gemvs; src="ns_gemvs.hip" ;;                  # FILES=ns_gemvs: gemvs_kernel ...
+      ns_gemvs|ns_gemvs_plan) f=ns_gemvs; src="-x hip $b.cpp" ;;     # ... and its host files
       ns_attn_decode|ns_attn_prefill) f=ns_attn ;;  # FILES=ns_attn: the attention kernels (ablation builds: NS_AS_ABL, NS_A2_ABL, NS_ATTN_U ...)
       ns_attn|ns_attn_plan) f=host ;;               # ... not their host code (.cpp, linked from the regular build)
       ns_gemm2|ns_gemm3) f=ns_gemm ;;               # FILES=ns_gemm: the two prefill GEMM kernel files

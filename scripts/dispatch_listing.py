@@ -27,8 +27,9 @@ if "--trace" in sys.argv:
             if cur is not None:
                 print("%03d %s" % (idx, " | ".join(cur)))
             idx, cur = idx + 1, []
-        elif cur is not None:  # name, grid in work-items, LDS bytes of a workgroup
-            cur.append("%s grid %s,%s,%s lds %s" % (n, r.get("Grid_Size_X"), r.get("Grid_Size_Y"), r.get("Grid_Size_Z"), r.get("LDS_Block_Size")))
+        elif cur is not None:  # name, grid and workgroup in work-items (the workgroup tells the wave count), LDS bytes of a workgroup
+            cur.append("%s grid %s,%s,%s wg %s,%s,%s lds %s" % (n, r.get("Grid_Size_X"), r.get("Grid_Size_Y"), r.get("Grid_Size_Z"), r.get("Workgroup_Size_X"),
+                                                                r.get("Workgroup_Size_Y"), r.get("Workgroup_Size_Z"), r.get("LDS_Block_Size")))
     if cur is not None:
         print("%03d %s" % (idx, " | ".join(cur)))
     sys.exit(0)
