@@ -244,6 +244,10 @@ int ns_hip_get_compute_mode(void);
  *                     GEMM per expert (0 = default: NS_MOE_GROUPED_ROWS in the environment, else 32; negative = never)
  *   "moe_ffn_fused"   ns_hip_moe_ffn_silu: 0 = every call takes the composition (three ns_hip_mul_mat_id calls per selection + the weighted
  *                     sum), 1 = the fused launches inside their envelope, -1 = back to the default (1)
+ *   "moe_ffn_grouped_rows" ns_hip_moe_ffn_silu / _gelu: token rows from which a call outside a capture takes the grouped pass - all (row,
+ *                     selection) pairs sorted by expert on the host, one gather, one fused gate / up and one down GEMM per populated expert, one
+ *                     weighted combine (0 = default, the same as "moe_grouped_rows": NS_MOE_GROUPED_ROWS in the environment, else 32;
+ *                     negative = never: the composition serves such calls)
  * Returns 0, or -1 for an unknown key. */
 int ns_hip_set_tuning(const char* key, int value);
 /* Loads the code objects of the hot kernels (tiled GEMM, decode GEMV, attention, the operators between them) for the current device now instead of at the
@@ -684,11 +688,34 @@ void ns_hip_moe_stats(uint64_t out[4]);
  * launches refuse - is the composition: three ns_hip_mul_mat_id calls per selection and a weighted sum; the entry serves every shape
  * ns_hip_mul_mat_id serves.  The intermediate results live in per-stream scratch.  Asynchronous on `stream`, capturable; a replayed
  * graph follows the ids and weights in device memory.  ns_hip_set_tuning("moe_ffn_fused", 0) keeps every call on the composition.
- * ns_hip_moe_ffn_stats (process-wide sums): [0] calls served by the fused launches, [1] calls served by the composition, [2] launches
- * issued for the calls of [0], [3] reserved (0). */
+ * Prompt size - the grouped pass: from "moe_ffn_grouped_rows" rows (default 32), outside a stream capture, with experts other than fp8,
+ * gate / up groups of one format and d, ff multiples of 64, the ids come back to the host ONCE (m x n_used ints, one synchronisation), the
+ * (row, selection) pairs are sorted by expert, one launch gathers their rows as fp16 in group order, every populated expert gets one fused
+ * gate / up launch of the tiled GEMM (act(gate) * up formed in registers, fp16 intermediate only) and one down launch, and one launch
+ * forms dOut[t] = sum_i w[t][i] * y[pair (t, i)] in selection order, starting from the first good selection's product.  Not capturable;
+ * whatever it refuses is refused before dOut is written, and the composition serves the call.
+ * ns_hip_moe_ffn_stats (process-wide sums): [0] calls served by the fused launches, [1] calls served by the composition (a call that tried
+ * the fused launches or the grouped pass and fell back counts here only), [2] launches issued for the calls of [0], [3] calls served by
+ * the grouped pass.
+ *
+ * ns_hip_moe_ffn_gelu — the same block with gelu(gate) * up: n_used x { ne_mul_id_ffn_gelu ; mul(weights) ; add } of the reference's Grok
+ * graph (models/grok/grok.cpp:292-343, ne_layers.c:8113 / :8170).  The GeLU is the tanh form of every NS_EPI_GELU epilogue here
+ * (kernel_ref.h:1570-1572), which is what the reference's fused node computes.  Same arguments, same contract, same three paths and
+ * the same counters as ns_hip_moe_ffn_silu; an id outside the groups contributes zero (gelu(0) * up = 0).
+ *
+ * ns_hip_moe_route_f — ns_hip_moe_route with flags.  flags = 0: ns_hip_moe_route bit for bit (that entry calls this one).
+ * NS_MOE_ROUTE_RAW_WEIGHTS: dWeights[t * w_stride + i] = p[selected i], the fp32 soft_max value itself - no sum, no division: the Grok
+ * graph's router, whose sum_rows / repeat / div nodes are commented out (grok.cpp:293-299).  Ids, probabilities, selection order, the tie
+ * rule, the -inf handling and capturability are those of flags = 0.  Any other bit: -1, nothing written. */
+#define NS_MOE_ROUTE_RAW_WEIGHTS 1
 int ns_hip_moe_route(const float* dLogits, int ld_logits, int m, int n_expert, int n_used, int32_t* dIds, int ids_stride,
                      float* dWeights, int w_stride, float* dProbs, void* stream);
+int ns_hip_moe_route_f(const float* dLogits, int ld_logits, int m, int n_expert, int n_used, int32_t* dIds, int ids_stride,
+                       float* dWeights, int w_stride, float* dProbs, int flags, void* stream);
 int ns_hip_moe_ffn_silu(const float* dA, int lda, int m, const int32_t* dIds, int ids_stride, const float* dWeights, int w_stride,
+                        int n_used, const ns_expert_group* gate, const ns_expert_group* up, const ns_expert_group* down,
+                        float* dOut, int ldo, void* stream);
+int ns_hip_moe_ffn_gelu(const float* dA, int lda, int m, const int32_t* dIds, int ids_stride, const float* dWeights, int w_stride,
                         int n_used, const ns_expert_group* gate, const ns_expert_group* up, const ns_expert_group* down,
                         float* dOut, int ldo, void* stream);
 void ns_hip_moe_ffn_stats(uint64_t out[4]);

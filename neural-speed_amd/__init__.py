@@ -31,6 +31,7 @@ INT_TYPES = {b: b | (1 << 8) for b in range(1, 9)}
 COMP_UNDEF, COMP_F32, COMP_BF16, COMP_F16, COMP_INT8 = range(5)
 # enum ns_epilogue
 EPI_NONE, EPI_ADD, EPI_MUL, EPI_ADD_GELU, EPI_GELU, EPI_SILU = range(6)
+MOE_ROUTE_RAW_WEIGHTS = 1  # ns_hip_moe_route_f: the weights are the selected soft_max values themselves
 CORE_AUTO = -1
 # ne_attn_flags_t (neural_speed/core/ne_layers.h:65-72)
 ATTN_CAUSAL, ATTN_ALIBI8, ATTN_PREFER_FP32, ATTN_TANH30 = 1, 2, 4, 8
@@ -176,6 +177,8 @@ def lib():
         L.ns_hip_moe_stats.argtypes = [vp]
         L.ns_hip_moe_route.argtypes = [vp, i, i, i, i, vp, i, vp, i, vp, vp]
         L.ns_hip_moe_ffn_silu.argtypes = [vp, i, i, vp, i, vp, i, i, vp, vp, vp, vp, i, vp]
+        L.ns_hip_moe_route_f.argtypes = [vp, i, i, i, i, vp, i, vp, i, vp, i, vp]
+        L.ns_hip_moe_ffn_gelu.argtypes = L.ns_hip_moe_ffn_silu.argtypes
         L.ns_hip_moe_ffn_stats.restype = None
         L.ns_hip_moe_ffn_stats.argtypes = [vp]
         L.ns_hip_p2p_create.restype = vp

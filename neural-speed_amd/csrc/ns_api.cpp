@@ -103,7 +103,8 @@ const TuningKey kTuning[] = {
     // row thresholds of ns_hip_mul_mat_id's paths; 0 = default, < 0 = off
     {"moe_gemv_rows", [](int v) { set_moe_tuning(0, v); }},
     {"moe_grouped_rows", [](int v) { set_moe_tuning(1, v); }},
-    {"moe_ffn_fused", set_moe_ffn_fused},  // ns_hip_moe_ffn_silu: 0 = always the composition, 1 / -1 = the fused launches inside their envelope
+    {"moe_ffn_grouped_rows", set_moe_ffn_grouped_rows},  // ns_hip_moe_ffn_silu / _gelu: rows from which the grouped pass serves a call (0 = default, < 0 = never)
+    {"moe_ffn_fused", set_moe_ffn_fused},  // ns_hip_moe_ffn_silu / _gelu: 0 = always the composition, 1 / -1 = the fused launches inside their envelope
     {"g3_min_m", set_gemm3_min_m},
     {"i8_tile", set_i8_tile},
     {"i8_mfma", set_i8_mfma_gen},

@@ -261,6 +261,10 @@ enum ScratchSlot : int {
   SLOT_MOE_T1 = 35,           // ... and its composition's three temporaries
   SLOT_MOE_T2 = 36,
   SLOT_MOE_T3 = 37,
+  SLOT_MOE_PAIR_INTS = 38,    // ns_moe.hip, the grouped pass of the block entries: gathered position -> source row, pair -> position
+  SLOT_MOE_PAIR_ROWS16 = 39,  // ... the pairs' activation rows in group order, fp16 [pairs + 1][k]
+  SLOT_MOE_PAIR_INTER16 = 40, // ... act(gate) * up of every pair, fp16 [pairs + 1][ff]
+  SLOT_MOE_PAIR_Y = 41,       // ... the down products, fp32 [pairs + 1][d_out]
 };
 void* stream_scratch(hipStream_t st, size_t bytes, int slot);
 void* stream_scratch_zeroed(hipStream_t st, size_t bytes, int slot);  // zero-filled when (re)allocated: self-resetting counters
@@ -296,6 +300,7 @@ void kv_mirrors_clear();  // ns_kvcache.hip: drops the device mirrors of library
 void set_i8_tile(int tile);     // ns_i8ref.hip: workgroup tile of i8mfma2_kernel (0 = by size)
 void set_i8_mfma_gen(int gen);  // ns_i8ref.hip: 2 = i8mfma2_kernel for nibble containers (default), 1 = i8mfma_kernel everywhere
 void set_moe_tuning(int what, int value);  // ns_moe.hip: row threshold of what = 0 the decode kernel (m <= value), 1 the grouped path (m >= value); 0 = default, < 0 = off
+void set_moe_ffn_grouped_rows(int rows);  // ns_moe.hip: rows from which the block entries take the grouped pass; 0 = default ("moe_grouped_rows"'s), < 0 = never
 void set_moe_ffn_fused(int on);  // ns_moe.hip: ns_hip_moe_ffn_silu takes 1 the fused launches inside their envelope, 0 always the composition, -1 the default
 // ns_moe.hip: the router's fp16 exponential table (ns_hip_moe_route) on the current device, built on the host and uploaded at the first call
 // (an expert group's creation, ns_hip_warm_up, a route call outside a stream capture); nullptr + error string when it cannot be made.

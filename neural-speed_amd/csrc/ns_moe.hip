@@ -18,7 +18,9 @@
 // Around that operator, the rest of a Mixtral-style layer's MoE block (docs/kernels/other.md, "MoE decode block"): ns_hip_moe_route, the
 // router's soft_max -> top_k -> weights tail in one launch (moe_route_kernel), and ns_hip_moe_ffn_silu, the expert feed-forward block of all
 // rows and selections in 1 + n_used launches of the decode kernel (ns_gemv.hip, XV = 4) or, outside their envelope, as the composition of
-// ns_hip_mul_mat_id calls with moe_weighted_add_kernel.
+// ns_hip_mul_mat_id calls with moe_weighted_add_kernel.  At prompt size the block is ONE grouped pass over all (row, selection) pairs
+// (moe_ffn_grouped: ns_moe_plan.cpp lays the pairs out, moe_pair_gather_kernel and moe_pair_combine_kernel around the tiled GEMM's launches);
+// ns_hip_moe_ffn_gelu is the same block with gelu(gate) * up, ns_hip_moe_route_f the router with the un-normalised weights of the Grok graph.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -34,6 +36,7 @@
 #include "ns_api_int.h"
 #include "ns_common.h"
 #include "ns_dev.h"
+#include "ns_moe_plan.h"
 
 namespace ns {
 namespace {
@@ -238,7 +241,7 @@ __global__ __launch_bounds__(kMoeThreads) void moe_gemv_kernel(const MoeParams p
 constexpr int kRouteWaves = 4;
 __global__ __launch_bounds__(kRouteWaves * 64) void moe_route_kernel(const float* __restrict__ logits, int ld, int m, int n_expert, int n_used,
                                                                      const uint16_t* __restrict__ exp_table, int32_t* __restrict__ ids, int ids_stride,
-                                                                     float* __restrict__ weights, int w_stride, float* __restrict__ probs) {
+                                                                     float* __restrict__ weights, int w_stride, float* __restrict__ probs, int raw) {
   const int row = blockIdx.x * kRouteWaves + int(threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= m) return;  // (wave-uniform)
   const bool on = lane < n_expert;
@@ -284,7 +287,7 @@ __global__ __launch_bounds__(kRouteWaves * 64) void moe_route_kernel(const float
   const float wsf = float(wsum);
   if (lane < n_used) {
     ids[size_t(row) * ids_stride + lane] = my_id;
-    weights[size_t(row) * w_stride + lane] = __fdiv_rn(my_p, wsf);
+    weights[size_t(row) * w_stride + lane] = raw ? my_p : __fdiv_rn(my_p, wsf);  // (raw: grok.cpp:293-299, no sum_rows / div)
   }
 }
 
@@ -298,6 +301,80 @@ __global__ void moe_weighted_add_kernel(float* __restrict__ out, int ldo, const 
   const float v = (w ? w[size_t(t) * w_stride] : 1.f) * x[size_t(t) * ldx + col];
   float* o = out + size_t(t) * ldo + col;
   *o = first ? v : *o + v;
+}
+
+// ---- the block's grouped pass (moe_ffn_grouped): the two memory-bound launches around the tiled GEMM's ----------------------------------------
+// gather: fp32 token rows -> fp16 rows [rows][k] in group order (MoePairPlan::src_row; a row selected twice is written twice, src_row < 0 is
+// the padding row: zeros).  One thread per 8 columns (k is a multiple of 64): two 16-byte loads where lda and the base allow (vec), one
+// 16-byte store.
+__global__ void moe_pair_gather_kernel(const float* __restrict__ a, int lda, const int32_t* __restrict__ src_row, int rows, int k, int vec,
+                                       _Float16* __restrict__ out) {
+  const size_t gid = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  const int per_row = k / 8;
+  if (gid >= size_t(rows) * per_row) return;
+  const int j = int(gid / per_row), c = int(gid % per_row) * 8;
+  const int t = src_row[j];
+  typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+  h8 v;
+  if (t < 0) {
+#pragma unroll
+    for (int e = 0; e < 8; e++) v[e] = (_Float16)0.f;
+  } else {
+    const float* src = a + size_t(t) * lda + c;
+    float x[8];
+    if (vec) {
+      const float4 x0 = *reinterpret_cast<const float4*>(src), x1 = *reinterpret_cast<const float4*>(src + 4);
+      x[0] = x0.x, x[1] = x0.y, x[2] = x0.z, x[3] = x0.w, x[4] = x1.x, x[5] = x1.y, x[6] = x1.z, x[7] = x1.w;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; e++) x[e] = src[e];
+    }
+#pragma unroll
+    for (int e = 0; e < 8; e++) v[e] = (_Float16)x[e];
+  }
+  *reinterpret_cast<h8*>(out + size_t(j) * k + c) = v;
+}
+// combine: out[t] = sum_i w[t][i] * y[pos(t, i)] — each product rounded, then added, in selection order, starting from the first good
+// selection's product (no FMA: the sum does not depend on how the compiler contracts it); pos < 0 (an id outside the groups) contributes
+// nothing, a row without a good selection is 0.0f.  One thread per 4 columns of a token row: 16-byte loads of y when n is a multiple of 4,
+// 16-byte stores when ldo and the base allow as well (vec_out); nothing is written beyond column n.
+__global__ void moe_pair_combine_kernel(const float* __restrict__ y, const int32_t* __restrict__ pos, const float* __restrict__ w, int w_stride, int m,
+                                        int n_used, int n, float* __restrict__ out, int ldo, int vec_out) {
+  const size_t gid = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  const int per_row = (n + 3) / 4;
+  if (gid >= size_t(m) * per_row) return;
+  const int t = int(gid / per_row), c = int(gid % per_row) * 4;
+  const bool full = (n & 3) == 0;  // (then c + 3 < n and every row of y starts on a 16-byte boundary)
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  bool first = true;
+  for (int i = 0; i < n_used; i++) {
+    const int j = pos[size_t(t) * n_used + i];
+    if (j < 0) continue;
+    const float wv = w ? w[size_t(t) * w_stride + i] : 1.f;
+    const float* yr = y + size_t(j) * n + c;
+    float x[4];
+    if (full) {
+      const float4 v = *reinterpret_cast<const float4*>(yr);
+      x[0] = v.x, x[1] = v.y, x[2] = v.z, x[3] = v.w;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; e++) x[e] = c + e < n ? yr[e] : 0.f;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      const float v = __fmul_rn(wv, x[e]);
+      acc[e] = first ? v : __fadd_rn(acc[e], v);
+    }
+    first = false;
+  }
+  float* o = out + size_t(t) * ldo + c;
+  if (full && vec_out) {
+    *reinterpret_cast<float4*>(o) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; e++)
+      if (c + e < n) o[e] = acc[e];
+  }
 }
 
 }  // namespace
@@ -318,9 +395,12 @@ void set_moe_tuning(int what, int value) { (what == 0 ? g_moe_gemv_rows : g_moe_
 // calls served by [0] the grouped path, [1] the decode kernel, [2] the loop kernel; [3] grouped attempts that returned "not taken" (ns_hip_moe_stats)
 static std::atomic<uint64_t> g_moe_stats[4];
 
-// ns_hip_moe_ffn_silu: "moe_ffn_fused" (-1 = default: on) and its counters (ns_hip_moe_ffn_stats)
+// ns_hip_moe_ffn_silu / _gelu: "moe_ffn_fused" (-1 = default: on), "moe_ffn_grouped_rows" (0 = NS_MOE_GROUPED_ROWS if set, else 32; negative =
+// never) and the counters (ns_hip_moe_ffn_stats)
 static std::atomic<int> g_moe_ffn_fused{-1};
 void set_moe_ffn_fused(int on) { g_moe_ffn_fused.store(on < 0 ? -1 : (on != 0)); }
+static std::atomic<int> g_moe_ffn_grouped_rows{0};
+void set_moe_ffn_grouped_rows(int rows) { g_moe_ffn_grouped_rows.store(rows); }
 static std::atomic<uint64_t> g_moe_ffn_stats[4];
 
 // the router's exponential table: table_exp_f16 of the reference (ne_layers.c:745), fp16(expf(fp16 -> fp32(code))) for every code, made by
@@ -620,7 +700,16 @@ void ns_hip_moe_stats(uint64_t out[4]) {
 
 int ns_hip_moe_route(const float* dLogits, int ld_logits, int m, int n_expert, int n_used, int32_t* dIds, int ids_stride, float* dWeights,
                      int w_stride, float* dProbs, void* stream) {
+  return ns_hip_moe_route_f(dLogits, ld_logits, m, n_expert, n_used, dIds, ids_stride, dWeights, w_stride, dProbs, 0, stream);
+}
+
+int ns_hip_moe_route_f(const float* dLogits, int ld_logits, int m, int n_expert, int n_used, int32_t* dIds, int ids_stride, float* dWeights,
+                       int w_stride, float* dProbs, int flags, void* stream) {
   if (!have_device()) return -1;
+  if (flags & ~NS_MOE_ROUTE_RAW_WEIGHTS) {
+    set_error("moe_route: unknown flag bits (NS_MOE_ROUTE_RAW_WEIGHTS is the only flag)");
+    return -1;
+  }
   if (n_used < 1 || n_used > 8 || n_expert < n_used || n_expert > 64 || m < 1) {
     set_error("moe_route: need 1 <= n_used <= 8, n_used <= n_expert <= 64 and at least one row");
     return -1;
@@ -639,7 +728,7 @@ int ns_hip_moe_route(const float* dLogits, int ld_logits, int m, int n_expert, i
     return -1;
   }
   hipLaunchKernelGGL(moe_route_kernel, dim3(unsigned((m + kRouteWaves - 1) / kRouteWaves)), dim3(kRouteWaves * 64), 0, st, dLogits, ld_logits, m,
-                     n_expert, n_used, table, dIds, ids_stride, dWeights, w_stride, dProbs);
+                     n_expert, n_used, table, dIds, ids_stride, dWeights, w_stride, dProbs, (flags & NS_MOE_ROUTE_RAW_WEIGHTS) ? 1 : 0);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     set_error(std::string("moe_route launch: ") + hipGetErrorString(e));
@@ -648,20 +737,23 @@ int ns_hip_moe_route(const float* dLogits, int ld_logits, int m, int n_expert, i
   return 0;
 }
 
-// the composition: per selection three ns_hip_mul_mat_id calls (gate with SiLU, up with Mul, down) and the weighted sum
+// the entry's name in error texts, by activation
+static const char* moe_ffn_name(int act) { return act == NS_EPI_GELU ? "moe_ffn_gelu" : "moe_ffn_silu"; }
+
+// the composition: per selection three ns_hip_mul_mat_id calls (gate with the activation, up with Mul, down) and the weighted sum
 static int moe_ffn_composition(const float* dA, int lda, int m, const int32_t* dIds, int ids_stride, const float* dWeights, int w_stride, int n_used,
                                const ns_expert_group* gate, const ns_expert_group* up, const ns_expert_group* down, float* dOut, int ldo,
-                               hipStream_t st) {
+                               int act, hipStream_t st) {
   const int ff = gate->experts[0]->n, dn = down->experts[0]->n;
   float* t1 = static_cast<float*>(stream_scratch(st, size_t(m) * ff * 4, SLOT_MOE_T1));
   float* t2 = static_cast<float*>(stream_scratch(st, size_t(m) * ff * 4, SLOT_MOE_T2));
   float* t3 = static_cast<float*>(stream_scratch(st, size_t(m) * dn * 4, SLOT_MOE_T3));
   if (!t1 || !t2 || !t3) {
-    set_error("moe_ffn_silu: scratch allocation failed");
+    set_error(std::string(moe_ffn_name(act)) + ": scratch allocation failed");
     return -1;
   }
   for (int i = 0; i < n_used; i++) {
-    if (ns_hip_mul_mat_id(dA, dIds, ids_stride, i, gate, t1, m, lda, ff, NS_EPI_SILU, nullptr, 0, st) != 0 ||
+    if (ns_hip_mul_mat_id(dA, dIds, ids_stride, i, gate, t1, m, lda, ff, act, nullptr, 0, st) != 0 ||
         ns_hip_mul_mat_id(dA, dIds, ids_stride, i, up, t2, m, lda, ff, NS_EPI_MUL, t1, ff, st) != 0 ||
         ns_hip_mul_mat_id(t2, dIds, ids_stride, i, down, t3, m, ff, dn, NS_EPI_NONE, nullptr, 0, st) != 0)
       return -1;
@@ -670,7 +762,7 @@ static int moe_ffn_composition(const float* dA, int lda, int m, const int32_t* d
                        dWeights ? dWeights + i : nullptr, w_stride, m, dn, i == 0 ? 1 : 0);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
-      set_error(std::string("moe_ffn_silu (weighted sum): ") + hipGetErrorString(e));
+      set_error(std::string(moe_ffn_name(act)) + " (weighted sum): " + hipGetErrorString(e));
       return -1;
     }
   }
@@ -680,12 +772,13 @@ static int moe_ffn_composition(const float* dA, int lda, int m, const int32_t* d
 
 // the fused launches: 0 = done, -1 = error, 1 = not taken (nothing written to dOut yet: the composition serves the call)
 static int moe_ffn_fused(const float* dA, int lda, int m, const int32_t* dIds, int ids_stride, const float* dWeights, int w_stride, int n_used,
-                         const ns_expert_group* gate, const ns_expert_group* up, const ns_expert_group* down, float* dOut, int ldo, hipStream_t st) {
+                         const ns_expert_group* gate, const ns_expert_group* up, const ns_expert_group* down, float* dOut, int ldo, int act,
+                         hipStream_t st) {
   const ns_weight *wg = gate->experts[0], *wu = up->experts[0], *wd = down->experts[0];
   const int ff = wg->n, n_as = int(gate->experts.size());
   if (wg->kind == WK_F8 || wd->kind == WK_F8 || !wg->single_span || !wu->single_span || !wd->single_span || (ff & 3)) return 1;
   if (int64_t(m) * n_used >= 65536 / std::max(n_used, 1)) return 1;  // (pairs along grid.y, launch_gemv)
-  // fp32 intermediate silu(gate) * up, [m][n_used][ff]: the down launches round it to fp16 while staging, like every fp32 activation row
+  // fp32 intermediate act(gate) * up, [m][n_used][ff]: the down launches round it to fp16 while staging, like every fp32 activation row
   float* inter = static_cast<float*>(stream_scratch(st, size_t(m) * n_used * ff * 4, SLOT_MOE_INTER));
   if (!inter) return 1;
   {
@@ -697,12 +790,12 @@ static int moe_ffn_fused(const float* dA, int lda, int m, const int32_t* dIds, i
     a.a = dA, a.lda = lda, a.m = 1, a.ldc = ff, a.nseg = 2;
     a.seg[0] = {wg, inter, nullptr};
     a.seg[1] = {wu, nullptr, nullptr};
-    a.epilogue = NS_EPI_SILU, a.dual = true;
+    a.epilogue = act, a.dual = true;  // (GV_DUAL's epilogue picks SiLU or GeLU from this run-time value)
     a.moe = &route;
     const hipError_t e = launch_gemv(a, st);
     if (e == hipErrorNotSupported) return 1;
     if (e != hipSuccess) {
-      set_error(std::string("moe_ffn_silu (gate / up launch): ") + hipGetErrorString(e));
+      set_error(std::string(moe_ffn_name(act)) + " (gate / up launch): " + hipGetErrorString(e));
       return -1;
     }
   }
@@ -722,7 +815,7 @@ static int moe_ffn_fused(const float* dA, int lda, int m, const int32_t* dIds, i
       return 1;
     }
     if (e != hipSuccess) {
-      set_error(std::string("moe_ffn_silu (down launch): ") + hipGetErrorString(e));
+      set_error(std::string(moe_ffn_name(act)) + " (down launch): " + hipGetErrorString(e));
       return -1;
     }
   }
@@ -731,17 +824,104 @@ static int moe_ffn_fused(const float* dA, int lda, int m, const int32_t* dIds, i
   return 0;
 }
 
-int ns_hip_moe_ffn_silu(const float* dA, int lda, int m, const int32_t* dIds, int ids_stride, const float* dWeights, int w_stride, int n_used,
-                        const ns_expert_group* gate, const ns_expert_group* up, const ns_expert_group* down, float* dOut, int ldo, void* stream) {
+// the grouped pass (prompt size, never captured): 0 = done, -1 = error, 1 = not taken.  dOut is written by the last launch alone, so whatever is
+// refused on the way — a format, a shape, a GEMM launch after others went out — leaves the whole call to the composition.
+// One host read-back of the ids; ns_moe_plan.cpp sorts the (row, selection) pairs by expert; one gather into fp16 rows in group order; per
+// populated expert, in ascending order (MoePairPlan::launch_rows), one gate / up pair launch of the tiled GEMM — act(gate) * up in registers,
+// fp16 out only — and one down launch on that fp16 intermediate; one combine.  Against the composition's n_used x 3 grouped mul_mat_id
+// calls: one read-back instead of n_used x 3, groups of n_used x the rows, no fp32 [m][ff] intermediate, no scatter, one weighted sum.
+static int moe_ffn_grouped(const float* dA, int lda, int m, const int32_t* dIds, int ids_stride, const float* dWeights, int w_stride, int n_used,
+                           const ns_expert_group* gate, const ns_expert_group* up, const ns_expert_group* down, float* dOut, int ldo, int act,
+                           hipStream_t st) {
+  const ns_weight *wg = gate->experts[0], *wu = up->experts[0], *wd = down->experts[0];
+  const int k = wg->k, ff = wg->n, dn = wd->n, n_as = int(gate->experts.size());
+  if (wg->kind == WK_F8 || wu->kind == WK_F8 || wd->kind == WK_F8) return 1;  // (fp8 experts: the composition)
+  if ((k % 64) != 0 || (ff % 64) != 0) return 1;
+  if (wu->kind != wg->kind || wu->qtype != wg->qtype || wu->blocksize != wg->blocksize || wu->scale_dt != wg->scale_dt || wu->asym != wg->asym ||
+      wu->qstride != wg->qstride || wu->sstride != wg->sstride || wu->zstride != wg->zstride)
+    return 1;  // (a gate / up pair launch needs one format)
+  const std::string name = moe_ffn_name(act);
+  // the ids, once: rows of ids_stride ints, the last one n_used long
+  std::vector<int32_t> ids(size_t(m - 1) * ids_stride + n_used);
+  if (hipMemcpyAsync(ids.data(), dIds, ids.size() * 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+    (void)hipGetLastError();
+    set_error(name + " (grouped): reading the expert ids failed");
+    return -1;
+  }
+  MoePairPlan pl;
+  if (!moe_pair_plan(ids.data(), ids_stride, m, n_used, n_as, &pl)) return 1;
+  const size_t rows = size_t(pl.pairs) + 1, n_pos = size_t(m) * n_used;  // (+ 1: the padding row behind a last group of one row)
+  if (rows * size_t(std::max(k, std::max(ff, dn))) >= (size_t(1) << 31)) return 1;
+  int32_t* ints = static_cast<int32_t*>(stream_scratch(st, (rows + n_pos) * 4, SLOT_MOE_PAIR_INTS));
+  _Float16* ag = static_cast<_Float16*>(stream_scratch(st, rows * k * 2, SLOT_MOE_PAIR_ROWS16));
+  _Float16* inter = static_cast<_Float16*>(stream_scratch(st, rows * ff * 2, SLOT_MOE_PAIR_INTER16));
+  float* y = static_cast<float*>(stream_scratch(st, rows * dn * 4, SLOT_MOE_PAIR_Y));
+  if (!ints || !ag || !inter || !y) return 1;
+  int32_t *d_src = ints, *d_pos = ints + rows;
+  // one upload of both tables; the stream is idle (the read-back above), so waiting for it here costs the copy alone and the host vectors
+  // may die with this frame while the launches below are still running
+  std::vector<int32_t> tables(pl.src_row);
+  tables.insert(tables.end(), pl.pos.begin(), pl.pos.end());
+  if (hipMemcpyAsync(ints, tables.data(), tables.size() * 4, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+    (void)hipGetLastError();
+    set_error(name + " (grouped): uploading the pair layout failed");
+    return -1;
+  }
+  {
+    const size_t units = rows * (k / 8);
+    const int vec = (lda & 3) == 0 && (reinterpret_cast<uintptr_t>(dA) & 15) == 0;
+    hipLaunchKernelGGL(moe_pair_gather_kernel, dim3(unsigned((units + 255) / 256)), dim3(256), 0, st, dA, lda, d_src, int(rows), k, vec, ag);
+  }
+  for (int e = 0; e < n_as; e++) {
+    const int r = pl.launch_rows[e];
+    if (!r) continue;
+    const size_t off = size_t(pl.offset[e]);
+    SmallMArgs gu{};
+    gu.a = nullptr, gu.a16 = ag + off * k, gu.lda = k, gu.m = r, gu.ldc = ff, gu.nseg = 2;
+    gu.seg[0] = {gate->experts[e], nullptr, inter + off * ff};
+    gu.seg[1] = {up->experts[e], nullptr, nullptr};
+    gu.epilogue = act, gu.dual = true, gu.c2 = nullptr;
+    SmallMArgs dw{};
+    dw.a = nullptr, dw.a16 = inter + off * ff, dw.lda = ff, dw.m = r, dw.ldc = dn, dw.nseg = 1;
+    dw.seg[0] = {down->experts[e], y + off * dn, nullptr};
+    dw.epilogue = NS_EPI_NONE;
+    hipError_t er = launch_gemm2(gu, st);
+    if (er == hipSuccess) er = launch_gemm2(dw, st);
+    if (er == hipErrorNotSupported) return 1;  // (dOut is untouched)
+    if (er != hipSuccess) {
+      set_error(name + " (grouped): " + hipGetErrorString(er));
+      return -1;
+    }
+  }
+  {
+    const size_t units = size_t(m) * ((dn + 3) / 4);
+    const int vec_out = (ldo & 3) == 0 && (reinterpret_cast<uintptr_t>(dOut) & 15) == 0;
+    hipLaunchKernelGGL(moe_pair_combine_kernel, dim3(unsigned((units + 255) / 256)), dim3(256), 0, st, y, d_pos, dWeights, w_stride, m, n_used, dn,
+                       dOut, ldo, vec_out);
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    set_error(name + " (grouped): " + hipGetErrorString(e));
+    return -1;
+  }
+  g_moe_ffn_stats[3]++;
+  return 0;
+}
+
+// the block of both activations: by row count the fused decode launches, the grouped pass, else — and wherever those refuse — the composition
+static int moe_ffn_block(const float* dA, int lda, int m, const int32_t* dIds, int ids_stride, const float* dWeights, int w_stride, int n_used,
+                         const ns_expert_group* gate, const ns_expert_group* up, const ns_expert_group* down, float* dOut, int ldo, int act,
+                         void* stream) {
   if (!have_device()) return -1;
+  const std::string name = moe_ffn_name(act);
   if (!dA || !dIds || !gate || !up || !down || !dOut || m < 1 || m > 65535 || n_used < 1 || n_used > ids_stride || (dWeights && w_stride < n_used)) {
-    set_error("moe_ffn_silu: bad argument");
+    set_error(name + ": bad argument");
     return -1;
   }
   const ns_weight *wg = gate->experts[0], *wu = up->experts[0], *wd = down->experts[0];
   if (wu->n != wg->n || wu->k != wg->k || wd->k != wg->n || gate->experts.size() != up->experts.size() || gate->experts.size() != down->experts.size() ||
       lda < wg->k || ldo < wd->n) {
-    set_error("moe_ffn_silu: the gate, up and down groups do not form one feed-forward block (shapes, expert counts), or a row stride is too short");
+    set_error(name + ": the gate, up and down groups do not form one feed-forward block (shapes, expert counts), or a row stride is too short");
     return -1;
   }
   hipStream_t st = (hipStream_t)stream;
@@ -749,10 +929,34 @@ int ns_hip_moe_ffn_silu(const float* dA, int lda, int m, const int32_t* dIds, in
   const int gemv_set = g_moe_gemv_rows.load();
   const int moe_gemv_rows = gemv_set ? gemv_set : gemv_env;
   if (g_moe_ffn_fused.load() != 0 && m <= moe_gemv_rows) {
-    const int rc = moe_ffn_fused(dA, lda, m, dIds, ids_stride, dWeights, w_stride, n_used, gate, up, down, dOut, ldo, st);
+    const int rc = moe_ffn_fused(dA, lda, m, dIds, ids_stride, dWeights, w_stride, n_used, gate, up, down, dOut, ldo, act, st);
     if (rc <= 0) return rc;
   }
-  return moe_ffn_composition(dA, lda, m, dIds, ids_stride, dWeights, w_stride, n_used, gate, up, down, dOut, ldo, st);
+  // prompt size, outside a capture (the host reads the ids): the grouped pass.  The default threshold is ns_hip_mul_mat_id's grouped one:
+  // from there on the composition synchronises with the host as well
+  static const int grouped_env = getenv("NS_MOE_GROUPED_ROWS") ? atoi(getenv("NS_MOE_GROUPED_ROWS")) : 32;
+  const int grouped_set = g_moe_ffn_grouped_rows.load();
+  const int grouped_from = grouped_set ? grouped_set : grouped_env;
+  if (grouped_from > 0 && m >= grouped_from) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    const bool capturing = hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+    (void)hipGetLastError();
+    if (!capturing) {
+      const int rc = moe_ffn_grouped(dA, lda, m, dIds, ids_stride, dWeights, w_stride, n_used, gate, up, down, dOut, ldo, act, st);
+      if (rc <= 0) return rc;
+    }
+  }
+  return moe_ffn_composition(dA, lda, m, dIds, ids_stride, dWeights, w_stride, n_used, gate, up, down, dOut, ldo, act, st);
+}
+
+int ns_hip_moe_ffn_silu(const float* dA, int lda, int m, const int32_t* dIds, int ids_stride, const float* dWeights, int w_stride, int n_used,
+                        const ns_expert_group* gate, const ns_expert_group* up, const ns_expert_group* down, float* dOut, int ldo, void* stream) {
+  return moe_ffn_block(dA, lda, m, dIds, ids_stride, dWeights, w_stride, n_used, gate, up, down, dOut, ldo, NS_EPI_SILU, stream);
+}
+
+int ns_hip_moe_ffn_gelu(const float* dA, int lda, int m, const int32_t* dIds, int ids_stride, const float* dWeights, int w_stride, int n_used,
+                        const ns_expert_group* gate, const ns_expert_group* up, const ns_expert_group* down, float* dOut, int ldo, void* stream) {
+  return moe_ffn_block(dA, lda, m, dIds, ids_stride, dWeights, w_stride, n_used, gate, up, down, dOut, ldo, NS_EPI_GELU, stream);
 }
 
 void ns_hip_moe_ffn_stats(uint64_t out[4]) {

@@ -5,14 +5,25 @@ selected expert, ids on the device, one HIP graph; parity of one token's rows ag
 MoE FFN layer, the HBM rate over the expert weights a token really touches, and tokens/s of 32 such layers.
 Below 32 tokens a second leg times the whole block through ns_hip_moe_ffn_silu (routing weights and the sum over the selections included)
 in the same graph form, on its fused launches and - "moe_ffn_fused" = 0 - on its composition: medians of interleaved replay batches.
-usage: moe_bench.py [tokens=1]"""
-import ctypes as C, json, os, sys
+From 32 tokens - or from grouped_rows=N tokens, which lowers "moe_ffn_grouped_rows" to N for that leg - a third leg times the block entry as
+plain calls (the grouped pass reads the ids on the host: no graph), wall clock around batches that end in a synchronisation, with the
+grouped pass on and - "moe_ffn_grouped_rows" negative - off: medians of interleaved batches again.
+usage: moe_bench.py [tokens=1] [act=silu|gelu] [grouped_rows=N]        (act: the block entry of the second and third leg)"""
+import ctypes as C, json, os, sys, time
 import numpy as np
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import __graft_entry__ as ge
 pkg = ge.load_package(); L = pkg.lib(); nso = ge.load_oracle()
-m = int(sys.argv[1]) if len(sys.argv) > 1 else 1
+opts = dict(x.split("=", 1) for x in sys.argv[1:] if "=" in x)
+pos_args = [x for x in sys.argv[1:] if "=" not in x]
+m = int(pos_args[0]) if pos_args else 1
+act_name = opts.get("act", "silu")
+assert act_name in ("silu", "gelu"), "act=silu or act=gelu"
+block_entry = L.ns_hip_moe_ffn_gelu if act_name == "gelu" else L.ns_hip_moe_ffn_silu
+act_f64 = (lambda x: 0.5 * x * (1.0 + np.tanh(0.7978845834732056 * (x + 0.044714998453855515 * x ** 3)))) if act_name == "gelu" else \
+    (lambda x: x / (1.0 + np.exp(-x)))
+grouped_rows = int(opts["grouped_rows"]) if "grouped_rows" in opts else 0   # 0: the library's default threshold
 n_as, d, ff, topk = 8, 4096, 14336, 2
 st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -90,7 +101,7 @@ if m < 32:
 
     def block_chain(s):
         for (wg, gg), (wu, gu), (wd, gd) in layers:
-            pkg.check(L.ns_hip_moe_ffn_silu(a.data_ptr(), d, m, ids.data_ptr(), topk, wts.data_ptr(), topk, topk, gg, gu, gd, out.data_ptr(), d, s))
+            pkg.check(block_entry(a.data_ptr(), d, m, ids.data_ptr(), topk, wts.data_ptr(), topk, topk, gg, gu, gd, out.data_ptr(), d, s))
 
     def stats():
         v = (C.c_uint64 * 4)()
@@ -132,8 +143,55 @@ if m < 32:
         ex = int(ids_np[0, sel])
         (wg, _), (wu, _), (wd, _) = layers[-1]
         hg, hu = nso.gemm_f64(a0b, hostb(wg[ex][1])), nso.gemm_f64(a0b, hostb(wu[ex][1]))
-        refb += float(wts[0, sel]) * nso.gemm_f64((hg / (1.0 + np.exp(-hg)) * hu).astype(np.float32), hostb(wd[ex][1]))
+        refb += float(wts[0, sel]) * nso.gemm_f64((act_f64(hg) * hu).astype(np.float32), hostb(wd[ex][1]))
     block["fused_parity_rel_l2_vs_fp64_oracle_token0"] = float("%.3g" % nso.rel_l2(out[:1].cpu().numpy(), refb))
+# the block entry at prompt size, plain calls: the grouped pass against the composition ("moe_ffn_grouped_rows" negative), interleaved batches
+prompt = {}
+if m >= 32 or (grouped_rows > 0 and m >= grouped_rows):
+    wts_p = torch.rand((m, topk), device="cuda") + 0.25
+    out_p = torch.empty((m, d), device="cuda")
+
+    def entry_chain():
+        for (wg, gg), (wu, gu), (wd, gd) in layers:
+            pkg.check(block_entry(a.data_ptr(), d, m, ids.data_ptr(), topk, wts_p.data_ptr(), topk, topk, gg, gu, gd, out_p.data_ptr(), d, st))
+
+    def ffn_stats():
+        v = (C.c_uint64 * 4)()
+        L.ns_hip_moe_ffn_stats(v)
+        return [int(x) for x in v]
+
+    legs = (("grouped", grouped_rows), ("composition", -1))
+    reps_p = 5 if m >= 1024 else 15 if m >= 256 else 50
+    times_p = {k: [] for k, _ in legs}
+    for rnd in range(8):   # (round 0 warms both legs up and is dropped)
+        for name, key in legs:
+            L.ns_hip_set_tuning(b"moe_ffn_grouped_rows", key)
+            s0 = ffn_stats()
+            entry_chain(); torch.cuda.synchronize()
+            s1 = ffn_stats()
+            prompt[name + "_calls"] = [s1[1] - s0[1], s1[3] - s0[3]]   # [on the composition, on the grouped pass] of one chain
+            t0 = time.perf_counter()
+            for _ in range(reps_p):
+                entry_chain()
+            torch.cuda.synchronize()
+            if rnd:
+                times_p[name].append((time.perf_counter() - t0) * 1e6 / reps_p / nlay)
+    L.ns_hip_set_tuning(b"moe_ffn_grouped_rows", 0)
+    for k, v in times_p.items():
+        prompt["us_per_layer_" + k] = {"median": round(float(np.median(v)), 1), "min": round(min(v), 1), "max": round(max(v), 1)}
+    prompt["act"], prompt["grouped_rows_key"] = act_name, grouped_rows
+    # parity of the grouped leg's token 0 against the fp64 oracle over both selections
+    L.ns_hip_set_tuning(b"moe_ffn_grouped_rows", grouped_rows)
+    entry_chain(); torch.cuda.synchronize()
+    L.ns_hip_set_tuning(b"moe_ffn_grouped_rows", 0)
+    hostp = lambda t: (lambda b: (b.__setitem__(slice(None), t.cpu().numpy()), b)[1])(nso.aligned_bytes(t.numel()))
+    a0p, refp = a[:1].cpu().numpy(), np.zeros((1, d))
+    for sel in range(topk):
+        ex = int(ids_np[0, sel])
+        (wg, _), (wu, _), (wd, _) = layers[-1]
+        hg, hu = nso.gemm_f64(a0p, hostp(wg[ex][1])), nso.gemm_f64(a0p, hostp(wu[ex][1]))
+        refp += float(wts_p[0, sel]) * nso.gemm_f64((act_f64(hg) * hu).astype(np.float32), hostp(wd[ex][1]))
+    prompt["grouped_parity_rel_l2_vs_fp64_oracle_token0"] = float("%.3g" % nso.rel_l2(out_p[:1].cpu().numpy(), refp))
 # parity of the last layer's last selection (token 0): silu(a Wg) * (a Wu) then Wd, fp64 over the oracle's blobs
 (wg, _), (wu, _), (wd, _) = layers[-1]
 e = int(ids_np[0, topk - 1])
@@ -151,4 +209,4 @@ print(json.dumps({"what": "Mixtral-8x7B-shaped MoE FFN (8 x {14336x4096 gate, up
                   "hbm_GBps_over_touched_weights": round(touched / us / 1e3, 1), "tokens_per_s_of_32_moe_ffn_layers": round(m * 1e6 / (32 * us), 1),
                   "parity_rel_l2_vs_fp64_oracle_token0": float("%.3g" % par), "launches_per_layer": 3 * topk,
                   "grouped_by_expert": m >= 32 and os.environ.get("NS_MOE_GROUPED_ROWS", "32") != "0",
-                  "tflops": round(m * topk * 3 * 2.0 * d * ff / us / 1e6, 1), "moe_ffn_silu": block}))
+                  "tflops": round(m * topk * 3 * 2.0 * d * ff / us / 1e6, 1), "moe_ffn_" + act_name: block, "moe_ffn_prompt": prompt}))
