@@ -800,7 +800,11 @@ hipError_t launch_smallm(const SmallMArgs& a, hipStream_t st) {
   static const int env_nw_plain = getenv("NS_NW_PLAIN") ? atoi(getenv("NS_NW_PLAIN")) : 0;  // diagnostics
   if (!a.dual && mb == 1 && (env_nw_plain == 2 || env_nw_plain == 4 || env_nw_plain == 8 || env_nw_plain == 16))
     nw = env_nw_plain;
-  // LDS: A chunk (rows x (chunk_k + 8) halves), at most ~64 KiB; and the reduction scratch
+  // LDS: A chunk (rows x (chunk_k + 8) halves) and the reduction scratch.  The chunk is halved while it is above 64 KiB but never below
+  // nw = 8 k-steps, so from 32 rows (4-bit records, kstep 128) / 64 rows (8-bit and fp8, kstep 64) the launch asks for MORE than 64 KiB:
+  // 66,048 B at 32 rows and 132,096 B at 64 rows of 4-bit records, 66,560 B at 64 rows of 8-bit ones.  This is a plain launch, not
+  // launch_lds: the runtime grants these sizes on gfx950 (160 KiB per workgroup) without the kernel's limit being raised —
+  // tests/test_gpu_rows17_64.py pins both crossings (docs/kernels/smallm.md)
   const int kstep = w0->kstep_len;
   int chunk_steps = ((w0->ksteps + nw - 1) / nw) * nw;
   const size_t budget = 64 * 1024;
@@ -839,6 +843,7 @@ struct GemmParams {
   uint32_t codes_bytes, scales_bytes, zps_bytes;
   uint32_t qstride, sstride, zstride;
   float* c;
+  _Float16* c16;  // optional fp16 shadow of C (same ldc)
   int ldc;
   int srows, srow_mul, srow_shift;
   int epilogue;
@@ -995,6 +1000,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmParams p) {
         const float dv = p.d ? p.d[size_t(row) * p.ldd + col] : 0.f;
         v = epi_apply(v, dv, p.epilogue);
         p.c[size_t(row) * p.ldc + col] = v;
+        if (p.c16) p.c16[size_t(row) * p.ldc + col] = (_Float16)v;
       }
     }
 }
@@ -1005,7 +1011,6 @@ hipError_t launch_gemm(const SmallMArgs& a, hipStream_t st) {
     if (e != hipErrorNotSupported) return e;
   }
   const ns_weight* w0 = a.seg[0].w;
-  if (a.seg[0].c16) return hipErrorInvalidValue;  // the fp16 output shadow is produced by gemm2_kernel / smallm_kernel
   GemmParams p;
   memset(&p, 0, sizeof(p));
   p.a = a.a;
@@ -1025,6 +1030,7 @@ hipError_t launch_gemm(const SmallMArgs& a, hipStream_t st) {
   p.sstride = w0->sstride;
   p.zstride = w0->zstride;
   p.c = a.seg[0].c;
+  p.c16 = static_cast<_Float16*>(a.seg[0].c16);  // the fp16 shadow of C: the same value, rounded once more (C does not depend on it)
   p.ldc = a.ldc;
   p.srows = w0->srows;
   if (!srow_params(w0, &p.srow_mul, &p.srow_shift)) return hipErrorInvalidValue;
