@@ -109,7 +109,8 @@ struct GemvParams {
   // segment pairs (GV_MSEGP): 16-column tiles per half head (head_size / 32) — workgroup u of a matrix owns tiles
   // t0 = head * 2 pair_tiles + j and t0 + pair_tiles (head = u / pair_tiles, j = u % pair_tiles); tb1 / tb2 count workgroups there
   uint32_t pair_tiles;
-  // ---- cold: read late, through the kernel-argument pointer (keeps them out of the streaming loop's SGPRs) ----
+  // ---- epilogue: mat[].n / .c / .c16, c2, d, ldc, ldd, epilogue and the carried norm's words are requested behind the ring fill and held in
+  //      SGPRs through the loop; the RoPE words and the overflow flags are read at the tail, through the kernel-argument pointer ----
   GemvMat mat[3];
   float* c2;
   const float* d;

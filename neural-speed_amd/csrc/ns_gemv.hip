@@ -10,8 +10,11 @@
 //   * lean prologue.  Every launch starts with cold instruction and scalar caches, so the time to the first weight
 //     request is the number of code lines and of dependent kernel-argument fetches in front of it.  smallm_kernel had
 //     1.8 KB of code and two argument round trips there (first request 1.3-1.8 us after entry); here ONE batch of scalar
-//     loads fetches the 30 words the prologue needs (epilogue arguments are read late, through the argument pointer,
-//     so they neither delay the batch nor sit in SGPRs through the loop) and the ring is filled ~0.6 KB into the code.
+//     loads fetches the 30 words the prologue needs and the ring is filled ~0.6 KB into the code.  The epilogue's arguments
+//     are a second batch BEHIND the ring fill, so they do not delay the first weight request either, and stay in SGPRs through
+//     the loop (7-8 registers; the kernel has room).  Up to round 13 they were read at the tail instead: on argument lines no
+//     earlier instruction had touched, a scalar-cache miss between the last record and the reduction barrier of every launch
+//     (docs/kernels/gemv.md, "launch tail").
 //   * weight records go HBM -> LDS directly (buffer_load ... lds into the wave's PRIVATE ring: codes, scales and zero
 //     points; no VGPRs, no cross-wave synchronisation).  The ring depth is therefore set by LDS, not by the register
 //     file: up to 8 records per wave, up to ~140 KiB per CU in flight from the first microsecond of a launch.
@@ -366,13 +369,45 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
   //      (its arguments are fetched here, late); only the epilogue reads them.  The requesting wave waits a little
   //      more strictly for its first records (a piece counts as one more request in flight), that is all.  With up
   //      to 16 rows x pieces the 6-bit request counter cannot overflow: PF x OPS + 16 <= 63 is asserted below.
+  //      The epilogue's arguments are requested here as well, one more batch of scalar loads behind the ring fill: they touch
+  //      argument lines the prologue has not, and fetched at the tail (as they were up to round 13) that scalar-cache miss sat
+  //      between the last record and the reduction barrier of every launch, with the whole workgroup and the next kernel
+  //      behind it.  They are pinned in SGPRs below, after the activation wait — a wait that exists anyway — and consumed
+  //      after the loop (7-8 more SGPRs through it, 14-16 with the carried norm's words: the one-row fp16 forms of a decode chain
+  //      have 57-64, below the 80 that eight 4-wave workgroups per CU allow; docs/kernels/gemv.md lists the forms above it).
+  const KArgs mid = late_args();
+  const auto* mp = &mid->mat[MSEGX ? sg : 0];  // indexed scalar loads
+  int ncols = mp->n;
+  float* cbase = mp->c;
+  _Float16* c16 = mp->c16;
+  int ldc = mid->ldc, epi = mid->epilogue;
+  int ldd = 0;
+  const float* dptr = nullptr;
+  float* c2 = nullptr;
+  if constexpr (DUAL) {
+    c2 = mid->c2;
+  } else {
+    dptr = mid->d;
+    ldd = mid->ldd;
+  }
+  uint32_t moe_cs = 0, moe_ds = 0;
+  if constexpr (MOE) moe_cs = mid->moe_c_stride, moe_ds = mid->moe_d_stride;
   const float* in_ssq = nullptr;
   uint32_t in_parts = 0, ssq_off = 0;
+  float in_eps = 0.f, in_inv = 0.f;
+  const float* ogamma = nullptr;
+  float* ossq = nullptr;
+  uint32_t ostride = 0;
+  int rope_on_arg = 0;
   if constexpr (EXT) {
-    const KArgs mid = late_args();
     in_ssq = mid->in_ssq;
     in_parts = mid->in_parts;
     ssq_off = mid->ssq_off;
+    in_eps = mid->in_eps, in_inv = mid->in_inv_size;
+    ogamma = mid->out_gamma;
+    ossq = mid->out_ssq;
+    ostride = mid->out_stride;
+    if constexpr (MSEG) rope_on_arg = mid->rope.on;
   }
   if (EXT && in_ssq && w == 0) {  // wave 0 finishes the tile: it fetches them itself and needs no barrier to read them
     const uint32_t in_stride = late_args()->in_stride;
@@ -394,6 +429,12 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
   // ---- 3. this wave's activation pieces (the oldest requests in its queue) have landed once only its ring
   //      requests are left in flight ----
   wait_records(min(nst * uint32_t(NQ), uint32_t(PF)));
+  // the epilogue arguments of 2b: in SGPRs from here on (without the pins hipcc sinks each load to its first use, behind the stream)
+  asm volatile("" : "+s"(ncols), "+s"(cbase), "+s"(c16), "+s"(ldc), "+s"(epi));
+  if constexpr (DUAL) asm volatile("" : "+s"(c2));
+  else asm volatile("" : "+s"(dptr), "+s"(ldd));
+  if constexpr (MOE) asm volatile("" : "+s"(moe_cs), "+s"(moe_ds));
+  if constexpr (EXT) asm volatile("" : "+s"(in_eps), "+s"(in_inv), "+s"(ogamma), "+s"(ossq), "+s"(ostride), "+s"(rope_on_arg));
   if constexpr (A32) {
 #pragma unroll
     for (int i = 0; i < kGvA32Regs; i++) asm volatile("" : "+v"(areg[i]));  // not to be read above the wait
@@ -791,6 +832,7 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
         wait_records(min(nitems - t - 1, uint32_t(PF - 1)));
         compute(ic, first + (ord << p.nw_log2));
         __builtin_amdgcn_sched_barrier(0);
+        if (t == 0) { NS_GSTAMP(3); }  /* first record consumed */
         if (ord + SPR < nst) issue(ic, first + ((ord + SPR) << p.nw_log2));
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -832,27 +874,12 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
     else
       red[w * kRedWave + q * 64 + l] = acc[q];
   }
-  const KArgs cold = late_args();  // epilogue-only arguments: fetched here, not held through the streaming loop
-  const auto* mp = &cold->mat[MSEGX ? sg : 0];  // indexed scalar loads
-  const int ncols = mp->n;
-  float* cbase = mp->c;
-  _Float16* c16 = mp->c16;
-  const int ldc = cold->ldc, ldd = cold->ldd, epi = cold->epilogue;
-  const float* dptr = cold->d;
+  // (the epilogue's arguments have been in SGPRs since section 3; only what rare paths read — the RoPE words, the overflow
+  // flags — is still fetched here, through the argument pointer)
+  [[maybe_unused]] const KArgs cold = late_args();
   if constexpr (MOE) {  // the pair's output row (and the row of its epilogue operand)
-    cbase += size_t(moe_y) * cold->moe_c_stride;
-    if (dptr) dptr += size_t(moe_y) * cold->moe_d_stride;
-  }
-  float* c2 = cold->c2;
-  float in_eps = 0.f, in_inv = 0.f;
-  const float* ogamma = nullptr;
-  float* ossq = nullptr;
-  uint32_t ostride = 0;
-  if constexpr (EXT) {
-    in_eps = cold->in_eps, in_inv = cold->in_inv_size;
-    ogamma = cold->out_gamma;
-    ossq = cold->out_ssq;
-    ostride = cold->out_stride;
+    cbase += size_t(moe_y) * moe_cs;
+    if (dptr) dptr += size_t(moe_y) * moe_ds;
   }
   // Wave 0 finishes the tile.  Everything its epilogue has to FETCH (the epilogue operand, the next norm's weight, the
   // RoPE table entry) is requested before the workgroup barrier, so the round trips overlap the wait for the slowest
@@ -882,7 +909,7 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
     if constexpr (EXT) {
       if (ogamma && col_ok) gam = ogamma[col];
       if constexpr (MSEG) {
-        rope_on = cold->rope.on != 0;
+        rope_on = rope_on_arg != 0;
         if (rope_on) {
           const int hs = cold->rope.head_size;
           rope_head = col / hs;
@@ -931,16 +958,43 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
     }
   }
   __syncthreads();
+  NS_GSTAMP(5);  // reduction barrier passed
   if (w == 0) {
+    // Every wave's partial sums are requested before the first add — one LDS round trip for any wave count (as a run-time loop
+    // the 2- and 4-wave launches paid one dependent round trip per wave) — and added in wave order 0 .. NW - 1 onto +0, as always:
+    // the same bits (and 0 + (-0) stays +0).
     floatx4 sum[NQ];
 #pragma unroll
-    for (int q = 0; q < NQ; q++) {
-      sum[q] = floatx4{0.f, 0.f, 0.f, 0.f};
-      if constexpr (R1) {
-        for (uint32_t ww = 0; ww < NW; ww++) sum[q][0] += red1[ww * kRedWave1 + q * 64 + l];
-      } else {
-        for (uint32_t ww = 0; ww < NW; ww++) sum[q] += red[ww * kRedWave + q * 64 + l];
+    for (int q = 0; q < NQ; q++) sum[q] = floatx4{0.f, 0.f, 0.f, 0.f};
+    auto reduce = [&](auto n_c) {
+      constexpr int N = decltype(n_c)::value;
+#pragma unroll
+      for (int q = 0; q < NQ; q++) {
+        if constexpr (R1) {
+          float t[N];
+#pragma unroll
+          for (int ww = 0; ww < N; ww++) t[ww] = red1[uint32_t(ww) * kRedWave1 + q * 64 + l];
+#pragma unroll
+          for (int ww = 0; ww < N; ww++) sum[q][0] += t[ww];
+        } else if constexpr (N <= 4) {
+          floatx4 t[N];
+#pragma unroll
+          for (int ww = 0; ww < N; ww++) t[ww] = red[uint32_t(ww) * kRedWave + q * 64 + l];
+#pragma unroll
+          for (int ww = 0; ww < N; ww++) sum[q] += t[ww];
+        } else {
+          // four floats per lane and wave: 16 waves at once are 64 registers more than the rest of the kernel needs (96 instead of 41 VGPRs:
+          // fewer workgroups per CU).  The run-time loop of before: hipcc unrolls it by eight with the reads pipelined
+          for (uint32_t ww = 0; ww < NW; ww++) sum[q] += red[ww * kRedWave + q * 64 + l];
+        }
       }
+    };
+    switch (p.nw_log2) {  // NW is a power of two <= 16 (gemv_plan)
+      case 0: reduce(std::integral_constant<int, 1>{}); break;
+      case 1: reduce(std::integral_constant<int, 2>{}); break;
+      case 2: reduce(std::integral_constant<int, 4>{}); break;
+      case 3: reduce(std::integral_constant<int, 8>{}); break;
+      default: reduce(std::integral_constant<int, 16>{}); break;
     }
     // ---- 6. epilogue: lane (nn, g) holds rows 4g .. 4g+3 of column nn (R1: row 0 alone, live in lane group 0) ----
 #pragma unroll

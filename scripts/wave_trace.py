@@ -1,9 +1,11 @@
 #!/usr/bin/env python
 """Intra-kernel timeline of the decode kernel (diagnostics; needs a -DNS_TRACE build, see scripts/build_variants.sh).
 
-Every wave stamps the 100 MHz wall clock at: 0 entry, 1 ring issued, 2 A staged (barrier), 3 first item arrived,
-4 last item consumed, 5 reduction barrier, 6 exit.  Prints percentiles relative to the earliest entry stamp.
-Run: NS_LIB_PATH=variants/libns_hip_trace.so python scripts/wave_trace.py [shape ...]
+Every wave stamps the 100 MHz wall clock at: 0 entry, 1 ring issued, 2 A staged (barrier), 3 first record consumed,
+4 last record consumed, 5 reduction barrier passed, 6 exit.  Prints percentiles relative to the earliest entry stamp, and the launch
+tail: last record -> barrier and barrier -> exit for wave 0 (which finishes the tile) and for the other waves, and chip-wide the time
+from the last record consumed anywhere to the last exit anywhere — what the next kernel of a dependent chain waits for.
+Run: NS_LIB_PATH=variants/libns_hip_trace.so python scripts/wave_trace.py [shape ...]   (shapes: gateup qkv down wo head)
 """
 import ctypes as C
 import os
@@ -52,7 +54,7 @@ def flush():
 if os.environ.get("NS_DECODE_KERNEL", "0") == "1":
     DIMS = {"gateup": (256, 12), "qkv": (256, 12), "down": (256, 12), "wo": (256, 8)}
 else:
-    DIMS = {"gateup": (688, 4), "qkv": (768, 4), "down": (256, 16), "wo": (256, 16)}
+    DIMS = {"gateup": (688, 4), "qkv": (768, 4), "down": (256, 8), "wo": (256, 16), "head": (2000, 2)}  # gemv_kernel's plan (decode_waves_rule)
 if os.environ.get("NS_GV_NW"):  # gemv_kernel with a forced wave count
     DIMS = {k: (v[0], int(os.environ["NS_GV_NW"])) for k, v in DIMS.items()}
 KARG = os.environ.get("NS_DECODE_KERNEL", "0") == "1"  # slot 7 = "kernargs arrived" (decode_kernel) instead of HW id
@@ -71,6 +73,7 @@ def build_ops():
             ws = [make_weight(n, k, seed + i) for i in range(nw)]
             seed += nw
             ops.append((name, ws))
+    ops.append(("head", [make_weight(*SHAPES["head"][:2], seed)]))  # lm_head, once per token
     return ops
 
 
@@ -87,7 +90,7 @@ def launcher(name, ws, bufs):
                                                                out.data_ptr(), outh.data_ptr(), 1, pkg.EPI_SILU, cur()))
     if kind == "qkv":
         return lambda: pkg.check(L.ns_hip_fusion_qkv_forward_h(x.data_ptr(), xh.data_ptr(), ws[0][0].h, ws[1][0].h,
-                                                               ws[2][0].h, out.data_ptr(), outh.data_ptr(), 1, k, 3 * n, cur()))
+                                                               ws[2][0].h, out.data_ptr(), outh.data_ptr(), 1, k, n, cur()))
     return lambda: pkg.check(L.ns_hip_f32f32_forward_h(x.data_ptr(), xh.data_ptr(), ws[0][0].h, out.data_ptr(),
                                                        outh.data_ptr(), 1, k, n, pkg.EPI_NONE, None, 0, cur()))
 
@@ -142,7 +145,7 @@ def report(name, t, live):
     rel = (t - t0) * 0.01  # us
     print(f"== {name}: blocks {int(live.any(axis=1).sum())} waves/block {int(live.sum(axis=1).max())} "
           f"kernel span {rel[:, :, 6][live].max():.2f} us")
-    names = ["entry", "ring issued", "A staged", "first item", "last item", "reduced", "exit"]
+    names = ["entry", "ring issued", "A staged", "first item", "last item", "barrier", "exit"]
     if KARG:
         v = rel[:, :, 7][live]
         q = np.percentile(v, [0, 10, 50, 90, 100])
@@ -162,6 +165,17 @@ def report(name, t, live):
         v = v[live]
         q = np.percentile(v, [10, 50, 90])
         print(f"  dur {nm:22s} p10 {q[0]:6.2f}  p50 {q[1]:6.2f}  p90 {q[2]:6.2f}")
+    # the launch tail: wave 0 finishes the tile behind the reduction barrier, the others only write their partial sums and leave
+    w0 = np.zeros_like(live)
+    w0[:, 0] = True
+    for who, sel in (("wave 0", live & w0), ("other waves", live & ~w0)):
+        if not sel.any():
+            continue
+        for nm, v in (("last item->barrier", rel[:, :, 5] - rel[:, :, 4]), ("barrier->exit", rel[:, :, 6] - rel[:, :, 5])):
+            q = np.percentile(v[sel], [50, 90, 100])
+            print(f"  tail {who:11s} {nm:20s} p50 {q[0]:6.2f}  p90 {q[1]:6.2f}  max {q[2]:6.2f}")
+    print(f"  tail chip-wide: last item anywhere -> last exit anywhere {rel[:, :, 6][live].max() - rel[:, :, 4][live].max():6.2f} us"
+          f"   (last barrier passed -> last exit {rel[:, :, 6][live].max() - rel[:, :, 5][live].max():6.2f})")
     # per-workgroup spread of the waves' finish times
     fin = np.where(live, rel[:, :, 4], np.nan)
     spread = np.nanmax(fin, axis=1) - np.nanmin(fin, axis=1)
@@ -190,4 +204,4 @@ def report(name, t, live):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1:] or ["gateup", "qkv", "down", "wo"])
+    main(sys.argv[1:] or ["gateup", "qkv", "down", "wo", "head"])
