@@ -231,6 +231,13 @@ int ns_hip_get_compute_mode(void);
  *                     last does inside the launch (one self-resetting counter per kv head); same sums in the same order, same time
  *   "attn_heads_first" dispatch order of the decode attention's workgroups: 1 = the kv heads of one context range side by side, 0 = the
  *                     ranges of one head, -1 (default) = by the cache layout (position-major caches take 1: 5-10 % faster at 2048 / 4096 keys)
+ *   "attn_block_split" opt-in: v > 0 = an attention call with 2 .. 127 query rows over max(v, 256) or more keys (head size 64 / 128, contiguous
+ *                     16-byte aligned K / V rows, no ALiBi, no tanh cap, no moving context length) splits the context into ranges: one matrix-core
+ *                     workgroup per (64 slots of a kv head = query rows x the head group's query heads, range), so K / V of a kv head are read once
+ *                     for its whole head group, then attn_merge_kernel (attn_block_split_kernel; ns_hip_attn_stats index 7); 0 or less (default) =
+ *                     off: every call is served as without the key; also NS_ATTN_BLOCK_SPLIT in the environment.  The two paths agree to fp32
+ *                     rounding.  "attn_block_wg_target" / "attn_block_min_keys": its context-range rule (defaults 512 workgroups, >= 128 keys per
+ *                     range; 0 keeps what is set)
  *   "gv_nw"           waves per 16-column tile of the decode kernels (2 / 4 / 8 / 16), 0 = by shape (default); the
  *                     partial sums of a tile are added in wave order, so this selects the summation order
  *   "gv_rows1"        1 (default) = a decode launch of ONE row takes the one-row instantiation of gemv_kernel where there is one (integer weights;
@@ -250,6 +257,11 @@ int ns_hip_get_compute_mode(void);
  *                     negative = never: the composition serves such calls)
  * Returns 0, or -1 for an unknown key. */
 int ns_hip_set_tuning(const char* key, int value);
+/* Process-wide counts of attention launches by the kernel family that served them (every entry that ends in an attention launch counts, the
+ * host-pointer ones included): [1] one query row per workgroup, generic, [2] ... K / V through registers over context ranges, [3] ... through LDS
+ * rings, [4] 64-row matrix-core kernel, [5] 128-row matrix-core kernels, [6] ... with K / V tiles by DMA, [7] the context-split 64-slot kernel of
+ * "attn_block_split"; [0] is not used (a refused call launches nothing). */
+void ns_hip_attn_stats(uint64_t out[8]);
 /* Loads the code objects of the hot kernels (tiled GEMM, decode GEMV, attention, the operators between them) for the current device now instead of at the
  * first launch from each (36 + 21 + ... ms otherwise paid by the first prompt and the first generated token); idempotent, called by bestla_create_device.
  * NS_WARM_UP=0 turns it off. */

@@ -123,6 +123,9 @@ const TuningKey kTuning[] = {
     {"attn_stream_min_keys", [](int v) { set_attn_stream_tuning(0, v); }},
     {"attn_stream", set_attn_stream},
     {"attn_inlaunch", set_attn_inlaunch},
+    {"attn_block_split", set_attn_block_split},  // (opt-in: 0 = off, the default)
+    {"attn_block_wg_target", [](int v) { set_attn_block_tuning(v, 0); }},
+    {"attn_block_min_keys", [](int v) { set_attn_block_tuning(0, v); }},
     // the device route's attention reads the fp16 mirror of the fp32 kv cache (1, default) or the fp32 cache itself (0); -1: NS_DEVICE_KV
     {"device_kv_f16", kv16_set},
 };

@@ -1,5 +1,5 @@
 // ns_attn.cpp — fused attention behind the reference's mha_dense C surface, host side: the tunables, and the launch of
-// what attn_plan (ns_attn_plan.cpp) decided.  The kernels are in ns_attn_decode.hip and ns_attn_prefill.hip, the library-managed kv-cache and the
+// what attn_plan (ns_attn_plan.cpp) decided.  The kernels are in ns_attn_decode.hip, ns_attn_prefill.hip and ns_attn_block.hip, the library-managed kv-cache and the
 // host-tensor entries in ns_kvcache.hip.
 #include <algorithm>
 #include <atomic>
@@ -21,6 +21,10 @@ static std::atomic<int> g_attn_inlaunch{env_int("NS_ATTN_INLAUNCH", 0) != 0};
 static std::atomic<int> g_attn_heads_first{env_int("NS_ATTN_HEADS_FIRST", -1)};
 static std::atomic<int> g_attn_wg_target{1024}, g_attn_min_keys{128}, g_attn_wg_target_s{256}, g_attn_min_keys_s{32};
 static std::atomic<int> g_alibi_heads{0}, g_alibi_off{0};  // ns_hip_attn_set_head_partition
+// "attn_block_split": opt-in (0) until the default dispatch, pinned by tests/test_attn_plan.py, is changed with the numbers of docs/kernels/attention.md
+static std::atomic<int> g_attn_block_split{std::max(0, env_int("NS_ATTN_BLOCK_SPLIT", 0))};
+static std::atomic<int> g_attn_block_target{512}, g_attn_block_min_keys{128};
+static std::atomic<uint64_t> g_attn_launches[kAttnPaths];  // ns_hip_attn_stats
 void set_attn_stream(int on) { g_attn_stream.store(on != 0); }
 void set_attn_mfma2_rows(int rows) { g_attn_mfma2_rows.store(rows > 0 ? rows : 128); }
 void set_attn_inlaunch(int on) { g_attn_inlaunch.store(on != 0); }
@@ -32,6 +36,11 @@ void set_attn_tuning(int wg_target, int min_keys) {
 void set_attn_stream_tuning(int wg_target, int min_keys) {
   if (wg_target > 0) g_attn_wg_target_s.store(wg_target);
   if (min_keys > 0) g_attn_min_keys_s.store(min_keys);
+}
+void set_attn_block_split(int keys) { g_attn_block_split.store(std::max(0, keys)); }
+void set_attn_block_tuning(int wg_target, int min_keys) {
+  if (wg_target > 0) g_attn_block_target.store(wg_target);
+  if (min_keys > 0) g_attn_block_min_keys.store(min_keys);
 }
 static AttnKnobs attn_knobs() {
   static const AttnKnobs env = [] {  // the switches only the environment sets (diagnostics, A/B runs)
@@ -52,6 +61,8 @@ static AttnKnobs attn_knobs() {
   k.wg_target = g_attn_wg_target.load(), k.min_keys = g_attn_min_keys.load();
   k.wg_target_s = g_attn_wg_target_s.load(), k.min_keys_s = g_attn_min_keys_s.load();
   k.alibi_heads = g_alibi_heads.load(), k.alibi_off = g_alibi_off.load();
+  k.block_split = g_attn_block_split.load(std::memory_order_relaxed);
+  k.block_target = g_attn_block_target.load(), k.block_min_keys = g_attn_block_min_keys.load();
   return k;
 }
 
@@ -59,9 +70,25 @@ static AttnKnobs attn_knobs() {
 static hipError_t launch_attn(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, hipStream_t st, std::string* why, bool device_tmp, void* dst16) {
   AttnKnobs kn = attn_knobs();
   AttnPlan pl = attn_plan(a, dst16, kn, g_affine, why);
-  if (pl.path == AP_REFUSED) return hipErrorInvalidValue;
-  if (pl.path == AP_ROWS64 || pl.path == AP_ROWS128 || pl.path == AP_PIPELINED) return launch_attn_rows(pl, st);
   float* ws = nullptr;
+  if (pl.path == AP_BLOCK_SPLIT) {
+    // bestla_fusion_attn_workspace_size does not know this path (the reference's contract, sized by the one-row rules): the caller's `tmp` serves
+    // only where it is large enough, the stream's scratch otherwise; without either the call is planned as with the key at 0
+    if (device_tmp && pl.partial_bytes <= attn_ws_bytes(kn, a.batch_size, a.head_num, a.heads_kv, a.head_size, a.sl_q, a.sl_kv))
+      ws = reinterpret_cast<float*>(a.tmp);
+    if (!ws) ws = static_cast<float*>(stream_scratch(st, pl.partial_bytes, SLOT_ATTN_PARTIALS));
+    if (!ws) {
+      kn.block_split = 0;
+      pl = attn_plan(a, dst16, kn, g_affine, why);
+    }
+  }
+  if (pl.path == AP_REFUSED) return hipErrorInvalidValue;
+  auto counted = [&](hipError_t e) {
+    if (e == hipSuccess) g_attn_launches[pl.path].fetch_add(1, std::memory_order_relaxed);
+    return e;
+  };
+  if (pl.path == AP_BLOCK_SPLIT) return counted(launch_attn_block_split(pl, ws, st));
+  if (pl.path == AP_ROWS64 || pl.path == AP_ROWS128 || pl.path == AP_PIPELINED) return counted(launch_attn_rows(pl, st));
   if (pl.partial_bytes) {
     // partials go to the caller's workspace (`tmp`, sized by bestla_fusion_attn_workspace_size: the reference's own contract, and the only choice
     // that works on a stream being captured for the first time); without one, to a grow-only per-stream scratch
@@ -74,7 +101,7 @@ static hipError_t launch_attn(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, hipS
   }
   // (nullptr, e.g. first use on a capturing stream: the merge launch)
   uint32_t* tickets = pl.want_tickets ? static_cast<uint32_t*>(stream_scratch_zeroed(st, kAttnTicketCap * 4, SLOT_ATTN_TICKETS)) : nullptr;
-  return launch_attn_onerow(pl, ws, tickets, st);
+  return counted(launch_attn_onerow(pl, ws, tickets, st));
 }
 
 // scratch a moving-length decode launch needs (partials for the longest context, the merge tickets): allocated BEFORE the route's capture
@@ -108,6 +135,11 @@ int ns_hip_attn_set_head_partition(int global_head_num, int head_offset) {
   }
   g_alibi_heads.store(global_head_num), g_alibi_off.store(global_head_num > 0 ? head_offset : 0);
   return 0;
+}
+
+void ns_hip_attn_stats(uint64_t out[8]) {
+  static_assert(kAttnPaths == 8, "ns_hip_attn_stats: one counter per AttnPath value");
+  for (int i = 0; i < kAttnPaths; i++) out[i] = g_attn_launches[i].load(std::memory_order_relaxed);
 }
 
 size_t bestla_fusion_attn_workspace_size(const attn_shape_t* s) {

@@ -1,5 +1,5 @@
 // ns_attn.h — what the attention files share (internal).  Kernels: ns_attn_decode.hip (one query row per workgroup), ns_attn_prefill.hip (matrix
-// cores).  Host: ns_attn_plan.cpp decides which kernel serves a call (attn_plan: a pure function, checked on the CPU by tests/test_attn_plan.py),
+// cores), ns_attn_block.hip (matrix cores over context ranges: a short block of query rows over a long cache).  Host: ns_attn_plan.cpp decides which kernel serves a call (attn_plan: a pure function, checked on the CPU by tests/test_attn_plan.py),
 // ns_attn.cpp reads the tunables, takes scratch and launches what the plan says.  ns_kvcache.hip is the library-managed kv-cache on top of them.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -97,13 +97,18 @@ struct AttnKnobs {
   bool dyn_ranges = true;      // NS_ATTN_DYN_RANGES=0: a moving context length keeps the ranges as laid out (A/B)
   int alibi_heads = 0, alibi_off = 0;  // ns_hip_attn_set_head_partition
   bool no_partials = false;    // not a tunable: launch_attn's second plan when the partials' scratch cannot be had — one range, still correct
+  int block_split = 0;         // "attn_block_split" / NS_ATTN_BLOCK_SPLIT: > 0 = 2 .. 127 query rows over max(value, 256) or more keys take the
+                               // context-split 64-slot kernel (attn_block_split_kernel); 0 (default) = every plan as without it
+  int block_target = 512, block_min_keys = 128;  // "attn_block_wg_target" / "attn_block_min_keys": its range rule (scripts/attn_block_split_bench.py)
 };
-enum AttnPath { AP_REFUSED = 0, AP_GENERIC, AP_SPLIT_REGS, AP_RING, AP_ROWS64, AP_ROWS128, AP_PIPELINED };
+enum AttnPath { AP_REFUSED = 0, AP_GENERIC, AP_SPLIT_REGS, AP_RING, AP_ROWS64, AP_ROWS128, AP_PIPELINED, AP_BLOCK_SPLIT };
+constexpr int kAttnPaths = 8;  // ns_hip_attn_stats: one counter per AttnPath value
 // What a launch needs; nothing is decided after it.  sp.ws and sp.tickets are null: the launcher's scratch.
 struct AttnPlan {
   AttnPath path = AP_REFUSED;
   int G = 0, lpk = 0, dpl = 0;       // one-row paths: attn_split_kernel<G, dpl> / attn_stream_kernel<G, lpk>
-  int hs_pad = 0, sb = 0, pad = 0;   // matrix-core paths: attn_mfma_kernel<hs_pad> / attn_mfma2(_hs256)_kernel<hs_pad, sb, pad> / attn_mfma3_kernel<hs_pad>
+  int hs_pad = 0, sb = 0, pad = 0;   // matrix-core paths: attn_mfma_kernel<hs_pad> / attn_mfma2(_hs256)_kernel<hs_pad, sb, pad> / attn_mfma3_kernel<hs_pad> /
+                                     // attn_block_split_kernel<hs_pad> (which reads sp.nsplit, sp.keys_per_split and sp.g_full as well)
   AttnSplitParams sp;                // sp.a: the kernels' AttnParams; the rest (ranges, order, head groups, moving length): one-row paths
   dim3 grid, block;
   size_t lds = 0;                    // dynamic LDS bytes
@@ -121,13 +126,16 @@ size_t attn_ws_bytes(const AttnKnobs& knobs, int batch, int head_num, int heads_
 // ---- launches of a plan ----------------------------------------------------------------------------------------------------------------------
 hipError_t launch_attn_onerow(const AttnPlan& pl, float* ws, uint32_t* tickets, hipStream_t st);  // ns_attn_decode.hip: AP_GENERIC, AP_SPLIT_REGS, AP_RING (+ merge)
 hipError_t launch_attn_rows(const AttnPlan& pl, hipStream_t st);                                  // ns_attn_prefill.hip: AP_ROWS64, AP_ROWS128, AP_PIPELINED
-// touch_attn_module (ns_common.h) makes the runtime load all three code objects
+hipError_t launch_attn_block_split(const AttnPlan& pl, float* ws, hipStream_t st);                // ns_attn_block.hip: AP_BLOCK_SPLIT (+ merge)
+hipError_t launch_attn_merge(const AttnSplitParams& sp, unsigned batch, hipStream_t st);          // ns_attn_decode.hip: attn_merge_kernel over sp.ws
+// touch_attn_module (ns_common.h) makes the runtime load all four code objects
 inline void touch_kernel(const void* kernel) {
   hipFuncAttributes fa;
   (void)hipFuncGetAttributes(&fa, kernel);
   (void)hipGetLastError();
 }
 void touch_attn_rows_module();  // ns_attn_prefill.hip
+void touch_attn_block_module(); // ns_attn_block.hip
 void touch_kvcache_module();    // ns_kvcache.hip
 // Is a HIP device visible?  who != nullptr: if not, the error is set and "Err: invalid parameters (<who>: no HIP device visible ...)" goes to stderr.
 bool attn_device_visible(const char* who);

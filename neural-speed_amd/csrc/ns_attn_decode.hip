@@ -766,16 +766,18 @@ hipError_t launch_attn_onerow(const AttnPlan& pl, float* ws, uint32_t* tickets, 
                  : pl.G == 4 ? launch_split_g<4>(pl, sp, st)
                              : launch_split_g<8>(pl, sp, st);
   if (e != hipSuccess) return e;
-  if (sp.nsplit > 1 && !sp.tickets) {
-    hipLaunchKernelGGL(attn_merge_kernel, dim3(unsigned(p.head_num), unsigned(p.sl_q), pl.grid.z), dim3(128), 0, st, sp);  // (grid.z: the batch)
-    e = hipGetLastError();
-  }
+  if (sp.nsplit > 1 && !sp.tickets) e = launch_attn_merge(sp, pl.grid.z, st);  // (grid.z: the batch)
   return e;
+}
+hipError_t launch_attn_merge(const AttnSplitParams& sp, unsigned batch, hipStream_t st) {
+  hipLaunchKernelGGL(attn_merge_kernel, dim3(unsigned(sp.a.head_num), unsigned(sp.a.sl_q), batch), dim3(128), 0, st, sp);
+  return hipGetLastError();
 }
 
 void touch_attn_module() {  // (one kernel of every attention file: each has a code object of its own)
   touch_kernel(reinterpret_cast<const void*>(attn_merge_kernel));
   touch_attn_rows_module();
+  touch_attn_block_module();
   touch_kvcache_module();
 }
 

@@ -137,8 +137,35 @@ AttnPlan attn_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst
                        a.step_v_bs % 8 == 0 && (reinterpret_cast<uintptr_t>(a.K) & 15) == 0 &&
                        (reinterpret_cast<uintptr_t>(a.V) & 15) == 0;
 
-  // ---- several query rows: matrix cores ----
   const bool biased = (a.attn_flags & (NS_ATTN_FLAG_IS_ALIBI8 | NS_ATTN_FLAG_IS_TANH30)) != 0;
+  // ---- a short block of query rows over a long cache: matrix cores over context ranges (opt-in, kn.block_split) ----
+  // A workgroup serves 64 SLOTS of one kv head — slot = row * g_full + j is query row `row` of the head group's j-th query head — over one range of
+  // keys, so K / V of a kv head are read once per slot block and range, whatever the head group; attn_merge_kernel combines the ranges.
+  // Ranges: two workgroups per CU, two 64-key blocks or more per range, whole blocks (512 / 128: the best pair of {128, 256, 512} x {128, 256} over
+  // 4 / 16 / 64 rows x 2048 / 8192 keys x 32 / 8 kv heads, profiles/attn_block_split.txt; 256 / 128, the ring kernel's pair, is 5 % behind).
+  if (kn.block_split > 0 && a.sl_q >= 2 && a.sl_q <= 127 && (a.head_size == 64 || a.head_size == 128) && !biased && rows_ok && !aff.k && !kn.no_mfma &&
+      !kn.v1 && !kn.no_partials && a.sl_kv >= std::max(kn.block_split, 256)) {
+    const int g_full = a.head_num / a.heads_kv;
+    const size_t slot_blocks = (size_t(a.sl_q) * g_full + 63) / 64;
+    const size_t base = size_t(a.heads_kv) * slot_blocks * a.batch_size;
+    int nsplit = int((size_t(std::max(1, kn.block_target)) + base - 1) / base);
+    const int min_keys = std::max(1, kn.block_min_keys);
+    nsplit = std::min(std::min(nsplit, std::max(1, (a.sl_kv + min_keys - 1) / min_keys)), 64);
+    const int kps = ((a.sl_kv + nsplit - 1) / nsplit + 63) / 64 * 64;
+    nsplit = (a.sl_kv + kps - 1) / kps;  // (no range starts at or past sl_kv)
+    if (size_t(a.heads_kv) * slot_blocks <= 65535 && nsplit >= 2) {
+      pl.path = AP_BLOCK_SPLIT;
+      pl.hs_pad = p.hs_pad;
+      pl.grid = dim3(unsigned(slot_blocks * a.heads_kv), unsigned(nsplit), unsigned(a.batch_size));
+      pl.block = dim3(256);
+      pl.sp.nsplit = nsplit, pl.sp.keys_per_split = kps, pl.sp.g_full = g_full;
+      pl.partial_bytes = attn_partial_bytes(a.batch_size, a.sl_q, a.head_num, a.head_size, nsplit);
+      pl.merge = true;
+      return pl;
+    }
+  }
+
+  // ---- several query rows: matrix cores ----
   const size_t nqb = (size_t(a.sl_q) + 127) / 128, wgs2 = nqb * a.head_num * a.batch_size;
   // the 128-row kernels pad any head size that is a multiple of 8 to 64 / 128 / 256; the 64-row kernel takes 64 and 128 as they are and has no biased
   // form.  Shapes it cannot take use the 128-row kernels from 16 rows on: a workgroup with idle waves is still far from the one-row-per-workgroup

@@ -287,6 +287,8 @@ void set_gemv_planes(int on);  // 1 (default): bit-plane formats stream their na
 void set_attn_mfma2_rows(int rows);  // query rows from which the 128-row prefill attention kernel is used (default 128; huge = never)
 void set_attn_stream_tuning(int wg_target, int min_keys);  // context-range rule of the LDS-ring kernel (defaults 256 workgroups, >= 32 keys)
 void set_attn_stream(int on);    // 1 (default): decode attention streams K / V through LDS rings (attn_stream_kernel); 0: attn_split_kernel
+void set_attn_block_split(int keys);  // ns_attn.cpp: > 0 = 2 .. 127 query rows over max(keys, 256) or more keys take attn_block_split_kernel (AP_BLOCK_SPLIT); 0 (default): off
+void set_attn_block_tuning(int wg_target, int min_keys);  // ... its context-range rule; values <= 0 keep what is set
 void set_attn_inlaunch(int on);  // 0 (default): attn_merge_kernel combines the context splits in a second launch; 1: the last split to finish merges inside attn_split_kernel's launch
 // NS_HOST_PROFILE=1: wall time and call count of every host-tensor entry, printed at exit (diagnostics of the default,
 // host-pointer route: where a token's milliseconds go between the graph executor and the GPU)
