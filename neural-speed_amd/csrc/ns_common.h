@@ -175,15 +175,16 @@ struct I8Act {
 };
 hipError_t i8_quantize_finish(I8Act* q, hipStream_t st);  // ns_i8ref.hip
 // expert-indexed decode launch (gemv_kernel XV = 4): the weight base comes from table[*id] on the device
+struct MoeExpertRow;  // ns_moe.h
 struct MoeRoute {
-  const void* table;   // device: rows {codes, scales, zps} of the group's experts (ns_moe.hip)
+  const MoeExpertRow* table;  // device: rows {codes, scales, zps} of the group's experts (ns_expert_group::table)
   const int32_t* id;   // device: &ids[token][id]
   int n_as;
   // one launch over several (token row, selection) pairs, pair y = row * nsel + sel along grid.y (ns_hip_moe_ffn_silu): the pair's id is
   // id[row * ids_stride + sel], its activation row a + row * a_stride, its output (epilogue operand) row seg[0].c + y * c_stride (d + y * d_stride)
   // — strides in floats — and w[row * w_stride + sel] (w == nullptr: 1) is multiplied into its product in front of the epilogue.
   // SmallMArgs::dual: seg[0] / seg[1] describe the gate / up groups (equal shape and format), table1 is the up group's table
-  const void* table1 = nullptr;
+  const MoeExpertRow* table1 = nullptr;
   int pairs = 1, nsel = 1, ids_stride = 0;
   const float* w = nullptr;
   int w_stride = 0;
@@ -246,7 +247,7 @@ enum ScratchSlot : int {
   SLOT_ROPE_TAB = 23,         // ns_quant.hip: cos / sin table of launch_rope_qkv_append
   SLOT_MHA_PARTIALS = 24,     // ns_device.hip device-layout attention (allocated ahead of a capture by ns_route.cpp): partials
   SLOT_MHA_TICKETS = 25,      // ... and its merge tickets (zeroed, self-resetting)
-  // 30 .. 32: two owners.  ns_moe.hip's grouped mul_mat_id (ids / gathered fp16 rows / raw products) and the device route's prompt-sized
+  // 30 .. 32: two owners.  ns_moe.cpp's grouped mul_mat_id (ids / gathered fp16 rows / raw products) and the device route's prompt-sized
   // window (fp16 shadows of a norm's, the attention's, the FFN's output; ns_route_fuse.cpp).  Shared safely, see above: the grouped path
   // synchronises its stream and is never captured, a window's shadows are written and read by launches of that one window
   // (the route's four keep the names its planner and tests/tools/route_fuse_main.cpp have always used)
@@ -257,11 +258,11 @@ enum ScratchSlot : int {
   SLOT_MOE_PRODUCTS = 32,
   kSlotFfn16 = 32,
   kSlotRopeTab = 33,   // ns_route_exec.cpp: RoPE angle table of XK_QKV_ROPE launches
-  SLOT_MOE_INTER = 34,        // ns_moe.hip ns_hip_moe_ffn_silu: the fused launches' intermediate
+  SLOT_MOE_INTER = 34,        // ns_moe.cpp ns_hip_moe_ffn_silu: the fused launches' intermediate
   SLOT_MOE_T1 = 35,           // ... and its composition's three temporaries
   SLOT_MOE_T2 = 36,
   SLOT_MOE_T3 = 37,
-  SLOT_MOE_PAIR_INTS = 38,    // ns_moe.hip, the grouped pass of the block entries: gathered position -> source row, pair -> position
+  SLOT_MOE_PAIR_INTS = 38,    // ns_moe.cpp, the grouped pass of the block entries: gathered position -> source row, pair -> position
   SLOT_MOE_PAIR_ROWS16 = 39,  // ... the pairs' activation rows in group order, fp16 [pairs + 1][k]
   SLOT_MOE_PAIR_INTER16 = 40, // ... act(gate) * up of every pair, fp16 [pairs + 1][ff]
   SLOT_MOE_PAIR_Y = 41,       // ... the down products, fp32 [pairs + 1][d_out]
@@ -301,10 +302,10 @@ struct HostScope {
 void kv_mirrors_clear();  // ns_kvcache.hip: drops the device mirrors of library-managed kv caches (ns_hip_cache_clear)
 void set_i8_tile(int tile);     // ns_i8ref.hip: workgroup tile of i8mfma2_kernel (0 = by size)
 void set_i8_mfma_gen(int gen);  // ns_i8ref.hip: 2 = i8mfma2_kernel for nibble containers (default), 1 = i8mfma_kernel everywhere
-void set_moe_tuning(int what, int value);  // ns_moe.hip: row threshold of what = 0 the decode kernel (m <= value), 1 the grouped path (m >= value); 0 = default, < 0 = off
-void set_moe_ffn_grouped_rows(int rows);  // ns_moe.hip: rows from which the block entries take the grouped pass; 0 = default ("moe_grouped_rows"'s), < 0 = never
-void set_moe_ffn_fused(int on);  // ns_moe.hip: ns_hip_moe_ffn_silu takes 1 the fused launches inside their envelope, 0 always the composition, -1 the default
-// ns_moe.hip: the router's fp16 exponential table (ns_hip_moe_route) on the current device, built on the host and uploaded at the first call
+void set_moe_tuning(int what, int value);  // ns_moe.cpp: row threshold of what = 0 the decode kernel (m <= value), 1 the grouped path (m >= value); 0 = default, < 0 = off
+void set_moe_ffn_grouped_rows(int rows);  // ns_moe.cpp: rows from which the block entries take the grouped pass; 0 = default (NS_MOE_GROUPED_ROWS if set, else 32 - not "moe_grouped_rows"), < 0 = never
+void set_moe_ffn_fused(int on);  // ns_moe.cpp: ns_hip_moe_ffn_silu takes 1 the fused launches inside their envelope, 0 always the composition, -1 the default
+// ns_moe_router.hip: the router's fp16 exponential table (ns_hip_moe_route) on the current device, built on the host and uploaded at the first call
 // (an expert group's creation, ns_hip_warm_up, a route call outside a stream capture); nullptr + error string when it cannot be made.
 // build = false: the table if it exists already, else nullptr (a caller inside a capture: the upload is synchronous)
 const uint16_t* moe_exp_table(bool build = true);

@@ -1,5 +1,5 @@
 // ns_dev.h — device-side helpers shared by the gfx950 kernels of libns_hip.so (ns_kernels.hip, ns_gemv.hip, ns_gemvs.hip, ns_gemm2.hip, ns_gemm3.hip,
-// ns_moe.hip, ns_i8ref.hip, ns_i8g2.hip): code -> fp16 converters, raw scale / zero-point records, buffer-descriptor loads, the output
+// ns_moe_loop.hip, ns_moe_rows.hip, ns_i8ref.hip, ns_i8g2.hip): code -> fp16 converters, raw scale / zero-point records, buffer-descriptor loads, the output
 // epilogue (epi_apply), the slot loop of the prefetch rings (NS_FOR_SLOTS).  The host side of a launch is in ns_launch.h.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -12,6 +12,7 @@
 
 #include "ns_common.h"
 #include "ns_dev.h"
+#include "ns_moe.h"  // MoeExpertRow: one row of an expert group's device table
 
 namespace ns {
 
@@ -58,13 +59,6 @@ struct GemvRope {
   float* v32;
   long long k32_head, k32_dim, k32_tok, v32_head, v32_dim, v32_tok;
   uint32_t* ovf;
-};
-
-// one row of an expert group's device table (ns_moe.hip: MoeExpert — same layout)
-struct MoeExpertRow {
-  const uint8_t* codes;
-  const uint8_t* scales;
-  const int8_t* zps;
 };
 
 struct GemvParams {

@@ -267,7 +267,7 @@ Miss plan_all(Ctx& c) {
   p.f8 = f8_consts(w0->qtype);
   if (a.moe) {
     const MoeRoute& r = *a.moe;
-    p.moe_table = static_cast<const MoeExpertRow*>(r.table), p.moe_table1 = static_cast<const MoeExpertRow*>(r.table1);
+    p.moe_table = r.table, p.moe_table1 = r.table1;
     p.moe_id = r.id, p.moe_n = r.n_as, p.moe_w = r.w;
     p.moe_nsel = uint32_t(r.nsel);
     p.moe_sel_mul = (65536u + p.moe_nsel - 1u) / p.moe_nsel;

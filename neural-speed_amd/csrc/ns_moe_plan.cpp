@@ -1,20 +1,49 @@
-// ns_moe_plan.cpp — which gathered row every (token row, selection) pair of a MoE block call gets: moe_pair_plan, a pure function of the id
-// table (no HIP call, no environment, no state).  ns_moe.hip uploads what it says; tests/test_moe_plan.py checks it on the CPU against the
-// rule written out independently.
+// ns_moe_plan.cpp — the decisions of ns_moe_plan.h as pure functions (no HIP call, no environment, no state); tests/test_moe_plan.py checks
+// them on the CPU against the rules written out independently.
 #include "ns_moe_plan.h"
+
+#include <algorithm>
 
 namespace ns {
 
-bool moe_pair_plan(const int32_t* ids, int ids_stride, int m, int n_used, int n_as, MoePairPlan* plan) {
+MoeMmPlan moe_mm_plan(const MoeKnobs& kn, const MoeFacts& f) {
+  MoeMmPlan p;
+  p.grouped.tried = kn.grouped_rows > 0 && f.m >= kn.grouped_rows && !f.capturing;  // (the host reads the ids)
+  // no activation shuffle, K in 64s; fp8: the tiled kernel takes it from 65 rows, and only experts inside its range rule
+  p.grouped.refused = f.shuf || f.k % 64 || (f.gate_f8 && (f.m <= 64 || !f.all_tiled_f8));
+  p.min_group_rows = f.gate_f8 ? 17 : 0;
+  p.decode.tried = f.m <= kn.gemv_rows;
+  p.decode.refused = !f.single_span || f.gate_f8;
+  return p;
+}
+
+MoeFfnPlan moe_ffn_plan(const MoeKnobs& kn, const MoeFacts& f) {
+  MoeFfnPlan p;
+  p.fused.tried = kn.ffn_fused != 0 && f.m <= kn.gemv_rows;
+  // (ff & 3: the rows of the fp32 intermediate must stay 16-byte aligned; an fp8 up group is left to launch_gemv's one-format rule)
+  p.fused.refused = f.gate_f8 || f.down_f8 || !f.single_span || (f.ff & 3) || !moe_pairs_fit_grid(f.m, f.n_used);
+  p.grouped.tried = kn.ffn_grouped_rows > 0 && f.m >= kn.ffn_grouped_rows && !f.capturing;
+  // (a gate / up pair launch needs one format)
+  p.grouped.refused = f.gate_f8 || f.up_f8 || f.down_f8 || f.k % 64 || f.ff % 64 || !f.gate_up_one_format;
+  return p;
+}
+
+bool moe_pairs_fit_grid(int m, int n_used) { return int64_t(m) * n_used < 65536 / std::max(n_used, 1); }
+bool moe_rows_addressable(size_t rows, int k, int ff, int dn) { return rows * size_t(std::max(k, std::max(ff, dn))) < (size_t(1) << 31); }
+
+bool moe_pair_plan(const int32_t* ids, int ids_stride, int m, int n_used, int n_as, MoePairPlan* plan, int min_group_rows) {
   if (!ids || !plan || m < 1 || n_used < 1 || n_as < 1 || ids_stride < n_used || int64_t(m) * n_used > (int64_t(1) << 30)) return false;
-  MoePairPlan& p = *plan;
   const auto in_range = [n_as](int32_t e) { return e >= 0 && e < n_as; };
-  p.count.assign(size_t(n_as), 0);
+  std::vector<int32_t> count(size_t(n_as), 0);
   for (int t = 0; t < m; t++)
     for (int i = 0; i < n_used; i++) {
       const int32_t e = ids[size_t(t) * ids_stride + i];
-      if (in_range(e)) p.count[e]++;
+      if (in_range(e)) count[e]++;
     }
+  for (int e = 0; e < n_as; e++)
+    if (count[e] > 0 && count[e] < min_group_rows) return false;
+  MoePairPlan& p = *plan;
+  p.count.swap(count);
   p.offset.assign(size_t(n_as), 0);
   p.launch_rows.assign(size_t(n_as), 0);
   int32_t at = 0;

@@ -1,5 +1,6 @@
-// ns_moe_plan.h — the (row, selection) pair layout of the MoE block's grouped pass (ns_moe.hip: ns_hip_moe_ffn_silu / _gelu at prompt size).
-// Plain C++: no HIP type, no library header — ns_moe_plan.cpp compiles with any host compiler (tests/tools/moe_plan_main.cpp, tests/test_moe_plan.py).
+// ns_moe_plan.h — what the mixture-of-experts family decides on the host, as values: which server takes a call (moe_mm_plan, moe_ffn_plan)
+// and the (row, selection) pair layout both grouped forms gather by (moe_pair_plan).  Plain C++: no HIP type, no library header — it builds
+// with any host compiler (tests/tools/moe_plan_main.cpp, tests/test_moe_plan.py).  ns_moe.cpp fills knobs and facts and follows the plan.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -7,9 +8,63 @@
 
 namespace ns {
 
+// Every tunable the family reads, resolved by moe_knobs() (ns_moe.cpp, the only reader): a non-zero tuning key wins, else the environment
+// variable (read once per process), else the built-in value.
+struct MoeKnobs {
+  int gemv_rows = 8;          // "moe_gemv_rows" / NS_MOE_GEMV_ROWS: the decode launches and the block's fused launches serve m <= this; <= 0 = never
+  int grouped_rows = 32;      // "moe_grouped_rows" / NS_MOE_GROUPED_ROWS: ns_hip_mul_mat_id's grouped path serves m >= this; <= 0 = never
+  int ffn_grouped_rows = 32;  // "moe_ffn_grouped_rows", else NS_MOE_GROUPED_ROWS, else 32 (NOT "moe_grouped_rows"): the block's grouped pass; <= 0 = never
+  int ffn_fused = -1;         // "moe_ffn_fused": 0 = the block never takes its fused launches; 1 / -1 (default) = inside their envelope
+};
+
+// What a decision needs from the weights and the call.  ns_hip_mul_mat_id describes its one group as `gate` (k = its K, ff = its N).
+struct MoeFacts {
+  bool gate_f8 = false, up_f8 = false, down_f8 = false;  // the group's weight kind is fp8 (all a decision asks about a kind)
+  int k = 0, ff = 0, dn = 0;                              // gate / up: [ff][k], down: [dn][ff]
+  int n_as = 0, n_used = 1, m = 0;
+  bool single_span = true;   // every group's records, scales and zero points lie in one allocation (the decode kernel's addressing)
+  bool shuf = false;         // an activation shuffle (act-order weights)
+  bool all_tiled_f8 = true;  // fp8 only: the tiled kernel takes EVERY expert of the group (gemm3_takes)
+  bool gate_up_one_format = true;
+  bool capturing = false;    // the stream is being captured: nothing may read the ids on the host
+};
+
+// One server of a call.  tried: the row thresholds and the capture state admit it; refused: its static envelope excludes the call (the
+// reasons stand beside the conditions in ns_moe_plan.cpp).  A candidate that is offered() may still hand the call on at run time.
+struct MoeCandidate {
+  bool tried = false, refused = false;
+  bool offered() const { return tried && !refused; }
+};
+
+// ns_hip_mul_mat_id: grouped path, decode launches, loop kernel — the last takes every call.  At run time the grouped path hands the call on
+// when a populated expert has fewer than min_group_rows rows, without scratch, and when launch_gemm2 answers hipErrorNotSupported; the decode
+// launches when launch_gemv does so for row 0.  ns_hip_moe_stats: [0] / [1] / [2] count the calls grouped / decode / loop served; [3] every
+// grouped candidate that was TRIED and did not serve, refused here or at run time alike (never a call below the threshold or being captured).
+struct MoeMmPlan {
+  MoeCandidate grouped, decode;
+  int min_group_rows = 0;  // of the grouped path: 17 for fp8 experts (the tiled kernel's fp8 range), else 0
+};
+MoeMmPlan moe_mm_plan(const MoeKnobs& kn, const MoeFacts& f);
+
+// The block entries: fused decode launches, grouped pass, composition of ns_hip_mul_mat_id calls — the last takes every call.  At run time
+// the fused launches hand the call on without scratch and when launch_gemv answers hipErrorNotSupported to the gate / up or the first down
+// launch; the grouped pass when moe_pair_plan refuses the table, when !moe_rows_addressable, without scratch and when launch_gemm2 answers
+// hipErrorNotSupported.  dOut is untouched in each case.  ns_hip_moe_ffn_stats: [0] / [1] / [3] count the calls fused / composition / grouped
+// served; [2] counts fused LAUNCHES: 1 + n_used of a served call, and 1 when the gate / up launch went out and the first down launch refused.
+struct MoeFfnPlan {
+  MoeCandidate fused, grouped;
+};
+MoeFfnPlan moe_ffn_plan(const MoeKnobs& kn, const MoeFacts& f);
+
+// the fused launches put the pairs along grid.y and divide by n_used with a 16-bit reciprocal (GemvParams::moe_sel_mul)
+bool moe_pairs_fit_grid(int m, int n_used);
+// the tiled GEMM indexes the gathered buffers with 32-bit element offsets: rows x the widest of them stays below 2^31
+bool moe_rows_addressable(size_t rows, int k, int ff, int dn);
+
 // Pair (t, i) is selection i of token row t, its expert is ids[t * ids_stride + i].  The pairs whose id lies in [0, n_as) are laid out in
 // GROUP ORDER: expert 0's pairs first, then expert 1's, ...; inside a group by (t, i) ascending (a stable counting sort).  A gathered
-// position j in [0, pairs) is one row of the fp16 activations, of the fp16 intermediate and of the fp32 down products.
+// position j in [0, pairs) is one row of the fp16 activations, of the fp16 intermediate and of the fp32 products.  ns_hip_mul_mat_id's
+// grouped path is the n_used = 1 case over the id column it reads back.
 struct MoePairPlan {
   int pairs = 0;                     // pairs with an id in range = gathered rows
   std::vector<int32_t> offset;       // [n_as] first gathered position of expert e's group (consecutive: offset[e + 1] = offset[e] + count[e])
@@ -23,7 +78,7 @@ struct MoePairPlan {
   std::vector<int32_t> pos;          // [m * n_used] gathered position of pair t * n_used + i; -1: its id is outside [0, n_as), it is in no group
 };
 
-// false (plan untouched): m, n_used or n_as below 1, ids_stride below n_used, or more than 2^30 pairs
-bool moe_pair_plan(const int32_t* ids, int ids_stride, int m, int n_used, int n_as, MoePairPlan* plan);
+// false (plan untouched): m, n_used or n_as below 1, ids_stride below n_used, over 2^30 pairs, or a populated group below min_group_rows pairs
+bool moe_pair_plan(const int32_t* ids, int ids_stride, int m, int n_used, int n_as, MoePairPlan* plan, int min_group_rows = 0);
 
 }  // namespace ns

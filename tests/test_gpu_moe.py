@@ -1,4 +1,4 @@
-"""Expert-indexed matmul with device-side routing (csrc/ns_moe.hip) against the reference semantics of
+"""Expert-indexed matmul with device-side routing (csrc/ns_moe.cpp, csrc/ns_moe_loop.hip) against the reference semantics of
 ne_compute_forward_mul_mat_id_q_f32_bestla (ne_layers.c:7783-7916): dst[t] = src1[t] . W[ids[t][id]], one
 bestla_f32f32_forward per (token, expert) — restated with the oracle's fp64 product per row."""
 import ctypes as C

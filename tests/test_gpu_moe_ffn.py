@@ -1,4 +1,4 @@
-"""ns_hip_moe_ffn_silu (csrc/ns_moe.hip, gemv_kernel XV = 4): out[t] = sum_i w[t][i] * down_e(silu(gate_e(a_t)) * up_e(a_t)), e = ids[t][i] —
+"""ns_hip_moe_ffn_silu (csrc/ns_moe.cpp, gemv_kernel XV = 4): out[t] = sum_i w[t][i] * down_e(silu(gate_e(a_t)) * up_e(a_t)), e = ids[t][i] —
 n_used x { ne_mul_id_ffn_silu ; mul(weights) ; add } of the reference (llama.cpp:641-679) — against the oracle's fp64 products per row
 and against the three-call ns_hip_mul_mat_id composition on the same inputs; which path served a call is read from
 ns_hip_moe_ffn_stats."""

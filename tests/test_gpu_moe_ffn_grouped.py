@@ -1,4 +1,4 @@
-"""The grouped pass of ns_hip_moe_ffn_silu (csrc/ns_moe.hip moe_ffn_grouped, csrc/ns_moe_plan.cpp): from "moe_ffn_grouped_rows" rows a call
+"""The grouped pass of ns_hip_moe_ffn_silu (csrc/ns_moe.cpp ffn_grouped, csrc/ns_moe_plan.cpp): from "moe_ffn_grouped_rows" rows a call
 outside a capture sorts all (row, selection) pairs by expert on the host, gathers their rows once, runs one fused gate / up and one down
 launch of the tiled GEMM per populated expert and combines the products with the routing weights in one launch.  Checked against the
 oracle's fp64 products and against the composition on the same inputs (the same entry with the tuning key negative); which path served a

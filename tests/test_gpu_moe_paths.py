@@ -1,4 +1,4 @@
-"""ns_hip_mul_mat_id (csrc/ns_moe.hip), every way it serves a call — the decode kernel (one gemv_kernel launch per row, expert picked on
+"""ns_hip_mul_mat_id (csrc/ns_moe.cpp), every way it serves a call — the decode kernel (one gemv_kernel launch per row, expert picked on
 the device), the per-row loop kernel (moe_gemv_kernel<KIND>) and the grouped path (rows sorted by expert on the host, one tiled GEMM per
 expert, scatter + epilogue) — each PINNED with ns_hip_set_tuning("moe_gemv_rows" / "moe_grouped_rows") and CONFIRMED with the deltas of
 ns_hip_moe_stats, every row against the oracle's fp64 product with that row's expert.

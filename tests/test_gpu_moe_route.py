@@ -1,4 +1,4 @@
-"""ns_hip_moe_route (csrc/ns_moe.hip): the router's tail soft_max -> top_k -> get_rows -> sum_rows -> div of the reference graph
+"""ns_hip_moe_route (csrc/ns_moe_router.hip): the router's tail soft_max -> top_k -> get_rows -> sum_rows -> div of the reference graph
 (models/llama/llama.cpp:631-638) in one launch, against the reference's arithmetic restated in numpy operation by operation
 (ne_compute_forward_soft_max_f32, ne_layers.c:8887-8954; table fill :745; sum_rows :5972; ne_vec_div_f32): x - max in fp32, rounded to
 fp16, table_exp_f16 (built here from the C library's expf - the host libm the library used), double sum, float(1 / sum), fp32 multiply;

@@ -1,4 +1,9 @@
-"""moe_pair_plan (neural-speed_amd/csrc/ns_moe_plan.cpp) lays out the (token row, selection) pairs of a MoE block call for the grouped pass of
+"""The host decisions of the mixture-of-experts family (neural-speed_amd/csrc/ns_moe_plan.cpp), checked without a GPU.
+
+moe_mm_plan / moe_ffn_plan say which server takes a call of ns_hip_mul_mat_id / of the block entries: the program's `plans` mode prints them
+for a table of (knobs, facts), and the rule of ns_moe_plan.h is restated here independently (want_mm, want_ffn).
+
+moe_pair_plan lays out the (token row, selection) pairs of a MoE block call for the grouped pass of
 ns_hip_moe_ffn_silu / _gelu: which gathered row every pair gets, where every expert's group starts, how many rows its GEMMs are launched
 with.  A host program (tests/tools/moe_plan_main.cpp, nothing launched) prints the plan for a list of id tables; the rule it must follow -
 ns_moe_plan.h - is restated here independently, as properties of the printed layout.  The program is plain C++: it is built once with the
@@ -62,8 +67,8 @@ def program_input():
     return "\n".join(lines) + "\n"
 
 
-def run_program(exe):
-    out = subprocess.run([exe], input=program_input(), check=True, capture_output=True, text=True, timeout=120)
+def run_program(exe, args=(), text=None):
+    out = subprocess.run([exe] + list(args), input=program_input() if text is None else text, check=True, capture_output=True, text=True, timeout=120)
     assert out.stderr == "", out.stderr
     plans = []
     for line in out.stdout.splitlines():
@@ -80,14 +85,19 @@ def run_program(exe):
 
 
 @pytest.fixture(scope="module")
-def plans(tmp_path_factory):
+def program(tmp_path_factory):
     hipcc = compiler()
     if not hipcc:
         pytest.skip("the library's compiler is not installed")
     exe = str(tmp_path_factory.mktemp("moe_plan") / "moe_plan")
     subprocess.run([hipcc, "-std=c++20", "-x", "hip", "--offload-arch=gfx950", "--cuda-host-only", "-Wall", "-Werror", "-I", CSRC] + SOURCES + ["-o", exe],
                    check=True, capture_output=True, text=True, timeout=300)
-    return run_program(exe)
+    return exe
+
+
+@pytest.fixture(scope="module")
+def plans(program):
+    return run_program(program)
 
 
 def check_plan(name, ids, n_as, p):
@@ -148,7 +158,7 @@ def test_the_cases_cover_what_they_are_named_for(plans):
     assert len(count("n_as_64")) == 64 and by_name["n_used_8"][0][1].shape[1] == 8
 
 
-def test_the_program_is_clean_under_the_sanitizers(tmp_path, plans):
+def test_the_program_is_clean_under_the_sanitizers(tmp_path, program, plans):
     gxx = shutil.which("g++")
     if not gxx:
         pytest.skip("no g++")
@@ -156,3 +166,169 @@ def test_the_program_is_clean_under_the_sanitizers(tmp_path, plans):
     subprocess.run([gxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                     "-I", CSRC] + SOURCES + ["-o", exe], check=True, capture_output=True, text=True, timeout=300)
     assert run_program(exe) == plans
+    assert run_program(exe, MIN17[0], MIN17[1]) == run_program(program, MIN17[0], MIN17[1])
+    assert run_decisions(exe) == run_decisions(program)
+
+
+# ---- the layout under ns_hip_mul_mat_id's grouped path: one id column (n_used = 1), a floor on the rows of a populated group -------------------
+def column_tables():
+    """(name, id column, n_as): lone last groups with out-of-range rows behind them in the old order, as ns_hip_mul_mat_id meets them"""
+    t = []
+    t.append(("lone_last_then_bad", [0, 0, 1, -1, 3, 4, 1, 0], 4))            # expert 3: one row, the last group; ids -1 and n_as present
+    t.append(("lone_last_is_expert_1_then_bad", [0, 9, 0, 1, -1], 4))         # the last POPULATED group is not the last expert
+    t.append(("lone_groups_to_the_end_then_bad", [-1, 1, 2, 3, 4, 0, 0], 4))
+    t.append(("only_a_lone_group_and_bad", [-1, 2, 7], 4))
+    return [(n, np.asarray(c, np.int64).reshape(-1, 1), a, 1) for n, c, a in t]
+
+
+def test_one_column_tables_with_a_lone_last_group_followed_by_out_of_range_rows(program):
+    tabs = column_tables()
+    text = "".join("%d 1 %d 1 %s\n" % (len(ids), n_as, " ".join(str(int(v)) for v in ids.reshape(-1))) for _, ids, n_as, _ in tabs)
+    got = run_program(program, text=text)
+    assert len(got) == len(tabs)
+    for (name, ids, n_as, _), p in zip(tabs, got):
+        assert p is not None, name
+        check_plan(name, ids, n_as, p)
+        last = max(e for e in range(n_as) if p["count"][e])
+        assert p["count"][last] == 1 and p["offset"][last] + 1 == p["pairs"], name      # the lone last group borrows ...
+        assert p["src_row"][p["pairs"]] == -1, name                                      # ... the zero padding row, never an out-of-range row
+        assert [t for t in range(len(ids)) if p["pos"][t] < 0] == [t for t in range(len(ids)) if not 0 <= ids[t, 0] < n_as], name
+
+
+def _column(counts):
+    return [e for e, c in enumerate(counts) for _ in range(c)]
+
+
+MIN17_TABLES = [("group_of_16", _column([20, 16, 0, 17]), 4, False), ("group_of_17", _column([17, 0, 40, 17]), 4, True),
+                ("group_of_1", _column([30, 1]) + [-1], 2, False), ("empty_groups_do_not_count", _column([0, 0, 17]) + [5], 3, True)]
+MIN17 = (["min_group_rows", "17"], "".join("%d 1 %d 1 %s\n" % (len(c), n_as, " ".join(map(str, c))) for _, c, n_as, _ in MIN17_TABLES))
+
+
+def test_min_group_rows_refuses_a_populated_group_below_it(program):
+    got = run_program(program, MIN17[0], MIN17[1])
+    assert [p is not None for p in got] == [ok for _, _, _, ok in MIN17_TABLES]
+    for (name, col, n_as, ok), p in zip(MIN17_TABLES, got):
+        if ok:
+            check_plan(name, np.asarray(col, np.int64).reshape(-1, 1), n_as, p)
+    assert all(p is not None for p in run_program(program, text=MIN17[1]))      # without the floor every one of them is laid out
+
+
+# ---- which server takes a call ---------------------------------------------------------------------------------------------------------------
+ROWS = [1, 8, 9, 31, 32, 33, 64, 65]
+KNOBS = dict(gemv_rows=8, grouped_rows=32, ffn_grouped_rows=32, ffn_fused=-1)          # the defaults, resolved
+FACTS = dict(gate_f8=0, up_f8=0, down_f8=0, k=128, ff=128, dn=128, n_as=8, n_used=2, m=1, single_span=1, shuf=0, all_tiled_f8=1,
+             gate_up_one_format=1, capturing=0)
+ORDER = ["gemv_rows", "grouped_rows", "ffn_grouped_rows", "ffn_fused", "gate_f8", "up_f8", "down_f8", "k", "ff", "dn", "n_as", "n_used", "m",
+         "single_span", "shuf", "all_tiled_f8", "gate_up_one_format", "capturing"]
+
+
+def decisions():
+    """(entry, knobs + facts) of every case"""
+    cases = []
+
+    def add(entry, **kw):
+        d = dict(KNOBS, **FACTS)
+        assert set(kw) <= set(d)
+        d.update(kw)
+        cases.append((entry, d))
+
+    for entry in ("mm", "ffn"):
+        for m in ROWS:
+            for cap in (0, 1):
+                add(entry, m=m, capturing=cap)
+            # every threshold at 0 (a resolved 0 - the environment variable set to 0 - means never, like -1), at positive values and at -1;
+            # a tuning KEY of 0 never reaches the plan: moe_knobs() resolves it to the environment's value or the default above
+            for key in ("gemv_rows", "grouped_rows", "ffn_grouped_rows"):
+                for v in (0, 4, 16, 40, -1):
+                    add(entry, m=m, **{key: v})
+            for v in (0, 1, -1):
+                add(entry, m=m, ffn_fused=v)
+            add(entry, m=m, grouped_rows=-1, ffn_grouped_rows=16)       # the block's threshold is its own ...
+            add(entry, m=m, grouped_rows=16, ffn_grouped_rows=-1)       # ... in both directions
+            add(entry, m=m, shuf=1)
+            add(entry, m=m, k=96)
+            add(entry, m=m, single_span=0)
+            add(entry, m=m, ff=96)
+            add(entry, m=m, ff=130)
+            add(entry, m=m, gate_up_one_format=0)
+            for which in ("gate_f8", "up_f8", "down_f8"):
+                add(entry, m=m, **{which: 1})
+        for m in (64, 65):
+            for tiled in (0, 1):
+                add(entry, m=m, gate_f8=1, all_tiled_f8=tiled, capturing=0)
+    for n_used in (1, 2, 8):                                            # the fused launches' pair bound: m * n_used < 65536 / n_used
+        edge = (65536 // n_used + n_used - 1) // n_used                 # the first m that is too many
+        for m in (edge - 1, edge):
+            add("ffn", m=m, n_used=n_used, gemv_rows=1 << 20)
+    return cases
+
+
+def want_mm(d):
+    tried_g = d["grouped_rows"] > 0 and d["m"] >= d["grouped_rows"] and not d["capturing"]
+    refused_g = bool(d["shuf"] or d["k"] % 64 or (d["gate_f8"] and (d["m"] <= 64 or not d["all_tiled_f8"])))
+    tried_d = d["m"] <= d["gemv_rows"]
+    refused_d = bool(not d["single_span"] or d["gate_f8"])
+    return "grouped=%d,%d decode=%d,%d min_group_rows=%d" % (tried_g, refused_g, tried_d, refused_d, 17 if d["gate_f8"] else 0)
+
+
+def want_ffn(d):
+    tried_f = d["ffn_fused"] != 0 and d["m"] <= d["gemv_rows"]
+    refused_f = bool(d["gate_f8"] or d["down_f8"] or not d["single_span"] or d["ff"] % 4 or d["m"] * d["n_used"] >= 65536 // d["n_used"])
+    tried_g = d["ffn_grouped_rows"] > 0 and d["m"] >= d["ffn_grouped_rows"] and not d["capturing"]
+    refused_g = bool(d["gate_f8"] or d["up_f8"] or d["down_f8"] or d["k"] % 64 or d["ff"] % 64 or not d["gate_up_one_format"])
+    return "fused=%d,%d grouped=%d,%d" % (tried_f, refused_f, tried_g, refused_g)
+
+
+PREDICATES = [("fit 32767 1", 1), ("fit 65535 1", 1), ("fit 65536 1", 0), ("fit 16383 2", 1), ("fit 16384 2", 0), ("fit 1023 8", 1), ("fit 1024 8", 0),
+              ("addressable 131072 16383 64 64", 1), ("addressable 131072 16384 64 64", 0), ("addressable 131072 64 16384 64", 0),
+              ("addressable 131072 64 64 16384", 0), ("addressable 131071 64 64 16384", 1), ("addressable 1 128 128 128", 1)]
+
+
+def run_decisions(exe):
+    text = "".join("%s %s\n" % (entry, " ".join(str(int(d[k])) for k in ORDER)) for entry, d in decisions())
+    text += "".join(q + "\n" for q, _ in PREDICATES)
+    out = subprocess.run([exe, "plans"], input=text, check=True, capture_output=True, text=True, timeout=120)
+    assert out.stderr == "", out.stderr
+    return out.stdout.splitlines()
+
+
+def test_the_server_of_every_call_follows_the_rule(program):
+    cases, got = decisions(), run_decisions(program)
+    assert len(got) == len(cases) + len(PREDICATES)
+    for (entry, d), line in zip(cases, got):
+        assert line == (want_mm(d) if entry == "mm" else want_ffn(d)), (entry, d, line)
+    assert [int(x) for x in got[len(cases):]] == [w for _, w in PREDICATES]
+
+
+def test_the_default_thresholds_send_the_rows_where_the_documents_say(program):
+    """rows -> server at the default knobs, outside a capture, on weights every server takes: docs/kernels/other.md's path table"""
+    cases, got = decisions(), run_decisions(program)
+    served = {}
+    for (entry, d), line in zip(cases, got):
+        if d == dict(KNOBS, **dict(FACTS, m=d["m"])):
+            first, second = (kv.split("=")[1] == "1,0" for kv in line.split()[:2])
+            served[(entry, d["m"])] = ("grouped" if first else "decode" if second else "loop") if entry == "mm" else \
+                ("fused" if first else "grouped" if second else "composition")
+    assert [served[("mm", m)] for m in ROWS] == ["decode", "decode", "loop", "loop", "grouped", "grouped", "grouped", "grouped"]
+    assert [served[("ffn", m)] for m in ROWS] == ["fused", "fused", "composition", "composition", "grouped", "grouped", "grouped", "grouped"]
+
+
+def test_a_threshold_of_zero_or_below_turns_its_server_off(program):
+    """MoeKnobs: gemv_rows / grouped_rows / ffn_grouped_rows <= 0 = never, whatever the row count"""
+    cases, got = decisions(), run_decisions(program)
+    seen = 0
+    for (entry, d), line in zip(cases, got):
+        first, second = (kv.split("=")[1].split(",")[0] for kv in line.split()[:2])      # tried?
+        if entry == "mm":
+            grouped, small = first, second
+            off_g = d["grouped_rows"] <= 0
+        else:
+            small, grouped = first, second
+            off_g = d["ffn_grouped_rows"] <= 0
+        if off_g:
+            assert grouped == "0", (entry, d)
+            seen += 1
+        if d["gemv_rows"] <= 0:
+            assert small == "0", (entry, d)
+            seen += 1
+    assert seen >= 6 * len(ROWS)

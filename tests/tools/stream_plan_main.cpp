@@ -176,8 +176,8 @@ static void make_call(const Case& c, Call* out) {
   if (c.moe || c.feat == 4) {
     MoeRoute& r = x.moe;
     r = MoeRoute{};
-    r.table = at<const void>(0x90000000), r.id = at<const int32_t>(0x91000000), r.n_as = 8;
-    r.table1 = a.dual && c.mbrk != 1 ? at<const void>(0x92000000) : nullptr;
+    r.table = at<const MoeExpertRow>(0x90000000), r.id = at<const int32_t>(0x91000000), r.n_as = 8;
+    r.table1 = a.dual && c.mbrk != 1 ? at<const MoeExpertRow>(0x92000000) : nullptr;
     r.pairs = c.pairs, r.nsel = c.nsel, r.ids_stride = c.nsel, r.w = at<const float>(0x93000000), r.w_stride = c.nsel;
     r.a_stride = c.mbrk == 2 ? c.k + 2 : c.k, r.c_stride = c.n, r.d_stride = c.n + 32;
     a.moe = &r;
