@@ -255,6 +255,11 @@ int ns_hip_get_compute_mode(void);
  *                     selection) pairs sorted by expert on the host, one gather, one fused gate / up and one down GEMM per populated expert, one
  *                     weighted combine (0 = default, the same as "moe_grouped_rows": NS_MOE_GROUPED_ROWS in the environment, else 32;
  *                     negative = never: the composition serves such calls)
+ *   "moe_ffn_device_rows" ns_hip_moe_ffn_silu / _gelu: token rows up to which a call, captured or not, takes the device-grouped pass - the
+ *                     pairs sorted by expert ON THE DEVICE, no host read-back, five launches (0 = default: NS_MOE_FFN_DEVICE_ROWS in the
+ *                     environment, else never; the pass is opt-in)
+ *   "moe_ffn_chunk_rows" ... a cap of 1 .. 16 on the pairs one workgroup of that pass serves with one stream of their expert (0 = default:
+ *                     as many as the staging memory holds, at most 16; diagnostics: small shapes reach the chunk boundaries with it)
  * Returns 0, or -1 for an unknown key. */
 int ns_hip_set_tuning(const char* key, int value);
 /* Process-wide counts of attention launches by the kernel family that served them (every entry that ends in an attention launch counts, the
@@ -709,6 +714,21 @@ void ns_hip_moe_stats(uint64_t out[4]);
  * ns_hip_moe_ffn_stats (process-wide sums): [0] calls served by the fused launches, [1] calls served by the composition (a call that tried
  * the fused launches or the grouped pass and fell back counts here only), [2] launches issued for the calls of [0], [3] calls served by
  * the grouped pass.
+ * In between, opt-in - the device-grouped pass: up to "moe_ffn_device_rows" rows (default 0: never), captured or not, asked after the fused
+ * launches and before the grouped pass.  With experts other than fp8 in the decode kernel's addressing, gate / up groups of one format, d and
+ * ff whole k-steps of their formats (128 columns for 4-bit, 64 for 8-bit codes), at most 1024 (row, selection) pairs and outside the
+ * int8-reference compute mode, the call is FIVE launches and no host read: one workgroup sorts the pairs by expert (the layout of the
+ * grouped pass) and cuts every expert's group into chunks of as many rows as a workgroup can stage; one gather; one fused gate / up launch
+ * and one down launch of the decode kernel over the chunks, each workgroup streaming its chunk's expert once for all the chunk's rows; one
+ * combine, which alone writes dOut, in selection order as above.  Capturable; a replayed graph follows the ids.  Whatever it refuses is
+ * refused before anything is launched, and the next server takes the call.
+ * ns_hip_moe_ffn_stats_ex(out, n) fills n slots: [0 .. 3] as ns_hip_moe_ffn_stats, [4] calls served by the device-grouped pass, [5] launches
+ * it issued, [6] calls where it was tried and handed on; slots from 7 on read 0.
+ * ns_hip_moe_ffn_device_layout (diagnostics, not capturable) runs that pass's sort alone on m x n_used ids for the chunk sizes r_gu and r_dn
+ * (1 .. 16 each) and copies what it left on the device to the host: src_row [P] (token row of gathered position j, -1 behind the good
+ * pairs), pos [P] (gathered position of pair t * n_used + i, -1 for an id outside [0, n_as)), then per chunk size a list of 1 + 3 * S ints,
+ * S = (P + min(n_as, P) * (r - 1)) / r: the chunk count, then {expert, first position, rows} per chunk, {-1, 0, 0} behind them; P = m *
+ * n_used <= 1024.  Returns the ints written, or -1 (n_out too small, bad argument).
  *
  * ns_hip_moe_ffn_gelu — the same block with gelu(gate) * up: n_used x { ne_mul_id_ffn_gelu ; mul(weights) ; add } of the reference's Grok
  * graph (models/grok/grok.cpp:292-343, ne_layers.c:8113 / :8170).  The GeLU is the tanh form of every NS_EPI_GELU epilogue here
@@ -731,6 +751,9 @@ int ns_hip_moe_ffn_gelu(const float* dA, int lda, int m, const int32_t* dIds, in
                         int n_used, const ns_expert_group* gate, const ns_expert_group* up, const ns_expert_group* down,
                         float* dOut, int ldo, void* stream);
 void ns_hip_moe_ffn_stats(uint64_t out[4]);
+void ns_hip_moe_ffn_stats_ex(uint64_t* out, int n);
+int ns_hip_moe_ffn_device_layout(const int32_t* dIds, int ids_stride, int m, int n_used, int n_as, int r_gu, int r_dn, int32_t* out,
+                                 int n_out, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
  * Part 5 — tensor-parallel all-reduce over peer-mapped HBM.  The decode-sized fast path of

@@ -181,6 +181,9 @@ def lib():
         L.ns_hip_moe_ffn_gelu.argtypes = L.ns_hip_moe_ffn_silu.argtypes
         L.ns_hip_moe_ffn_stats.restype = None
         L.ns_hip_moe_ffn_stats.argtypes = [vp]
+        L.ns_hip_moe_ffn_stats_ex.restype = None
+        L.ns_hip_moe_ffn_stats_ex.argtypes = [vp, i]
+        L.ns_hip_moe_ffn_device_layout.argtypes = [vp, i, i, i, i, i, i, vp, i, vp]
         L.ns_hip_p2p_create.restype = vp
         L.ns_hip_p2p_create.argtypes = [i, i, sz, vp]
         L.ns_hip_p2p_connect.argtypes = [vp, vp]

@@ -104,6 +104,8 @@ const TuningKey kTuning[] = {
     {"moe_gemv_rows", [](int v) { set_moe_tuning(0, v); }},
     {"moe_grouped_rows", [](int v) { set_moe_tuning(1, v); }},
     {"moe_ffn_grouped_rows", set_moe_ffn_grouped_rows},  // ns_hip_moe_ffn_silu / _gelu: rows from which the grouped pass serves a call (0 = default, < 0 = never)
+    {"moe_ffn_device_rows", set_moe_ffn_device_rows},  // ns_hip_moe_ffn_silu / _gelu: rows up to which the device-grouped pass serves a call (0 = default: never)
+    {"moe_ffn_chunk_rows", set_moe_ffn_chunk_rows},    // ... a cap of 1 .. 16 on the rows of its chunks (0 = by LDS fit)
     {"moe_ffn_fused", set_moe_ffn_fused},  // ns_hip_moe_ffn_silu / _gelu: 0 = always the composition, 1 / -1 = the fused launches inside their envelope
     {"g3_min_m", set_gemm3_min_m},
     {"i8_tile", set_i8_tile},

@@ -189,6 +189,12 @@ struct MoeRoute {
   const float* w = nullptr;
   int w_stride = 0;
   long long a_stride = 0, c_stride = 0, d_stride = 0;
+  // Expert CHUNKS instead of pairs (gemv_kernel XV = 6, the block entries' device-grouped pass): `chunks` is the device list
+  // moe_pair_sort_kernel writes — its count, then {expert, first gathered position, rows} per chunk — and grid.y its `chunk_slots`, the
+  // host's bound of the count (moe_chunk_slots).  SmallMArgs: a16 = the fp16 rows in gathered order [pairs][lda], m = the most rows a chunk
+  // has, seg[0].c / .c16 = the outputs by gathered position (either may be null); id, w, nsel and the strides above are not read
+  const int32_t* chunks = nullptr;
+  int chunk_slots = 0;
 };
 // replayed device route (ns_route.cpp XK_QKV_ROPE; gemv_kernel only, one row): the fused QKV launch's RoPE epilogue (ns_qkv_rope) also stores k (rotated)
 // and v into the reference's fp32 cache cells, and its position — RoPE angle table aside, which a captured launch of its own fills — follows the graph's counter
@@ -266,6 +272,10 @@ enum ScratchSlot : int {
   SLOT_MOE_PAIR_ROWS16 = 39,  // ... the pairs' activation rows in group order, fp16 [pairs + 1][k]
   SLOT_MOE_PAIR_INTER16 = 40, // ... act(gate) * up of every pair, fp16 [pairs + 1][ff]
   SLOT_MOE_PAIR_Y = 41,       // ... the down products, fp32 [pairs + 1][d_out]
+  SLOT_MOE_DEV_INTS = 42,     // ns_moe.cpp, the device-grouped pass of the block entries: src_row, pos and the two chunk lists (MoeDevLayout)
+  SLOT_MOE_DEV_ROWS16 = 43,   // ... the pairs' activation rows in group order, fp16 [m * n_used][k]
+  SLOT_MOE_DEV_INTER16 = 44,  // ... act(gate) * up of every pair, fp16 [m * n_used][ff]
+  SLOT_MOE_DEV_Y = 45,        // ... the down products, fp32 [m * n_used][d_out]
 };
 void* stream_scratch(hipStream_t st, size_t bytes, int slot);
 void* stream_scratch_zeroed(hipStream_t st, size_t bytes, int slot);  // zero-filled when (re)allocated: self-resetting counters
@@ -304,6 +314,8 @@ void set_i8_tile(int tile);     // ns_i8ref.hip: workgroup tile of i8mfma2_kerne
 void set_i8_mfma_gen(int gen);  // ns_i8ref.hip: 2 = i8mfma2_kernel for nibble containers (default), 1 = i8mfma_kernel everywhere
 void set_moe_tuning(int what, int value);  // ns_moe.cpp: row threshold of what = 0 the decode kernel (m <= value), 1 the grouped path (m >= value); 0 = default, < 0 = off
 void set_moe_ffn_grouped_rows(int rows);  // ns_moe.cpp: rows from which the block entries take the grouped pass; 0 = default (NS_MOE_GROUPED_ROWS if set, else 32 - not "moe_grouped_rows"), < 0 = never
+void set_moe_ffn_device_rows(int rows);  // ns_moe.cpp: rows up to which the block entries take the device-grouped pass; 0 = default (NS_MOE_FFN_DEVICE_ROWS if set, else never)
+void set_moe_ffn_chunk_rows(int rows);   // ns_moe.cpp: cap of 1 .. 16 on the rows of a chunk of that pass; 0 = by LDS fit
 void set_moe_ffn_fused(int on);  // ns_moe.cpp: ns_hip_moe_ffn_silu takes 1 the fused launches inside their envelope, 0 always the composition, -1 the default
 // ns_moe_router.hip: the router's fp16 exponential table (ns_hip_moe_route) on the current device, built on the host and uploaded at the first call
 // (an expert group's creation, ns_hip_warm_up, a route call outside a stream capture); nullptr + error string when it cannot be made.

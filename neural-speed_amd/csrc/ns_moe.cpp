@@ -6,29 +6,36 @@
 #include <cstdlib>
 
 #include "ns_api_int.h"
+#include "ns_gemv.h"
 #include "ns_moe.h"
 #include "ns_moe_plan.h"
 
 namespace ns {
 // the tuning keys (ns_hip_set_tuning): 0 = the environment variable if set, else the built-in value ("moe_ffn_fused": -1)
-static std::atomic<int> g_gemv_rows{0}, g_grouped_rows{0}, g_ffn_grouped_rows{0}, g_ffn_fused{-1};
+static std::atomic<int> g_gemv_rows{0}, g_grouped_rows{0}, g_ffn_grouped_rows{0}, g_ffn_fused{-1}, g_ffn_device_rows{0}, g_ffn_chunk_rows{0};
 void set_moe_tuning(int what, int value) { (what == 0 ? g_gemv_rows : g_grouped_rows).store(value); }
 void set_moe_ffn_fused(int on) { g_ffn_fused.store(on < 0 ? -1 : (on != 0)); }
 void set_moe_ffn_grouped_rows(int rows) { g_ffn_grouped_rows.store(rows); }
-static std::atomic<uint64_t> g_moe_stats[4], g_moe_ffn_stats[4];  // ns_hip_moe_stats, ns_hip_moe_ffn_stats (ns_moe_plan.h)
+void set_moe_ffn_device_rows(int rows) { g_ffn_device_rows.store(rows); }
+void set_moe_ffn_chunk_rows(int rows) { g_ffn_chunk_rows.store(rows < 0 ? 0 : rows > kMoeChunkMaxRows ? kMoeChunkMaxRows : rows); }
+static std::atomic<uint64_t> g_moe_stats[4], g_moe_ffn_stats[7];  // ns_hip_moe_stats, ns_hip_moe_ffn_stats / _stats_ex (ns_moe_plan.h)
+static_assert(kMoeChunkALds == kGvMaxALds && kMoeChunkMaxRows == kGvMaxRows, "ns_moe_plan.h restates the decode kernel's staging limits");
 
 static MoeKnobs moe_knobs() {
   static const MoeKnobs env = [] {
     MoeKnobs k;
     if (const char* s = getenv("NS_MOE_GEMV_ROWS")) k.gemv_rows = atoi(s);
     if (const char* s = getenv("NS_MOE_GROUPED_ROWS")) k.grouped_rows = k.ffn_grouped_rows = atoi(s);
+    if (const char* s = getenv("NS_MOE_FFN_DEVICE_ROWS")) k.ffn_device_rows = atoi(s);
     return k;
   }();
   MoeKnobs k = env;
   if (const int v = g_gemv_rows.load()) k.gemv_rows = v;
   if (const int v = g_grouped_rows.load()) k.grouped_rows = v;
   if (const int v = g_ffn_grouped_rows.load()) k.ffn_grouped_rows = v;
+  if (const int v = g_ffn_device_rows.load()) k.ffn_device_rows = v;
   k.ffn_fused = g_ffn_fused.load();
+  k.ffn_chunk_rows = g_ffn_chunk_rows.load();
   return k;
 }
 
@@ -217,6 +224,64 @@ static int ffn_grouped(const MoeFfnCall& c) {
   return 0;
 }
 
+// The device-grouped pass (opt-in, any stream state): nothing is read on the host.  Five launches: moe_pair_sort_kernel lays the pairs out in
+// group order and cuts every group into chunks of up to R rows, for the R of each of the two K; one gather into fp16 rows; one GV_DUAL
+// launch of gemv_kernel's chunk form (XV = 6) over the gate / up chunk slots, whose epilogue writes the fp16 intermediate alone; one
+// GV_PLAIN launch over the down chunk slots; one combine, which alone writes out.  Both streaming launches are planned before the sort goes out.
+struct MoeDevLayout {  // the ints of SLOT_MOE_DEV_INTS: [src_row P | pos P | gate / up list 1 + 3 slots_gu | down list 1 + 3 slots_dn]
+  size_t pairs = 0;
+  int r_gu = 0, r_dn = 0, slots_gu = 0, slots_dn = 0;
+  MoeDevLayout(int m, int n_used, int n_as, int k, int gu_kstep, int ff, int dn_kstep, int cap) : pairs(size_t(m) * n_used) {
+    r_gu = moe_chunk_rows(k, gu_kstep, cap), r_dn = moe_chunk_rows(ff, dn_kstep, cap);
+    slots_gu = moe_chunk_slots(m, n_used, n_as, r_gu), slots_dn = moe_chunk_slots(m, n_used, n_as, r_dn);
+  }
+  size_t ints() const { return 2 * pairs + 2 + 3 * (size_t(slots_gu) + size_t(slots_dn)); }
+  MoeDevSort sort(const int32_t* ids, int ids_stride, int n_used, int n_as, int32_t* base) const {
+    int32_t* gu = base + 2 * pairs;
+    return MoeDevSort{ids, ids_stride, n_used, int(pairs), n_as, r_gu, r_dn, slots_gu, slots_dn, base, base + pairs, gu, gu + 1 + 3 * size_t(slots_gu)};
+  }
+};
+
+static int ffn_device_grouped(const MoeFfnCall& c, const MoeKnobs& kn) {
+  const ns_weight *wg = c.gate->experts[0], *wd = c.down->experts[0];
+  const int m = c.m, n_used = c.n_used, k = wg->k, ff = wg->n, dn = wd->n, n_as = int(c.gate->experts.size());
+  hipStream_t st = c.st;
+  const MoeDevLayout lay(m, n_used, n_as, k, wg->kstep_len, ff, wd->kstep_len, kn.ffn_chunk_rows);
+  const size_t P = lay.pairs;
+  int32_t* ints = scratch<int32_t>(st, lay.ints(), SLOT_MOE_DEV_INTS);
+  _Float16* ag = scratch<_Float16>(st, P * k, SLOT_MOE_DEV_ROWS16);
+  _Float16* inter = scratch<_Float16>(st, P * ff, SLOT_MOE_DEV_INTER16);
+  float* y = scratch<float>(st, P * dn, SLOT_MOE_DEV_Y);
+  if (!ints || !ag || !inter || !y) return 1;
+  const MoeDevSort so = lay.sort(c.ids, c.ids_stride, n_used, n_as, ints);
+  MoeRoute gu_route{c.gate->table, nullptr, n_as};
+  gu_route.table1 = c.up->table, gu_route.pairs = int(P), gu_route.chunks = so.chunks_gu, gu_route.chunk_slots = lay.slots_gu;
+  SmallMArgs gu{};
+  gu.a16 = ag, gu.lda = k, gu.m = lay.r_gu, gu.ldc = ff, gu.nseg = 2;
+  gu.seg[0] = {wg, nullptr, inter};  // (the fp16 output alone: the down launch stages fp16 rows)
+  gu.seg[1] = {c.up->experts[0], nullptr, nullptr};
+  gu.epilogue = c.act, gu.dual = true, gu.moe = &gu_route;
+  MoeRoute dn_route{c.down->table, nullptr, n_as};
+  dn_route.pairs = int(P), dn_route.chunks = so.chunks_dn, dn_route.chunk_slots = lay.slots_dn;
+  SmallMArgs dw{};
+  dw.a16 = inter, dw.lda = ff, dw.m = lay.r_dn, dw.ldc = dn, dw.nseg = 1, dw.epilogue = NS_EPI_NONE;
+  dw.seg[0] = {wd, y, nullptr};
+  dw.moe = &dn_route;
+  GemvPlan plan_gu = plan_gemv(gu), plan_dn = plan_gemv(dw);
+  if (plan_gu.refusal == hipErrorNotSupported || plan_dn.refusal == hipErrorNotSupported) return 1;
+  if (!hip_ok(plan_gu.refusal, c.name(" (device-grouped: gate / up plan)").c_str()) || !hip_ok(plan_dn.refusal, c.name(" (device-grouped: down plan)").c_str()))
+    return -1;
+  hipError_t er = launch_moe_pair_sort(so, st);
+  if (er == hipSuccess) er = launch_moe_gather(c.a, c.lda, so.src_row, int(P), k, ag, st);
+  if (er == hipSuccess) er = launch_gemv_planned(plan_gu, st);
+  if (er == hipSuccess) er = launch_gemv_planned(plan_dn, st);
+  if (er == hipSuccess) er = launch_moe_combine(y, so.pos, c.w, c.w_stride, m, n_used, dn, c.out, c.ldo, st);
+  if (!hip_ok(er, c.name(" (device-grouped)").c_str())) return -1;
+  g_moe_ffn_stats[4]++;
+  g_moe_ffn_stats[5] += 5;
+  return 0;
+}
+
 // one launch can serve both weights: the same quantization format and record strides (shapes are the caller's business)
 static bool one_format(const ns_weight* a, const ns_weight* b) {
   return same_quant(a, b) && a->qstride == b->qstride && a->sstride == b->sstride && a->zstride == b->zstride;
@@ -238,8 +303,13 @@ static int moe_ffn_block(const MoeFfnCall& c) {
   f.k = wg->k, f.ff = wg->n, f.dn = wd->n, f.n_as = int(c.gate->experts.size()), f.n_used = c.n_used, f.m = c.m;
   f.single_span = wg->single_span && wu->single_span && wd->single_span, f.gate_up_one_format = one_format(wg, wu);
   f.capturing = kn.ffn_grouped_rows > 0 && c.m >= kn.ffn_grouped_rows && stream_is_capturing(c.st);  // (asked where the plan looks at it)
+  f.gu_kstep = wg->kstep_len, f.dn_kstep = wd->kstep_len, f.i8_mode = ns_hip_get_compute_mode() == NS_COMPUTE_REF_INT8;
   const MoeFfnPlan pl = moe_ffn_plan(kn, f);
   int rc = pl.fused.offered() ? ffn_fused(c) : 1;
+  if (rc == 1 && pl.device.tried) {
+    rc = pl.device.refused ? 1 : ffn_device_grouped(c, kn);
+    if (rc == 1) g_moe_ffn_stats[6]++;
+  }
   if (rc == 1 && pl.grouped.offered()) rc = ffn_grouped(c);
   return rc == 1 ? ffn_composition(c) : rc;
 }
@@ -340,6 +410,31 @@ int ns_hip_moe_ffn_gelu(const float* dA, int lda, int m, const int32_t* dIds, in
 
 void ns_hip_moe_ffn_stats(uint64_t out[4]) {
   for (int i = 0; i < 4; i++) out[i] = g_moe_ffn_stats[i].load();
+}
+
+void ns_hip_moe_ffn_stats_ex(uint64_t* out, int n) {
+  for (int i = 0; out && i < n; i++) out[i] = i < 7 ? g_moe_ffn_stats[i].load() : 0;
+}
+
+int ns_hip_moe_ffn_device_layout(const int32_t* dIds, int ids_stride, int m, int n_used, int n_as, int r_gu, int r_dn, int32_t* out, int n_out,
+                                 void* stream) {
+  if (!have_device()) return -1;
+  if (!dIds || !out || m < 1 || n_used < 1 || n_used > ids_stride || n_as < 1 || int64_t(m) * n_used > kMoeDevMaxPairs || r_gu < 1 ||
+      r_gu > kMoeChunkMaxRows || r_dn < 1 || r_dn > kMoeChunkMaxRows)
+    return moe_fail("moe_ffn_device_layout: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  MoeDevLayout lay(m, n_used, n_as, 1, 1, 1, 1, 0);
+  lay.r_gu = r_gu, lay.r_dn = r_dn;
+  lay.slots_gu = moe_chunk_slots(m, n_used, n_as, r_gu), lay.slots_dn = moe_chunk_slots(m, n_used, n_as, r_dn);
+  if (size_t(n_out) < lay.ints()) return moe_fail("moe_ffn_device_layout: the output is too short");
+  int32_t* ints = scratch<int32_t>(st, lay.ints(), SLOT_MOE_DEV_INTS);
+  if (!ints) return moe_fail("moe_ffn_device_layout: scratch allocation failed");
+  if (!hip_ok(launch_moe_pair_sort(lay.sort(dIds, ids_stride, n_used, n_as, ints), st), "moe_ffn_device_layout")) return -1;
+  if (hipMemcpyAsync(out, ints, lay.ints() * 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+    (void)hipGetLastError();
+    return moe_fail("moe_ffn_device_layout: reading the layout failed");
+  }
+  return int(lay.ints());
 }
 
 }  // extern "C"

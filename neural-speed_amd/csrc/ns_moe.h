@@ -56,6 +56,15 @@ hipError_t launch_moe_weighted_add(float* out, int ldo, const float* x, int ldx,
                                    hipStream_t st);
 hipError_t launch_moe_combine(const float* y, const int32_t* pos, const float* w, int w_stride, int m, int n_used, int n, float* out, int ldo,
                               hipStream_t st);
+// ns_moe_group.hip — moe_pair_sort_kernel, one workgroup: the pair layout of moe_chunk_plan (ns_moe_plan.h) and its chunk lists for two chunk
+// sizes, from the ids on the device.  src_row, pos: [pairs]; a chunk list: its count, then {expert, first position, rows} x slots
+struct MoeDevSort {
+  const int32_t* ids;
+  int ids_stride, n_used, pairs, n_as;  // pairs = m * n_used <= kMoeDevMaxPairs
+  int r_gu, r_dn, slots_gu, slots_dn;   // rows per chunk and the host's bound of the chunk count (moe_chunk_slots), per list
+  int32_t *src_row, *pos, *chunks_gu, *chunks_dn;
+};
+hipError_t launch_moe_pair_sort(const MoeDevSort& a, hipStream_t st);
 
 }  // namespace ns
 

@@ -8,7 +8,11 @@ in the same graph form, on its fused launches and - "moe_ffn_fused" = 0 - on its
 From 32 tokens - or from grouped_rows=N tokens, which lowers "moe_ffn_grouped_rows" to N for that leg - a third leg times the block entry as
 plain calls (the grouped pass reads the ids on the host: no graph), wall clock around batches that end in a synchronisation, with the
 grouped pass on and - "moe_ffn_grouped_rows" negative - off: medians of interleaved batches again.
-usage: moe_bench.py [tokens=1] [act=silu|gelu] [grouped_rows=N]        (act: the block entry of the second and third leg)"""
+With device_rows=N (N >= tokens) a fourth leg times the block entry as graph replays - any token count: a captured stream never takes the
+grouped pass - on three servers: the composition (every key at its default: the behaviour without the device-grouped pass), the fused
+launches stretched to this token count ("moe_gemv_rows" = tokens) and the device-grouped pass ("moe_ffn_device_rows" = N): medians of
+interleaved replay batches, median [min ... max] per layer.
+usage: moe_bench.py [tokens=1] [act=silu|gelu] [grouped_rows=N] [device_rows=N]      (act: the block entry of the second to fourth leg)"""
 import ctypes as C, json, os, sys, time
 import numpy as np
 import torch
@@ -24,6 +28,7 @@ block_entry = L.ns_hip_moe_ffn_gelu if act_name == "gelu" else L.ns_hip_moe_ffn_
 act_f64 = (lambda x: 0.5 * x * (1.0 + np.tanh(0.7978845834732056 * (x + 0.044714998453855515 * x ** 3)))) if act_name == "gelu" else \
     (lambda x: x / (1.0 + np.exp(-x)))
 grouped_rows = int(opts["grouped_rows"]) if "grouped_rows" in opts else 0   # 0: the library's default threshold
+device_rows = int(opts["device_rows"]) if "device_rows" in opts else 0      # 0: no device-grouped leg
 n_as, d, ff, topk = 8, 4096, 14336, 2
 st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -192,6 +197,65 @@ if m >= 32 or (grouped_rows > 0 and m >= grouped_rows):
         hg, hu = nso.gemm_f64(a0p, hostp(wg[ex][1])), nso.gemm_f64(a0p, hostp(wu[ex][1]))
         refp += float(wts_p[0, sel]) * nso.gemm_f64((act_f64(hg) * hu).astype(np.float32), hostp(wd[ex][1]))
     prompt["grouped_parity_rel_l2_vs_fp64_oracle_token0"] = float("%.3g" % nso.rel_l2(out_p[:1].cpu().numpy(), refp))
+# the block entry on a captured stream: composition / stretched fused launches / device-grouped pass, interleaved replay batches
+device = {}
+if device_rows > 0:
+    assert m <= device_rows, "device_rows below the token count: the pass would not be tried"
+    wts_d = torch.rand((m, topk), device="cuda") + 0.25
+    out_d = torch.empty((m, d), device="cuda")
+
+    def device_chain(s):
+        for (wg, gg), (wu, gu), (wd, gd) in layers:
+            pkg.check(block_entry(a.data_ptr(), d, m, ids.data_ptr(), topk, wts_d.data_ptr(), topk, topk, gg, gu, gd, out_d.data_ptr(), d, s))
+
+    def stats_ex():
+        v = (C.c_uint64 * 7)()
+        L.ns_hip_moe_ffn_stats_ex(v, 7)
+        return [int(x) for x in v]
+
+    legs_d = (("composition", {}), ("fused_stretched", {b"moe_gemv_rows": m}), ("device_grouped", {b"moe_ffn_device_rows": device_rows}))
+    graphs_d, outs_d = {}, {}
+    for name, keys in legs_d:
+        for key, v in keys.items():
+            L.ns_hip_set_tuning(key, v)
+        device_chain(st)
+        torch.cuda.synchronize()
+        s0 = stats_ex()
+        gd_ = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gd_):
+            device_chain(C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        s1 = stats_ex()
+        device[name + "_calls"] = {"fused": s1[0] - s0[0], "composition": s1[1] - s0[1], "grouped": s1[3] - s0[3], "device_grouped": s1[4] - s0[4]}
+        for key in keys:
+            L.ns_hip_set_tuning(key, 0)
+        gd_.replay(); torch.cuda.synchronize()
+        outs_d[name] = out_d.clone()
+        graphs_d[name] = gd_
+    reps_d = 10
+    times_d = {k: [] for k in graphs_d}
+    for _ in range(7):
+        for k, gb in graphs_d.items():
+            gb.replay(); torch.cuda.synchronize()
+            e0.record()
+            for _ in range(reps_d):
+                gb.replay()
+            e1.record(); torch.cuda.synchronize()
+            times_d[k].append(e0.elapsed_time(e1) * 1e3 / reps_d / nlay)
+    for k, v in times_d.items():
+        device["us_per_layer_" + k] = {"median": round(float(np.median(v)), 1), "min": round(min(v), 1), "max": round(max(v), 1)}
+    device["act"], device["device_rows_key"] = act_name, device_rows
+    ref_d = outs_d["composition"].double()
+    for k in ("fused_stretched", "device_grouped"):
+        device[k + "_rel_l2_vs_composition"] = float("%.3g" % ((outs_d[k].double() - ref_d).norm() / ref_d.norm()).item())
+    # parity of the device-grouped leg's token 0 against the fp64 oracle over both selections
+    hostd = lambda t: (lambda b: (b.__setitem__(slice(None), t.cpu().numpy()), b)[1])(nso.aligned_bytes(t.numel()))
+    a0d, refd = a[:1].cpu().numpy(), np.zeros((1, d))
+    for sel in range(topk):
+        ex = int(ids_np[0, sel])
+        (wg, _), (wu, _), (wd, _) = layers[-1]
+        hg, hu = nso.gemm_f64(a0d, hostd(wg[ex][1])), nso.gemm_f64(a0d, hostd(wu[ex][1]))
+        refd += float(wts_d[0, sel]) * nso.gemm_f64((act_f64(hg) * hu).astype(np.float32), hostd(wd[ex][1]))
+    device["device_grouped_parity_rel_l2_vs_fp64_oracle_token0"] = float("%.3g" % nso.rel_l2(outs_d["device_grouped"][:1].cpu().numpy(), refd))
 # parity of the last layer's last selection (token 0): silu(a Wg) * (a Wu) then Wd, fp64 over the oracle's blobs
 (wg, _), (wu, _), (wd, _) = layers[-1]
 e = int(ids_np[0, topk - 1])
@@ -209,4 +273,4 @@ print(json.dumps({"what": "Mixtral-8x7B-shaped MoE FFN (8 x {14336x4096 gate, up
                   "hbm_GBps_over_touched_weights": round(touched / us / 1e3, 1), "tokens_per_s_of_32_moe_ffn_layers": round(m * 1e6 / (32 * us), 1),
                   "parity_rel_l2_vs_fp64_oracle_token0": float("%.3g" % par), "launches_per_layer": 3 * topk,
                   "grouped_by_expert": m >= 32 and os.environ.get("NS_MOE_GROUPED_ROWS", "32") != "0",
-                  "tflops": round(m * topk * 3 * 2.0 * d * ff / us / 1e6, 1), "moe_ffn_" + act_name: block, "moe_ffn_prompt": prompt}))
+                  "tflops": round(m * topk * 3 * 2.0 * d * ff / us / 1e6, 1), "moe_ffn_" + act_name: block, "moe_ffn_prompt": prompt, "moe_ffn_device": device}))
