@@ -5,7 +5,7 @@
  * and ne_compute_params, so they are compiled against the REFERENCE's headers (with -DNS_SYCL, the reference's own switch
  * for its device hooks: ne_layers.c:4252, :4568, :5633, :6405, :6592, :9247, :9912) and forward to libns_hip.so, which
  * exports the pointer-only half under the reference's names (bestla_create_device ... bestla_device_f32f32_forward,
- * csrc/ns_device.hip).  A maintainer adds this file + ne_bestla_hip_glue.c to the ne_layers target in place of
+ * csrc/ns_device*.{hip,cpp}).  A maintainer adds this file + ne_bestla_hip_glue.c to the ne_layers target in place of
  * core/layers/ne_bestla.cpp / ne_bestla_sycl.cpp.  params->dev_queue is a hipStream_t.
  */
 #include <assert.h>

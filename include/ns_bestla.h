@@ -487,7 +487,7 @@ int ns_hip_quant_pack_device(void* dBlob, const float* dW, size_t N, size_t K, s
                              void* stream);
 
 /* ---- Part 3a — the reference's device-backend set under its own names (ne_bestla.h:85-112, guarded there by NS_SYCL;
- * csrc/ns_device.hip).  The pointer-only functions are exported by libns_hip.so AS IS — a reference tree built with
+ * csrc/ns_device*.{hip,cpp}).  The pointer-only functions are exported by libns_hip.so AS IS — a reference tree built with
  * -DNS_SYCL binds to them — and the tensor-level ones (bestla_device_mul_f32 / _add_f32 / _elewise_f32 / _rms_norm_f32 /
  * _rope_f32 / _dup_f32 / _mha_f32) are glue/ne_bestla_hip_device.c over the ns_hip_* entries.  "queue" = hipStream_t. ---- */
 /* Threads: the device set is driven by ONE host thread at a time, as the reference's executor drives it (claimed nodes run with n_tasks = 1,

@@ -251,7 +251,7 @@ enum ScratchSlot : int {
   SLOT_GEMVS_TICKETS = 21,    // ns_gemvs.cpp: split-K tickets (zeroed, self-resetting)
   SLOT_ATTN_TICKETS = 22,     // ns_attn.cpp: merge tickets (zeroed, self-resetting)
   SLOT_ROPE_TAB = 23,         // ns_quant.hip: cos / sin table of launch_rope_qkv_append
-  SLOT_MHA_PARTIALS = 24,     // ns_device.hip device-layout attention (allocated ahead of a capture by ns_route.cpp): partials
+  SLOT_MHA_PARTIALS = 24,     // ns_device_mha.hip device-layout attention (allocated ahead of a capture by ns_route.cpp; sized by ns_device_plan.h): partials
   SLOT_MHA_TICKETS = 25,      // ... and its merge tickets (zeroed, self-resetting)
   // 30 .. 32: two owners.  ns_moe.cpp's grouped mul_mat_id (ids / gathered fp16 rows / raw products) and the device route's prompt-sized
   // window (fp16 shadows of a norm's, the attention's, the FFN's output; ns_route_fuse.cpp).  Shared safely, see above: the grouped path
@@ -375,7 +375,7 @@ hipError_t launch_rmsnorm(int norm_count, int norm_size, bool isrms, float eps, 
                           hipStream_t st, const float* gamma = nullptr, void* out16 = nullptr);
 hipError_t launch_norm_prep(int m, int n, const float* x, int ldx, const float* gamma, void* x16, float* ssq,
                             int ssq_stride, hipStream_t st);
-// Replay of the reference's device route (round 5, ns_device.hip "route"): a captured launch may take ONE moving value — a position, a
+// Replay of the reference's device route (round 5, ns_route.cpp): a captured launch may take ONE moving value — a position, a
 // context length, a cache address — as base + delta * (*k), k a device word the replayed graph increments once per token.  The
 // launchers below that have such a value (launch_rope: n_past, launch_dup: dst, the device-layout attention: seq_all) read this
 // thread-local; k == nullptr (always, outside a route capture) = the plain value.
@@ -457,6 +457,10 @@ hipError_t i8_quantize_for_decode(const float* a, int lda, const ns_weight* w, i
 hipError_t launch_i8ref(const float* a, int lda, const ns_weight* w, float* c, void* c16, int m, int ldc, int epilogue,
                         const float* d, int ldd, hipStream_t st, bool reuse_aq = false);
 hipError_t launch_silu(const float* x, float* y, size_t n, hipStream_t st);
+// ns_quant.hip, for the lazy peephole (ns_device_ops.hip): a norm / silu node and the multiply behind it in one launch that writes BOTH tensors
+hipError_t launch_rmsnorm_mul2(int norm_count, int norm_size, bool isrms, float eps, const float* in, float* plain, const float* gamma, float* out,
+                               hipStream_t st);
+hipError_t launch_silu_mul2(const float* x, const float* y, float* s, float* out, size_t n, int silu_first, hipStream_t st);
 // rope(q), rope(k) in place on adjacent rows + the K and V cache writes of one decode position in one launch (ns_route.cpp)
 hipError_t launch_rope_append(float* qk, int rows_front, int rows_k_first, int rows_k, int head_size, int n_past, int n_dims, int mode, float freq_base,
                               float freq_scale, float attn_factor, float ext_factor, float corr0, float corr1, const void* ksrc, void* kdst,

@@ -347,7 +347,7 @@ void bestla_f32f32_forward(float* activation, void* weiptr, float* output, int _
 }
 
 // The reference's model code asks these for every layer of every evaluation (llama.cpp:212, :609).  On its device route a weight tensor's data is the
-// storage record of bestla_device_load_storage, not a blob (first word all ones: no blob starts like that, csrc/ns_device.hip DeviceStorage) — refused
+// storage record of bestla_device_load_storage, not a blob (first word all ones: no blob starts like that, csrc/ns_device.h DeviceStorage) — refused
 // here as the parse would refuse it, without the lock, the cache lookup and the error text: the unfused nodes the reference then builds are the ones its
 // own device branch builds (ne_bestla.cpp:222-225).
 static inline bool is_device_record(const void* p) {

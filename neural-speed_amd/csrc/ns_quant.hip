@@ -430,7 +430,7 @@ __global__ __launch_bounds__(256) void norm_kernel(const float* __restrict__ in,
                                                    bool rms, float eps, const float* __restrict__ gamma,
                                                    _Float16* __restrict__ out16, float* __restrict__ out_plain = nullptr) {
   // out_plain (with gamma): the normalised values BEFORE the gamma product as well — the two tensors of the reference's norm and
-  // mul nodes from one launch (ns_device.hip: lazy peephole of the device route)
+  // mul nodes from one launch (ns_device_ops.hip: lazy peephole of the device route)
   __shared__ float red[2][4];
   const float* src = in + size_t(blockIdx.x) * size;
   float* dst = out + size_t(blockIdx.x) * size;
@@ -1041,10 +1041,6 @@ hipError_t launch_rope_qkv_append(float* q, const float* k, const float* v, void
   return hipGetLastError();
 }
 
-thread_local Affine g_affine;
-thread_local void* g_mha_out16 = nullptr;
-thread_local bool g_mha_out16_written = false;
-thread_local KvMirrorPair g_kvm;
 // a cache cell at `addr` received `v`: its fp16 mirror cell, found from the cell's address (ns_route.h)
 __device__ __forceinline__ void kvm_store(const KvMirrorArgs& m, const char* addr, float v) {
   if (!m.m16) return;

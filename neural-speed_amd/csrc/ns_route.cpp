@@ -40,6 +40,7 @@
 
 #include "../../include/ns_bestla.h"
 #include "ns_common.h"
+#include "ns_device_plan.h"
 #include "ns_route_int.h"
 
 namespace ns {
@@ -102,7 +103,7 @@ struct RouteTiming {
       win_t0 = 0;
     }
   }
-  void mark(int what, bool trace_empty) {  // ns_device.hip marks a token's synchronisation (0) and the end of a copy (1)
+  void mark(int what, bool trace_empty) {  // ns_device.hip (bestla_device_sync / _memcpy_sync) marks a token's synchronisation (0) and the end of a copy (1)
     const long long now = now_us();
     if (what == 0) {
       if (!tm[TM_SYNC_IN] || tm[TM_SYNC_IN] < tm[TM_LAST_LAUNCH]) tm[TM_SYNC_IN] = now;
@@ -342,9 +343,8 @@ bool prepare_plan_device(const std::vector<PlanOp>& plan) {
   for (const PlanOp& po : plan)
     if (po.op.kind == RK_MHA) {
       const MhaView a{po.op};
-      const size_t nsplit_max = size_t((a.n_ctx() + 127) / 128);
-      if (!stream_scratch(R.st, size_t(a.batch()) * a.seq() * a.heads() * nsplit_max * (2 + a.head_size()) * sizeof(float), SLOT_MHA_PARTIALS)) return false;
-      if (!stream_scratch_zeroed(R.st, 65536 * 4, SLOT_MHA_TICKETS)) return false;  // the tickets of the merge inside the launch (ns_device.hip)
+      if (!stream_scratch(R.st, mha_f32_partials_bytes(int(a.batch()), int(a.seq()), int(a.heads()), int(a.head_size()), int(a.n_ctx())), SLOT_MHA_PARTIALS)) return false;
+      if (!stream_scratch_zeroed(R.st, kMhaTicketBytes, SLOT_MHA_TICKETS)) return false;  // the tickets of the merge inside the launch (ns_device_mha.hip)
       // ... and what the fp16-mirror form needs (ns_attn.cpp, moving context length)
       if (kv16_enabled() && !attn_prepare_moving(R.st, int(a.batch()), int(a.heads()), int(a.heads_kv()), int(a.head_size()), int(a.n_ctx()))) return false;
     }

@@ -1,4 +1,4 @@
-// ns_route.h — what the device route's pieces share (ns_route*.cpp, ns_device.hip, the operator kernels of ns_quant.hip): the fp16
+// ns_route.h — what the device route's pieces share (ns_route*.cpp, ns_device*.{hip,cpp}, the operator kernels of ns_quant.hip): the fp16
 // mirror of the reference's fp32 device kv cache (round 6) and the per-token bookkeeping around it.
 //
 // Why a mirror: a reference tree built with its device switch keeps its kv cache in fp32 on the device — K [batch][heads_kv][n_ctx][head_size],
@@ -41,11 +41,11 @@ struct KvMirrorArgs {
 struct KvMirrorPair {
   KvMirrorArgs k, v;
 };
-extern thread_local KvMirrorPair g_kvm;  // set around a captured cache-write launch (like g_affine), zero otherwise
+extern thread_local KvMirrorPair g_kvm;  // ns_route_exec.cpp: set around a captured cache-write launch (like g_affine), zero otherwise
 
 bool route_executing();  // ns_route_exec.cpp (ExecGuard): the calling thread is inside a launch the route issues (its cache protocol is known)
 
-// ---- ns_device.hip ----
+// ---- ns_device_kvm.cpp (the records and their rules: KvMirrorTable, ns_device_plan.h) ----
 bool kv16_enabled();          // NS_DEVICE_KV / ns_hip_set_tuning("device_kv_f16")
 void kv16_set(int on);        // -1: environment / default (on)
 // the mirror behind the fp32 cache cell at `cell` (a cpy node's destination): fills `out`, false when no mirror holds it

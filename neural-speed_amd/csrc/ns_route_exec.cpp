@@ -8,6 +8,11 @@
 #include "ns_route_int.h"
 
 namespace ns {
+// what a launch issued here is told beside its arguments (ns_common.h, ns_route.h): set around the call, cleared behind it (ExecGuard)
+thread_local Affine g_affine;
+thread_local void* g_mha_out16 = nullptr;
+thread_local bool g_mha_out16_written = false;
+thread_local KvMirrorPair g_kvm;
 namespace {
 
 thread_local bool t_in_exec = false;

@@ -1,5 +1,5 @@
 // ns_route_op.h — the fields of a RouteOp (ns_common.h), stated once: which of p[4] / i[24] / f[8] holds what for each RouteKind.  The producers
-// (ns_api.cpp, ns_device.hip) fill an op through the constructors below, the route (ns_route*.cpp) reads it through the views; nobody indexes
+// (ns_api.cpp, ns_device_load.cpp, ns_device_ops.hip, ns_device_mha.hip) fill an op through the constructors below, the route (ns_route*.cpp) reads it through the views; nobody indexes
 // p / i / f by number.  The struct itself stays plain bytes: a token is verified against its plan with one memcmp per op (ns_route.cpp).
 #pragma once
 #include <cstddef>

@@ -1,4 +1,4 @@
-"""Lazy peephole of the device route (csrc/ns_device.hip, round 4): rms_norm and silu nodes are recorded, a multiply that consumes the
+"""Lazy peephole of the device route (csrc/ns_device_ops.hip, round 4): rms_norm and silu nodes are recorded, a multiply that consumes the
 recorded result runs ONE kernel writing both tensors; everything else launches the recorded node first.  Every tensor must hold
 the bits the node-by-node kernels write."""
 import ctypes as C

@@ -409,7 +409,7 @@ def test_replayed_attention_over_several_context_ranges(L, pkg, nso, nctx, pos0)
     """Twelve positions from pos0 on of caches made for nctx: the replayed attention's grid and partials are laid out for nctx, its ranges follow the LIVE
     length (AttnSplitParams::dyn_*: every workgroup applies the host's range rule to the length it reads from the device counter — a few ranges of a
     few dozen keys at 122 .. 133 positions, crossing the one-range threshold at 128; more at 700; the layout's own at 2030 ..), and the last range to
-    finish merges them inside the launch (ns_device.hip, tickets) — no merge launch in the plan."""
+    finish merges them inside the launch (ns_device_mha.hip, tickets) — no merge launch in the plan."""
     rng = np.random.default_rng(6)
     mk = lambda n, k: nso.quant_pack((rng.standard_normal((n, k)) * k ** -0.5).astype(np.float32), 32, nso.S4, nso.BF16, False, nso.CORE_AVX512_VNNI_KB)
     blobs = {"wq": mk(D, D), "wk": mk(D, D), "wv": mk(D, D), "wo": mk(D, D), "w1": mk(FF, D), "w3": mk(FF, D), "w2": mk(D, FF)}
