@@ -97,7 +97,8 @@ int ns_hip_lazy_flush(void) { return g_lazy.kind ? lazy_flush_impl() : 0; }
 int ns_hip_lazy_rms_norm(int rows, int cols, float eps, const float* dIn, float* dOut, void* stream) {
   if (route_hook(stream)) return route_submit(route_op_rms_norm(dIn, dOut, rows, cols, eps));
   if (ns_hip_lazy_flush() != 0) return -1;
-  if (!dIn || !dOut || rows < 1 || cols < 1) return fail("lazy rms_norm: invalid argument");
+  if (!dIn || !dOut || rows < 0 || cols < 1) return fail("lazy rms_norm: invalid argument");
+  if (!rows) return 0;  // no rows: nothing to record, like ns_hip_lazy_silu with n == 0
   g_lazy = LazyNode{1, dIn, dOut, rows, cols, eps, size_t(rows) * cols, static_cast<hipStream_t>(stream)};
   return lazy_on() ? 0 : ns_hip_lazy_flush();
 }

@@ -624,6 +624,7 @@ void bestla_packweight_copyattr(const float* f32ptr, void* dstpr, int n, int k, 
 
 static bool host_unary(size_t in_elems, size_t out_elems, const float* in, float* out,
                        const std::function<hipError_t(const float*, float*)>& fn) {
+  if (!in_elems && !out_elems) return true;  // nothing to do (a scratch buffer of zero bytes that was never allocated is a null pointer)
   // decode-sized tensors: pinned, device-mapped staging — memcpy, ONE launch that reads / writes host memory over PCIe, ONE
   // synchronisation (three blocking hipMemcpy round trips cost 36-53 us per call; the graph issues six such calls per layer)
   if (zero_copy_enabled() && (in_elems + out_elems) * 4 <= kZeroCopyMaxBytes) {

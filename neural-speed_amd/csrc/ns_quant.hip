@@ -502,6 +502,7 @@ __global__ __launch_bounds__(256) void norm_kernel(const float* __restrict__ in,
 }
 hipError_t launch_rmsnorm(int norm_count, int norm_size, bool isrms, float eps, const float* in, float* out,
                           hipStream_t st, const float* gamma, void* out16) {
+  if (norm_count <= 0 || norm_size <= 0) return hipSuccess;  // no rows: nothing to do (a grid of zero workgroups is refused)
   const bool cached = norm_size <= 4096 && (norm_size & 3) == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0 &&
                       (reinterpret_cast<uintptr_t>(out) & 15) == 0 && (reinterpret_cast<uintptr_t>(out16) & 7) == 0 &&
                       (!gamma || (reinterpret_cast<uintptr_t>(gamma) & 3) == 0);
@@ -538,6 +539,7 @@ hipError_t launch_dq8_expand(const uint8_t* codes, const float* dq, const float*
 // as launch_rmsnorm(in -> plain) followed by the row-broadcast multiply
 hipError_t launch_rmsnorm_mul2(int norm_count, int norm_size, bool isrms, float eps, const float* in, float* plain, const float* gamma,
                                float* out, hipStream_t st) {
+  if (norm_count <= 0 || norm_size <= 0) return hipSuccess;
   const bool cached = norm_size <= 4096 && (norm_size & 3) == 0 && ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out) |
                                                                    reinterpret_cast<uintptr_t>(plain)) & 15) == 0 &&
                       (reinterpret_cast<uintptr_t>(gamma) & 3) == 0;
@@ -1394,6 +1396,7 @@ __global__ void gather_cols_kernel(const float* __restrict__ a, int lda, const i
   out[gid] = a[size_t(r) * lda + idx[j]];
 }
 hipError_t launch_gather_cols(const float* a, int lda, const int* idx, float* out, int m, int k, hipStream_t st) {
+  if (m <= 0 || k <= 0) return hipSuccess;
   const size_t total = size_t(m) * k;
   hipLaunchKernelGGL(gather_cols_kernel, dim3(unsigned((total + 255) / 256)), dim3(256), 0, st, a, lda, idx, out, m, k);
   return hipGetLastError();
@@ -1401,6 +1404,7 @@ hipError_t launch_gather_cols(const float* a, int lda, const int* idx, float* ou
 
 hipError_t launch_bcast_binary(int batch, int vsize, const float* t, const float* v, int vstep, float* out, bool mul,
                                hipStream_t st) {
+  if (batch <= 0 || vsize <= 0) return hipSuccess;
   const size_t total = size_t(batch) * vsize;
   hipLaunchKernelGGL(bcast_kernel, grid1d(total, 256), dim3(256), 0, st, t, v, out, total, vsize, vstep, mul);
   return hipGetLastError();

@@ -21,7 +21,8 @@ def _dims(t):
 def _mul(L, fn, a, b, d, st, is_mul=None):
     ne0, nb0 = _dims(a)
     ne1, nb1 = _dims(b)
-    nb1 = (C.c_longlong * 4)(*[0 if (i > 0 and ne1[i] == 1) else nb1[i] for i in range(4)])
+    # (only a dimension that is really broadcast gets a stride of 0: lazy_mul_plan asks an operand of a's shape for packed strides before it fuses a silu)
+    nb1 = (C.c_longlong * 4)(*[0 if (i > 0 and ne1[i] == 1 and ne0[i] != 1) else nb1[i] for i in range(4)])
     _, nbd = _dims(d)
     args = [a.data_ptr(), b.data_ptr(), d.data_ptr(), ne0, nb0, ne1, nb1, nbd, st]
     return fn(*([is_mul] + args if is_mul is not None else args))
