@@ -471,6 +471,17 @@ int ns_hip_rope_qkv_append(float* dQ, const float* dK, const float* dV, void* dK
                            int heads_kv, int head_size, int n_past, int n_dims, int mode, float freq_base, float freq_scale,
                            float ext_factor, float attn_factor, long long cache_step_sl, long long cache_step_head,
                            void* stream);
+/* The same three operators for a batch of independent REQUESTS at decode, one position per row: row r is request r — dQ[r][heads][head_size]
+ * (rotated in place), dK[r][heads_kv][head_size], dV[r][heads_kv][head_size] — at position dPos[r] (DEVICE array of `rows` ints) of its own cache
+ * slab, which starts at cache + r * cache_step_bs (elements): rotated K and V go, as fp16, to cell dPos[r] * cache_step_sl + head * cache_step_head
+ * of slab r.  A row with dPos[r] < 0 or dPos[r] >= pos_cap is an idle slot: nothing of it is read or written, its Q row stays as it is; the bound
+ * is checked on the device, the host never sees the positions.  Modes and refusals are those of ns_hip_rope_qkv_append (modes 0 and 2, ext_factor
+ * 0), and so is the arithmetic: row r holds the bits of ns_hip_rope_qkv_append(seq = 1, n_past = dPos[r]) on slab r's pointers.  One launch,
+ * asynchronous, capturable: a captured step moves by changing the contents of dPos. */
+int ns_hip_rope_qkv_append_rows(float* dQ, const float* dK, const float* dV, void* dKcache16, void* dVcache16, int rows, int heads, int heads_kv,
+                                int head_size, const int* dPos, int pos_cap, int n_dims, int mode, float freq_base, float freq_scale,
+                                float ext_factor, float attn_factor, long long cache_step_bs, long long cache_step_sl, long long cache_step_head,
+                                void* stream);
 
 /* activation prologue of the reference's int8-compute path: quantize_fp_u8_colblock
  * (/root/reference/bestla/bestla/kernel_ref.h:1824-1883, driven by ActivationKBlockQuantize::run, bestla_prologue_a.h:133-154).
@@ -651,6 +662,25 @@ int ns_hip_attn_fp32_fp16_fp16_fp32_forward_h(const attn_fp32_fp16_fp16_fp32_fwd
  * follow head_num * world and start at rank * head_num).  Process-wide (one process per GPU); (0, 0) clears it.
  * A forward call whose heads do not fit the partition is refused. */
 int ns_hip_attn_set_head_partition(int global_head_num, int head_offset);
+/* Decode attention for a batch of independent REQUESTS: one query row per request, each over its own live keys, in one launch (plus the merge
+ * launch where the plan has one).  dparams is the device-pointer block of ns_hip_attn_fp32_fp16_fp16_fp32_forward_h with two differences: sl_q
+ * must be 1, and sl_kv is the CAPACITY of a request's slab in keys.  Request b (the batch index) attends over keys [0, len_b) of its slab
+ * (K + b * step_k_bs, V + b * step_v_bs), len_b = clamp(dKvLens[b] + kv_len_bias, 0, sl_kv); dKvLens is a DEVICE array of batch_size ints, read
+ * inside the launch — the host never sees the lengths, so a captured step moves by changing the array's contents.  kv_len_bias lets the positions
+ * array of ns_hip_rope_qkv_append_rows drive this entry as well (bias 1: the step's own key is included).  len_b == 0 is an idle slot: its row
+ * of dst (and of dst16) is written as zeros.  Causal, ALiBi and tanh-cap flags, Q_sc .. dst_sc, QK_scale, GQA, dst16, tmp and
+ * ns_hip_attn_set_head_partition work as in the uniform entry.
+ * Plan: that of the uniform entry's one-row kernels for (batch_size, .., sl_q 1, sl_kv = capacity) — grid, context ranges, partials and buffer
+ * descriptors are laid out for the capacity; every workgroup applies the range rule to its own request's live length, ranges past it leave at
+ * once, a single live range writes the output row itself, and no byte behind len_b is consumed (NS_ATTN_DYN_RANGES=0: ranges as laid out).
+ * Workspace: `tmp`, when given, is DEVICE memory of bestla_fusion_attn_workspace_size(batch_size, .., sl_q 1, sl_kv = capacity) bytes; otherwise the
+ * stream's scratch, which a first use on a capturing stream cannot allocate — give tmp there, or make one eager call first.
+ * Refused (returns -1, ns_hip_last_error set, nothing written): sl_q != 1, a null dKvLens, sl_kv < 1, and any call whose K / V rows are not
+ * contiguous in the head dimension and 16-byte aligned (what the uniform entry serves with its generic kernel). */
+int ns_hip_attn_decode_rows(const attn_fp32_fp16_fp16_fp32_fwd_args_t* dparams, const int* dKvLens, int kv_len_bias, void* dst16, void* stream);
+/* Process-wide counts of ns_hip_attn_decode_rows: [0] launches on the LDS-ring kernel, [1] launches on the register kernel, [2] merge launches,
+ * [3] refused calls.  (ns_hip_attn_stats counts these launches too, by kernel family: its slots [3] and [2].) */
+void ns_hip_attn_rows_stats(unsigned long long out[4]);
 
 /* ----------------------------------------------------------------------------------------------
  * Part 4b — mixture-of-experts matmul with the routing on the device.  Device twin of

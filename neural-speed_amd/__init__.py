@@ -261,6 +261,10 @@ def lib():
         L.ns_hip_attn_stats.restype = None
         L.ns_hip_attn_stats.argtypes = [vp]
         L.ns_hip_attn_fp32_fp16_fp16_fp32_forward_h.argtypes = [vp, vp, vp]
+        L.ns_hip_attn_decode_rows.argtypes = [vp, vp, i, vp, vp]
+        L.ns_hip_attn_rows_stats.restype = None
+        L.ns_hip_attn_rows_stats.argtypes = [vp]
+        L.ns_hip_rope_qkv_append_rows.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, vp, i, i, i, f, f, f, f, C.c_longlong, C.c_longlong, C.c_longlong, vp]
         L.ns_hip_blob_validate.argtypes = [vp, sz]
         L.ns_BTLAGemmPackBSize.restype = sz
         L.ns_BTLAGemmPackBSize.argtypes = [sz, sz, sz, u32, u32, b, i, vp]

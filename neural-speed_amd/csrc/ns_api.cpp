@@ -373,6 +373,24 @@ int ns_hip_rope_qkv_append(float* dQ, const float* dK, const float* dV, void* dK
                                        freq_base, freq_scale, attn_factor, cache_step_sl, cache_step_head,
                                        (hipStream_t)stream), "rope/kv-append launch") ? 0 : -1;
 }
+int ns_hip_rope_qkv_append_rows(float* dQ, const float* dK, const float* dV, void* dKcache16, void* dVcache16, int rows, int heads, int heads_kv,
+                                int head_size, const int* dPos, int pos_cap, int n_dims, int mode, float freq_base, float freq_scale,
+                                float ext_factor, float attn_factor, long long cache_step_bs, long long cache_step_sl, long long cache_step_head,
+                                void* stream) {
+  if (!have_device()) return -1;
+  if (!dQ || !dK || !dV || !dKcache16 || !dVcache16 || !dPos || rows < 0 || heads <= 0 || heads_kv <= 0 || head_size <= 0 || (head_size & 1) ||
+      n_dims <= 0 || (n_dims & 1) || n_dims > head_size || pos_cap < 0) {
+    set_error("rope_qkv_append_rows: invalid argument");
+    return -1;
+  }
+  if ((mode & ~2) != 0 || ext_factor != 0.f || ((mode & 2) && head_size % n_dims != 0)) {
+    set_error("rope_qkv_append_rows: only modes 0 and 2 (NeoX, head_size a multiple of n_dims) without YaRN extrapolation");
+    return -1;
+  }
+  return hip_ok(launch_rope_qkv_append_rows(dQ, dK, dV, dKcache16, dVcache16, rows, heads, heads_kv, head_size, dPos, pos_cap, n_dims, mode, freq_base,
+                                            freq_scale, attn_factor, cache_step_bs, cache_step_sl, cache_step_head, (hipStream_t)stream),
+                "rope/kv-append (rows) launch") ? 0 : -1;
+}
 // device twins of bestla_device_elewise_f32 (NE_OP_SILU) and bestla_device_dup_f32 (ne_bestla.h:103-109)
 int ns_hip_silu_f32(const float* dSrc, float* dDst, size_t n, void* stream) {
   if (!have_device()) return -1;

@@ -66,11 +66,31 @@ static AttnKnobs attn_knobs() {
   return k;
 }
 
+// scratch of a one-row plan, then its launch; *merged: attn_merge_kernel followed
+static hipError_t launch_onerow_plan(AttnPlan pl, const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, AttnKnobs kn, const Affine& aff, hipStream_t st,
+                                     std::string* why, bool device_tmp, void* dst16, bool* merged) {
+  float* ws = nullptr;
+  if (pl.partial_bytes) {
+    // partials go to the caller's workspace (`tmp`, sized by bestla_fusion_attn_workspace_size: the reference's own contract, and the only choice
+    // that works on a stream being captured for the first time); without one, to a grow-only per-stream scratch
+    ws = device_tmp ? reinterpret_cast<float*>(a.tmp) : nullptr;
+    if (!ws) ws = static_cast<float*>(stream_scratch(st, pl.partial_bytes, SLOT_ATTN_PARTIALS));
+    if (!ws) {  // scratch allocation failed: planned again as one range, still correct
+      kn.no_partials = true;
+      pl = attn_plan(a, dst16, kn, aff, why);
+    }
+  }
+  // (nullptr, e.g. first use on a capturing stream: the merge launch)
+  uint32_t* tickets = pl.want_tickets ? static_cast<uint32_t*>(stream_scratch_zeroed(st, kAttnTicketCap * 4, SLOT_ATTN_TICKETS)) : nullptr;
+  if (merged) *merged = pl.sp.nsplit > 1 && !tickets;
+  return launch_attn_onerow(pl, ws, tickets, st);
+}
+
 // plan, take scratch, launch
 static hipError_t launch_attn(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, hipStream_t st, std::string* why, bool device_tmp, void* dst16) {
   AttnKnobs kn = attn_knobs();
   AttnPlan pl = attn_plan(a, dst16, kn, g_affine, why);
-  float* ws = nullptr;
+  float* ws = nullptr;  // (of the block-split path)
   if (pl.path == AP_BLOCK_SPLIT) {
     // bestla_fusion_attn_workspace_size does not know this path (the reference's contract, sized by the one-row rules): the caller's `tmp` serves
     // only where it is large enough, the stream's scratch otherwise; without either the call is planned as with the key at 0
@@ -89,19 +109,42 @@ static hipError_t launch_attn(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, hipS
   };
   if (pl.path == AP_BLOCK_SPLIT) return counted(launch_attn_block_split(pl, ws, st));
   if (pl.path == AP_ROWS64 || pl.path == AP_ROWS128 || pl.path == AP_PIPELINED) return counted(launch_attn_rows(pl, st));
-  if (pl.partial_bytes) {
-    // partials go to the caller's workspace (`tmp`, sized by bestla_fusion_attn_workspace_size: the reference's own contract, and the only choice
-    // that works on a stream being captured for the first time); without one, to a grow-only per-stream scratch
-    ws = device_tmp ? reinterpret_cast<float*>(a.tmp) : nullptr;
-    if (!ws) ws = static_cast<float*>(stream_scratch(st, pl.partial_bytes, SLOT_ATTN_PARTIALS));
-    if (!ws) {  // scratch allocation failed: planned again as one range, still correct
-      kn.no_partials = true;
-      pl = attn_plan(a, dst16, kn, g_affine, why);
-    }
+  return counted(launch_onerow_plan(pl, a, kn, g_affine, st, why, device_tmp, dst16, nullptr));
+}
+
+// ns_hip_attn_decode_rows: the moving-length plan of the capacity, its live length read per batch entry.  The Affine is this call's own (the
+// thread-local g_affine belongs to the replayed route); the merge follows the "attn_inlaunch" key as in the uniform entry.
+static std::atomic<uint64_t> g_attn_rows[4];  // ns_hip_attn_rows_stats
+static hipError_t launch_attn_decode_rows(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const int* lens, int bias, hipStream_t st, std::string* why,
+                                          void* dst16) {
+  if (a.sl_q != 1) {
+    *why = "attention, per-request context lengths: one query row per request (sl_q must be 1)";
+    return hipErrorInvalidValue;
   }
-  // (nullptr, e.g. first use on a capturing stream: the merge launch)
-  uint32_t* tickets = pl.want_tickets ? static_cast<uint32_t*>(stream_scratch_zeroed(st, kAttnTicketCap * 4, SLOT_ATTN_TICKETS)) : nullptr;
-  return counted(launch_attn_onerow(pl, ws, tickets, st));
+  if (!lens) {
+    *why = "attention, per-request context lengths: dKvLens is null";
+    return hipErrorInvalidValue;
+  }
+  if (a.sl_kv < 1) {
+    *why = "attention, per-request context lengths: sl_kv is the capacity of a request's slab (at least 1 key)";
+    return hipErrorInvalidValue;
+  }
+  const AttnKnobs kn = attn_knobs();
+  Affine aff;
+  aff.k = lens, aff.delta = 1, aff.cap = a.sl_kv, aff.inlaunch = 0, aff.rows = 1, aff.bias = bias;
+  const AttnPlan pl = attn_plan(a, dst16, kn, aff, why);
+  if (pl.path != AP_RING && pl.path != AP_SPLIT_REGS) {  // (refused: the plan gives nothing else to this form)
+    if (why->empty()) *why = "attention, per-request context lengths: no split kernel takes this call";
+    return hipErrorInvalidValue;
+  }
+  bool merged = false;
+  const hipError_t e = launch_onerow_plan(pl, a, kn, aff, st, why, a.tmp != nullptr, dst16, &merged);
+  if (e == hipSuccess) {
+    g_attn_launches[pl.path].fetch_add(1, std::memory_order_relaxed);
+    g_attn_rows[pl.path == AP_RING ? 0 : 1].fetch_add(1, std::memory_order_relaxed);
+    if (merged) g_attn_rows[2].fetch_add(1, std::memory_order_relaxed);
+  }
+  return e;
 }
 
 // scratch a moving-length decode launch needs (partials for the longest context, the merge tickets): allocated BEFORE the route's capture
@@ -174,6 +217,21 @@ int ns_hip_attn_fp32_fp16_fp16_fp32_forward_h(const attn_fp32_fp16_fp16_fp32_fwd
     return -1;
   }
   return 0;
+}
+
+int ns_hip_attn_decode_rows(const attn_fp32_fp16_fp16_fp32_fwd_args_t* a, const int* dKvLens, int kv_len_bias, void* dst16, void* stream) {
+  std::string why;
+  const hipError_t e = a ? launch_attn_decode_rows(*a, dKvLens, kv_len_bias, static_cast<hipStream_t>(stream), &why, dst16) : hipErrorInvalidValue;
+  if (e != hipSuccess) {
+    g_attn_rows[3].fetch_add(1, std::memory_order_relaxed);
+    set_error(why.empty() ? std::string("attention launch (per-request context lengths): ") + (a ? hipGetErrorString(e) : "null arguments") : why);
+    return -1;
+  }
+  return 0;
+}
+
+void ns_hip_attn_rows_stats(unsigned long long out[4]) {
+  for (int i = 0; i < 4; i++) out[i] = g_attn_rows[i].load(std::memory_order_relaxed);
 }
 
 }  // extern "C"

@@ -61,10 +61,23 @@ struct AttnSplitParams {
   // (attn_nsplit) to the live length itself: dyn_min_keys / dyn_batch_keys / dyn_single_below are that rule's constants for this launch, nsplit its
   // upper bound (grid and partials' layout stay those of the longest context).  dyn_min_keys == 0: ranges as laid out (keys_per_split).
   int dyn_min_keys, dyn_batch_keys, dyn_single_below;
+  // A batch of independent requests (ns_hip_attn_decode_rows; AttnPlan::rows, the kernels' ROWS instantiations): the moving length is ONE VALUE PER
+  // BATCH ENTRY — clamp(kmove[ibs] + kdelta, 0, a.sl_kv): kmove is an array, kdelta the bias added to its entries, a.sl_kv the capacity of a request's
+  // slab.  Everything above holds per request (ranges, live ranges, the single live range that writes its row); a length of 0 is an idle slot, whose
+  // output row the first range's workgroups write as zeros.  (No field of its own: the struct, and with it the code of every other instantiation,
+  // is what it was.)
 };
 // live context length / live ranges of a launch (kmove == nullptr: what the host said).  Host and device: tests/test_attn_plan.py walks every live
-// length of a plan through the two range functions.
-__host__ __device__ __forceinline__ int attn_live_kv(const AttnSplitParams& sp) { return sp.kmove ? sp.a.sl_kv + sp.kdelta * *sp.kmove : sp.a.sl_kv; }
+// length of a plan through the two range functions.  ROWS: the per-request form, the live length of batch entry ibs (the clamp and the zero
+// length belong to it alone) — a template argument, so the instantiations that serve every other call hold the code they held without it.
+template <bool ROWS = false>
+__host__ __device__ __forceinline__ int attn_live_kv(const AttnSplitParams& sp, int ibs = 0) {
+  if constexpr (ROWS) {
+    const long long len = (long long)sp.kmove[ibs] + sp.kdelta;
+    return len < 0 ? 0 : (len > sp.a.sl_kv ? sp.a.sl_kv : int(len));
+  }
+  return sp.kmove ? sp.a.sl_kv + sp.kdelta * *sp.kmove : sp.a.sl_kv;
+}
 // keys per range at the live length (the host's rule: as many ranges as the launch has workgroups for, at least dyn_min_keys keys each, whole softmax batches)
 __host__ __device__ __forceinline__ int attn_live_kps(const AttnSplitParams& sp, int sl_kv) {
   if (!sp.kmove || sp.dyn_min_keys <= 0) return sp.keys_per_split;
@@ -112,6 +125,7 @@ struct AttnPlan {
   AttnSplitParams sp;                // sp.a: the kernels' AttnParams; the rest (ranges, order, head groups, moving length): one-row paths
   dim3 grid, block;
   size_t lds = 0;                    // dynamic LDS bytes
+  bool rows = false;                 // one-row paths: one live length per batch entry (the ROWS instantiations; sp.kmove an array, sp.kdelta its bias)
   bool want_tickets = false;         // ranges merge inside the launch if the stream's ticket buffer can be had
   bool merge = false;                // attn_merge_kernel follows (also when tickets are wanted and cannot be had)
   size_t partial_bytes = 0;          // of sp.ws
@@ -127,7 +141,7 @@ size_t attn_ws_bytes(const AttnKnobs& knobs, int batch, int head_num, int heads_
 hipError_t launch_attn_onerow(const AttnPlan& pl, float* ws, uint32_t* tickets, hipStream_t st);  // ns_attn_decode.hip: AP_GENERIC, AP_SPLIT_REGS, AP_RING (+ merge)
 hipError_t launch_attn_rows(const AttnPlan& pl, hipStream_t st);                                  // ns_attn_prefill.hip: AP_ROWS64, AP_ROWS128, AP_PIPELINED
 hipError_t launch_attn_block_split(const AttnPlan& pl, float* ws, hipStream_t st);                // ns_attn_block.hip: AP_BLOCK_SPLIT (+ merge)
-hipError_t launch_attn_merge(const AttnSplitParams& sp, unsigned batch, hipStream_t st);          // ns_attn_decode.hip: attn_merge_kernel over sp.ws
+hipError_t launch_attn_merge(const AttnSplitParams& sp, unsigned batch, hipStream_t st, bool rows = false);  // ns_attn_decode.hip: attn_merge_kernel over sp.ws
 // touch_attn_module (ns_common.h) makes the runtime load all four code objects
 inline void touch_kernel(const void* kernel) {
   hipFuncAttributes fa;

@@ -278,7 +278,22 @@ __device__ __forceinline__ void attn_split_finish(const AttnSplitParams& sp, flo
   }
 }
 
-template <int G, int DPL>  // G query heads per kv head; DPL head dims per lane (8: head_size <= 128, 16: <= 256)
+// Per-request form (ROWS instantiations): an idle slot — a live length of 0 — has no key to attend over; the workgroups of its first range write the
+// output rows of their heads as zeros, every workgroup of the slot leaves before it has requested anything.
+template <int G>
+__device__ __forceinline__ void attn_zero_rows(const AttnSplitParams& sp, int chunk, int ihkv, int i, int ibs) {
+  const AttnParams& p = sp.a;
+  for (int idx = threadIdx.x; idx < G * p.head_size; idx += kAttnThreads) {
+    const int g = idx / p.head_size, dd = idx % p.head_size;
+    if (chunk * G + g >= sp.g_full) continue;
+    float* dst = p.dst + ibs * p.step_dst_bs + (ihkv * sp.g_full + chunk * G + g) * p.step_dst_head_num + i * p.step_dst_sl;
+    dst[dd] = 0.f;
+    if (p.dst16) p.dst16[dst - p.dst + dd] = (_Float16)0.f;
+  }
+}
+
+// ROWS (both split kernels and the merge): one live length per batch entry (ns_hip_attn_decode_rows, AttnPlan::rows); false: the code as without it
+template <int G, int DPL, bool ROWS = false>  // G query heads per kv head; DPL head dims per lane (8: head_size <= 128, 16: <= 256)
 __global__ __launch_bounds__(kAttnThreads) void attn_split_kernel(const AttnSplitParams sp) {
   const AttnParams& p = sp.a;
   __shared__ float ml_s[4][G][2];
@@ -297,7 +312,13 @@ __global__ __launch_bounds__(kAttnThreads) void attn_split_kernel(const AttnSpli
   const bool causal = (p.flags & NS_ATTN_FLAG_IS_CAUSAL) != 0;
   const bool alibi = (p.flags & NS_ATTN_FLAG_IS_ALIBI8) != 0;
   const bool tanh30 = (p.flags & NS_ATTN_FLAG_IS_TANH30) != 0;
-  const int sl_kv = attn_live_kv(sp), live = attn_live_splits(sp, sl_kv);
+  const int sl_kv = attn_live_kv<ROWS>(sp, ibs), live = attn_live_splits(sp, sl_kv);
+  if constexpr (ROWS) {
+    if (sl_kv == 0) {  // an idle slot
+      if (split == 0) attn_zero_rows<G>(sp, chunk, ihkv, i, ibs);
+      return;
+    }
+  }
   if (split >= live) return;  // (moving context length: a range past the live keys)
   const int unmasked = causal ? (sl_kv - p.sl_q) + i + 1 : sl_kv;
   const int kps = attn_live_kps(sp, sl_kv);
@@ -457,7 +478,7 @@ __global__ __launch_bounds__(kAttnThreads) void attn_split_kernel(const AttnSpli
 #ifndef NS_AS_ABL
 #define NS_AS_ABL 0  // timing ablations (diagnostic builds, wrong results): 1 no arithmetic in the key loop, 2 nothing behind the key loop, 3 no key loop at all (nothing streamed), 4 streamed but never read
 #endif
-template <int G, int LPK = 16>  // LPK lanes per key: 16 (head sizes 72 .. 128) or 8 (40 .. 64: a 1 KiB request then holds 8 key rows, a wave step 8 keys)
+template <int G, int LPK = 16, bool ROWS = false>  // LPK lanes per key: 16 (head sizes 72 .. 128) or 8 (40 .. 64: a 1 KiB request then holds 8 key rows, a wave step 8 keys)
 __global__ __launch_bounds__(kAttnThreads) void attn_stream_kernel(const AttnSplitParams sp) {
   constexpr int DPL = 8;
   constexpr int KPW = 64 / LPK;  // keys per wave and step
@@ -478,7 +499,13 @@ __global__ __launch_bounds__(kAttnThreads) void attn_stream_kernel(const AttnSpl
   const bool causal = (p.flags & NS_ATTN_FLAG_IS_CAUSAL) != 0;
   const bool alibi = (p.flags & NS_ATTN_FLAG_IS_ALIBI8) != 0;
   const bool tanh30 = (p.flags & NS_ATTN_FLAG_IS_TANH30) != 0;
-  const int sl_kv = attn_live_kv(sp), live = attn_live_splits(sp, sl_kv);
+  const int sl_kv = attn_live_kv<ROWS>(sp, ibs), live = attn_live_splits(sp, sl_kv);
+  if constexpr (ROWS) {
+    if (sl_kv == 0) {  // an idle slot
+      if (split == 0) attn_zero_rows<G>(sp, chunk, ihkv, i, ibs);
+      return;
+    }
+  }
   if (split >= live) return;  // (moving context length: a range past the live keys)
   const int unmasked = causal ? (sl_kv - p.sl_q) + i + 1 : sl_kv;
   const int kps = attn_live_kps(sp, sl_kv);
@@ -668,13 +695,14 @@ __global__ __launch_bounds__(kAttnThreads) void attn_stream_kernel(const AttnSpl
 // one workgroup per (batch, query row, head): combine the splits' (m, l, acc).  The per-split (m, l) are fetched by
 // one thread each (one round trip instead of nsplit dependent ones), the weights exp(m_s - m) go through LDS, and the
 // accumulator columns are summed with independent loads.
+template <bool ROWS = false>
 __global__ __launch_bounds__(128) void attn_merge_kernel(const AttnSplitParams sp) {
   const AttnParams& p = sp.a;
   __shared__ float c_s[64];
   __shared__ float l_s[64];
   const int ihn = blockIdx.x, i = blockIdx.y, ibs = blockIdx.z;
   const int hs = p.head_size, t = threadIdx.x;
-  const int ns = attn_live_splits(sp, attn_live_kv(sp));  // ns <= 64
+  const int ns = attn_live_splits(sp, attn_live_kv<ROWS>(sp, ibs));  // ns <= 64
   if (sp.kmove && ns == 1) return;  // (a single live range wrote the output row itself)
   const float* wp = sp.ws + (((size_t)ibs * p.sl_q + i) * p.head_num + ihn) * sp.nsplit * (2 + hs);
   // the common decode shapes (<= 32 splits, one output element per thread): every thread fetches all (max, sum) pairs — wave-
@@ -740,17 +768,24 @@ __global__ __launch_bounds__(128) void attn_merge_kernel(const AttnSplitParams s
 }
 
 // ---- launch of a plan (ns_attn_plan.cpp) -------------------------------------------------------------------------------------------------
-template <int G>
+template <int G, bool ROWS>
 static hipError_t launch_split_g(const AttnPlan& pl, const AttnSplitParams& sp, hipStream_t st) {
   if (pl.path == AP_RING)  // head sizes 72 .. 128: sixteen lanes per key, 40 .. 64: eight
-    return pl.lpk == 16 ? launch_lds<attn_stream_kernel<G, 16>>(int(kAsLdsBytes), pl.grid, pl.block, pl.lds, st, sp)
-                        : launch_lds<attn_stream_kernel<G, 8>>(int(kAsLdsBytes), pl.grid, pl.block, pl.lds, st, sp);
+    return pl.lpk == 16 ? launch_lds<attn_stream_kernel<G, 16, ROWS>>(int(kAsLdsBytes), pl.grid, pl.block, pl.lds, st, sp)
+                        : launch_lds<attn_stream_kernel<G, 8, ROWS>>(int(kAsLdsBytes), pl.grid, pl.block, pl.lds, st, sp);
   if (pl.dpl == 8) {
-    hipLaunchKernelGGL((attn_split_kernel<G, 8>), pl.grid, pl.block, pl.lds, st, sp);
+    hipLaunchKernelGGL((attn_split_kernel<G, 8, ROWS>), pl.grid, pl.block, pl.lds, st, sp);
   } else {
-    hipLaunchKernelGGL((attn_split_kernel<G, 16>), pl.grid, pl.block, pl.lds, st, sp);
+    hipLaunchKernelGGL((attn_split_kernel<G, 16, ROWS>), pl.grid, pl.block, pl.lds, st, sp);
   }
   return hipGetLastError();
+}
+template <bool ROWS>
+static hipError_t launch_split(const AttnPlan& pl, const AttnSplitParams& sp, hipStream_t st) {
+  return pl.G == 1   ? launch_split_g<1, ROWS>(pl, sp, st)
+         : pl.G == 2 ? launch_split_g<2, ROWS>(pl, sp, st)
+         : pl.G == 4 ? launch_split_g<4, ROWS>(pl, sp, st)
+                     : launch_split_g<8, ROWS>(pl, sp, st);
 }
 // ws: the partials (pl.partial_bytes); tickets: the stream's ticket buffer when the plan wants one, nullptr = the merge launch
 hipError_t launch_attn_onerow(const AttnPlan& pl, float* ws, uint32_t* tickets, hipStream_t st) {
@@ -761,21 +796,22 @@ hipError_t launch_attn_onerow(const AttnPlan& pl, float* ws, uint32_t* tickets, 
   }
   AttnSplitParams sp = pl.sp;
   sp.ws = ws, sp.tickets = tickets;
-  hipError_t e = pl.G == 1   ? launch_split_g<1>(pl, sp, st)
-                 : pl.G == 2 ? launch_split_g<2>(pl, sp, st)
-                 : pl.G == 4 ? launch_split_g<4>(pl, sp, st)
-                             : launch_split_g<8>(pl, sp, st);
+  hipError_t e = pl.rows ? launch_split<true>(pl, sp, st) : launch_split<false>(pl, sp, st);
   if (e != hipSuccess) return e;
-  if (sp.nsplit > 1 && !sp.tickets) e = launch_attn_merge(sp, pl.grid.z, st);  // (grid.z: the batch)
+  if (sp.nsplit > 1 && !sp.tickets) e = launch_attn_merge(sp, pl.grid.z, st, pl.rows);  // (grid.z: the batch)
   return e;
 }
-hipError_t launch_attn_merge(const AttnSplitParams& sp, unsigned batch, hipStream_t st) {
-  hipLaunchKernelGGL(attn_merge_kernel, dim3(unsigned(sp.a.head_num), unsigned(sp.a.sl_q), batch), dim3(128), 0, st, sp);
+hipError_t launch_attn_merge(const AttnSplitParams& sp, unsigned batch, hipStream_t st, bool rows) {
+  if (rows) {
+    hipLaunchKernelGGL(attn_merge_kernel<true>, dim3(unsigned(sp.a.head_num), unsigned(sp.a.sl_q), batch), dim3(128), 0, st, sp);
+  } else {
+    hipLaunchKernelGGL(attn_merge_kernel<false>, dim3(unsigned(sp.a.head_num), unsigned(sp.a.sl_q), batch), dim3(128), 0, st, sp);
+  }
   return hipGetLastError();
 }
 
 void touch_attn_module() {  // (one kernel of every attention file: each has a code object of its own)
-  touch_kernel(reinterpret_cast<const void*>(attn_merge_kernel));
+  touch_kernel(reinterpret_cast<const void*>(attn_merge_kernel<false>));
   touch_attn_rows_module();
   touch_attn_block_module();
   touch_kvcache_module();

@@ -131,6 +131,7 @@ AttnPlan attn_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst
   // replayed device route (ns_route.cpp): the context length of a captured decode step moves with the graph's token counter
   if (aff.k && (a.sl_q != 1 || aff.cap < a.sl_kv))
     return refuse("attention: a moving context length is served for decode steps (one query row) within the cache's capacity");
+  if (aff.k && aff.rows && aff.cap != a.sl_kv) return refuse("attention: per-request context lengths take sl_kv as the capacity of a request's slab");
   // what every kernel but attn_kernel asks of K and V: a contiguous head dimension and 16-byte aligned rows
   const bool rows_ok = a.step_k_head_size == 1 && a.step_v_head_size == 1 && a.step_k_sl % 8 == 0 && a.step_v_sl % 8 == 0 &&
                        a.step_k_head_num % 8 == 0 && a.step_v_head_num % 8 == 0 && a.step_k_bs % 8 == 0 &&
@@ -209,6 +210,9 @@ AttnPlan attn_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst
   const int dpl = a.head_size <= 128 ? 8 : 16;  // head dims per lane of the register kernel
   const size_t base_blocks = size_t(a.heads_kv) * a.sl_q * chunks;  // workgroups per range and batch entry
   if (kn.v1 || !rows_ok || a.head_size % dpl != 0 || base_blocks > 65535) {
+    // per-request context lengths (ns_hip_attn_decode_rows): attn_kernel knows one length per launch
+    if (aff.rows && !rows_ok) return refuse("attention: per-request context lengths need K / V rows contiguous in the head dimension and 16-byte aligned");
+    if (aff.rows) return refuse("attention: per-request context lengths need a head size that is a multiple of 8 and at most 65535 kv heads (and no NS_ATTN_V1)");
     pl.path = AP_GENERIC;
     pl.grid = dim3(unsigned(a.sl_q), unsigned(a.head_num), unsigned(a.batch_size));
     return pl;
@@ -228,7 +232,8 @@ AttnPlan attn_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst
   const int nsplit = kn.no_partials ? 1 : attn_nsplit(rule, base_blocks * a.batch_size, rule_kv);
   sp.nsplit = nsplit;
   sp.keys_per_split = (rule_kv + nsplit - 1) / nsplit;
-  sp.kmove = aff.k, sp.kdelta = int(aff.delta);
+  pl.rows = aff.k && aff.rows;  // (one live length per batch entry: kdelta is the bias of the entries, a.sl_kv the capacity)
+  sp.kmove = aff.k, sp.kdelta = pl.rows ? aff.bias : int(aff.delta);
   if (aff.k && nsplit > 1 && kn.dyn_ranges && a.sl_q == 1)  // the rule's constants, for the workgroups to apply to the live length
     sp.dyn_min_keys = rule.min_keys, sp.dyn_batch_keys = rule.batch_keys, sp.dyn_single_below = rule.single_below;
   // partials go to the caller's workspace (`tmp`, sized by bestla_fusion_attn_workspace_size) or the stream's scratch

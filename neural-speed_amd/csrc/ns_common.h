@@ -385,6 +385,10 @@ struct Affine {
   long long delta2 = 0;  // launch_dup2: the second copy's destination
   long long cap = 0;     // decode attention (ns_attn_plan.cpp): the largest value the moving context length can take (the cache's n_ctx)
   int inlaunch = 1;      // decode attention: the context ranges merge inside the launch (tickets)
+  // decode attention over a batch of independent requests (ns_hip_attn_decode_rows, which builds its own value: never g_affine): k is an ARRAY, one
+  // context length per batch entry — clamp(k[b] + bias, 0, cap), delta 1
+  int rows = 0;
+  int bias = 0;
 };
 // ns_attn.cpp: per-stream scratch of a moving-length decode attention, allocated before the capture that uses it
 bool attn_prepare_moving(hipStream_t st, int batch, int heads, int heads_kv, int head_size, int cap);
@@ -441,6 +445,11 @@ int qkv_rope_route_forward(const float* dA, const void* dA16, const ns_weight* w
 hipError_t launch_rope_qkv_append(float* q, const float* k, const float* v, void* kc, void* vc, int seq, int heads,
                                   int heads_kv, int head_size, int n_past, int n_dims, int mode, float freq_base,
                                   float freq_scale, float attn_factor, long long c_sl, long long c_head, hipStream_t st);
+// ... one row per REQUEST: row r at position pos[r] (device array) of its own cache slab (kc / vc + r * c_bs); rows with pos[r] outside [0, pos_cap)
+// are idle slots: nothing of them is read or written
+hipError_t launch_rope_qkv_append_rows(float* q, const float* k, const float* v, void* kc, void* vc, int rows, int heads, int heads_kv, int head_size,
+                                       const int* pos, int pos_cap, int n_dims, int mode, float freq_base, float freq_scale, float attn_factor,
+                                       long long c_bs, long long c_sl, long long c_head, hipStream_t st);
 hipError_t launch_aquant_u8(int row, int col, const float* src, int ld_src, uint8_t* dst, int ld_dst, float* scales,
                             int ld_scale, uint8_t* zps, int blocksize, float* blkreduce, hipStream_t st);
 // GEMM-sized form (16-byte loads, dword stores; bit-identical codes), optionally with the fp16 operand of the int8-reference GEMM

@@ -899,6 +899,58 @@ __global__ void rope_qkv_append_kernel(float* __restrict__ q, const float* __res
     vc[(long long)(n_past + i2) * c_sl + (long long)ih * c_head + e] = (_Float16)v[g];
   }
 }
+// The same for a batch of independent requests at decode (ns_hip_rope_qkv_append_rows): row r is request r at position pos[r] of its own cache
+// slab (kc / vc + r * c_bs).  rope_qkv_append_kernel's arithmetic with seq = 1 and n_past = pos[r], operation for operation, so a row holds the bits of
+// that launch on its slab.  pos is read HERE: a captured step moves with the array's contents; a position outside [0, pos_cap) marks an idle slot,
+// whose threads leave before they have read or written anything.
+__global__ void rope_qkv_append_rows_kernel(float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
+                                            _Float16* __restrict__ kc, _Float16* __restrict__ vc, int rows, int heads, int heads_kv, int head_size,
+                                            const int* __restrict__ pos, int pos_cap, int n_dims, int neox, float theta_scale, float freq_scale,
+                                            float attn_factor, long long c_bs, long long c_sl, long long c_head) {
+  const size_t npairs = neox ? size_t(head_size / n_dims) * (n_dims / 2) : size_t(head_size / 2);
+  const size_t nq = size_t(heads) * npairs, nk = size_t(heads_kv) * npairs, nv = size_t(heads_kv) * head_size;
+  const size_t gid = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (gid >= size_t(rows) * (nq + nk + nv)) return;
+  const size_t r = gid / (nq + nk + nv), it = gid % (nq + nk + nv);
+  const int n_past = pos[r];
+  if (n_past < 0 || n_past >= pos_cap) return;
+  q += r * heads * head_size, k += r * heads_kv * head_size, v += r * heads_kv * head_size;
+  kc += (long long)r * c_bs + (long long)n_past * c_sl, vc += (long long)r * c_bs + (long long)n_past * c_sl;
+  if (it < nq + nk) {
+    const bool is_k = it >= nq;
+    const size_t g = is_k ? it - nq : it;
+    const size_t ih = g / npairs;
+    const int pr = int(g % npairs);
+    float theta_base = float(n_past);
+    if (neox) theta_base = __fmul_rn(theta_base, freq_scale);
+    for (int t = 0; t < pr; t++) theta_base = __fmul_rn(theta_base, theta_scale);
+    const float theta = __fmul_rn(freq_scale, theta_base);
+    const float c = __fmul_rn(cosf(theta), attn_factor), s = __fmul_rn(sinf(theta), attn_factor);
+    int ia, ib;
+    if (neox) {
+      const int blk = pr / (n_dims / 2), ic = pr % (n_dims / 2);
+      ia = blk * n_dims + ic;
+      ib = ia + n_dims / 2;
+    } else {
+      ia = 2 * pr;
+      ib = ia + 1;
+    }
+    const float* x = (is_k ? k : q) + ih * head_size;
+    const float x0 = x[ia], x1 = x[ib];
+    const float y0 = __fsub_rn(__fmul_rn(x0, c), __fmul_rn(x1, s)), y1 = __fadd_rn(__fmul_rn(x0, s), __fmul_rn(x1, c));
+    if (is_k) {
+      _Float16* d = kc + (long long)ih * c_head;
+      d[ia] = (_Float16)y0;
+      d[ib] = (_Float16)y1;
+    } else {
+      q[ih * head_size + ia] = y0;
+      q[ih * head_size + ib] = y1;
+    }
+  } else {
+    const size_t g = it - nq - nk;
+    vc[(long long)(g / head_size) * c_head + (long long)(g % head_size)] = (_Float16)v[g];
+  }
+}
 // (cos, sin) * attn_factor of the mode-0 pairs of positions n_past .. n_past + m - 1: the angle arithmetic of
 // rope_qkv_append_kernel, once per token for all layers (ns_qkv_rope)
 // neox (ns_hip_rope_cos_sin_mode, mode 2): the NeoX branch's angles — freq_scale goes into theta_base first and is applied again below
@@ -1040,6 +1092,19 @@ hipError_t launch_rope_qkv_append(float* q, const float* k, const float* v, void
   hipLaunchKernelGGL(rope_qkv_append_kernel, grid1d(total, 256), dim3(256), 0, st, q, k, v, static_cast<_Float16*>(kc),
                      static_cast<_Float16*>(vc), seq, heads, heads_kv, head_size, n_past, n_dims, neox ? 1 : 0, theta_scale,
                      freq_scale, attn_factor, c_sl, c_head);
+  return hipGetLastError();
+}
+
+hipError_t launch_rope_qkv_append_rows(float* q, const float* k, const float* v, void* kc, void* vc, int rows, int heads, int heads_kv, int head_size,
+                                       const int* pos, int pos_cap, int n_dims, int mode, float freq_base, float freq_scale, float attn_factor,
+                                       long long c_bs, long long c_sl, long long c_head, hipStream_t st) {
+  const bool neox = (mode & 2) != 0;
+  const size_t npairs = neox ? size_t(head_size / n_dims) * (n_dims / 2) : size_t(head_size / 2);
+  const size_t total = size_t(rows) * ((heads + heads_kv) * npairs + size_t(heads_kv) * head_size);
+  if (total == 0) return hipSuccess;
+  hipLaunchKernelGGL(rope_qkv_append_rows_kernel, grid1d(total, 256), dim3(256), 0, st, q, k, v, static_cast<_Float16*>(kc), static_cast<_Float16*>(vc),
+                     rows, heads, heads_kv, head_size, pos, pos_cap, n_dims, neox ? 1 : 0, powf(freq_base, -2.0f / n_dims), freq_scale, attn_factor, c_bs,
+                     c_sl, c_head);
   return hipGetLastError();
 }
 
