@@ -682,6 +682,49 @@ int ns_hip_attn_decode_rows(const attn_fp32_fp16_fp16_fp32_fwd_args_t* dparams, 
  * [3] refused calls.  (ns_hip_attn_stats counts these launches too, by kernel family: its slots [3] and [2].) */
 void ns_hip_attn_rows_stats(unsigned long long out[4]);
 
+/* ---- Decode over a PAGED kv cache (block tables): the per-request pair above without one slab of full capacity per request -------------------
+ * The cache: a K pool and a V pool (fp16), each pool_blocks blocks of block_keys keys (a power of two from 16 to 256).  Element (block, key in block,
+ * kv head, e) lives at block * block_step + key * step_sl + head * step_head + e, all strides in elements and the caller's: position-major and
+ * head-major blocks are both expressible; a block must hold its cells ((block_keys - 1) * step_sl + (heads_kv - 1) * step_head + head_size <=
+ * block_step).  A DEVICE table int dBlockTable[requests][table_stride] maps logical block j of a request to a physical block id: key n of request b is
+ * in block dBlockTable[b][n / block_keys] at offset n % block_keys.  A request's capacity is table_stride * block_keys keys.  The table is the
+ * caller's (allocation policy, copy-on-write, prefix sharing: two requests may name the same block) and is read inside the launches, so a captured
+ * step moves by changing its contents.
+ * Out-of-range ids: an entry outside [0, pool_blocks) is never turned into an address.  The append and the store skip such a row (nothing of it is
+ * written; the append leaves its Q row as it is); the attention reads such a key as zeros, so THAT request's output row is unspecified, and every
+ * other request's row is what it would be with a valid table.
+ *
+ * ns_hip_rope_qkv_append_paged: ns_hip_rope_qkv_append_rows with the slabs replaced by the pools and the table.  Row r at position dPos[r] writes the
+ * cell its table row names; same arithmetic, operation for operation (modes 0 and 2, ext_factor 0, the same refusals), so a row holds the bits of the
+ * rows entry.  Idle: dPos[r] < 0 or dPos[r] >= min(pos_cap, capacity) writes nothing and leaves Q untouched.  One launch, capturable.
+ * Refused as well (-1, ns_hip_last_error, nothing written): a null table, a block_keys outside the set, pool_blocks < 1, table_stride < 1, strides
+ * with which a block does not hold its cells. */
+int ns_hip_rope_qkv_append_paged(float* dQ, const float* dK, const float* dV, void* dKpool16, void* dVpool16, int rows, int heads, int heads_kv,
+                                 int head_size, const int* dPos, int pos_cap, int n_dims, int mode, float freq_base, float freq_scale, float ext_factor,
+                                 float attn_factor, const int* dBlockTable, int table_stride, int block_keys, int pool_blocks, long long block_step,
+                                 long long cache_step_sl, long long cache_step_head, void* stream);
+/* ns_hip_attn_decode_paged: ns_hip_attn_decode_rows (same argument block, dKvLens, kv_len_bias, dst16) over the pools.  K / V of the block are the pool
+ * bases, step_k_sl / step_k_head_num (and V's) the strides inside a block, sl_kv the capacity of a request, which must equal table_stride * block_keys;
+ * step_k_bs / step_v_bs are not used.  Flags, scales, GQA, the head partition, tmp, zero rows for len_b = 0 and the refusals are those of the rows
+ * entry; the plan (kernel, grid, ranges, partials, workspace size) is that of the rows entry for the same shape and capacity, and with the same keys
+ * in the cells the output holds the same bits.  Kernels: the PAGED instantiations of the ring kernel, whose buffer descriptor spans a pool — for
+ * pools of (pool_blocks * block_step + 256) * 2 bytes below 4 GiB — and of the register kernel, which has 64-bit pointers and takes the larger pools
+ * (offsets are never wrapped).
+ * Refused as well (-1, ns_hip_last_error, nothing written): a null table, a block_keys outside the set, pool_blocks < 1, sl_kv != table_stride *
+ * block_keys, a block_step that is not a multiple of 8 elements, strides with which a block does not hold its cells. */
+int ns_hip_attn_decode_paged(const attn_fp32_fp16_fp16_fp32_fwd_args_t* dparams, const int* dKvLens, int kv_len_bias, const int* dBlockTable,
+                             int table_stride, int block_keys, int pool_blocks, long long block_step, void* dst16, void* stream);
+/* ns_hip_kv_paged_store: one launch copies the fp16 rows [pos0, pos0 + n) of a contiguous slab — element (position, head, e) at position *
+ * slab_step_sl + head * slab_step_head + e, what ns_hip_rope_qkv_append and the prefill forms write — into ONE request's pages, K and V both, bit for
+ * bit: this is how a prompt enters the pool.  dTableRow is that request's row of the table (dBlockTable + b * table_stride), table_len its entries.
+ * Refused: what the append refuses of the cache's description, and rows that reach behind table_len * block_keys. */
+int ns_hip_kv_paged_store(const void* dKslab16, const void* dVslab16, long long slab_step_sl, long long slab_step_head, int pos0, int n, int heads_kv,
+                          int head_size, void* dKpool16, void* dVpool16, const int* dTableRow, int table_len, int block_keys, int pool_blocks,
+                          long long block_step, long long cache_step_sl, long long cache_step_head, void* stream);
+/* Process-wide counts of ns_hip_attn_decode_paged, the four slots of ns_hip_attn_rows_stats: [0] launches on the LDS-ring kernel, [1] on the register
+ * kernel, [2] merge launches, [3] refused calls. */
+void ns_hip_attn_paged_stats(unsigned long long out[4]);
+
 /* ----------------------------------------------------------------------------------------------
  * Part 4b — mixture-of-experts matmul with the routing on the device.  Device twin of
  * ne_compute_forward_mul_mat_id_q_f32_bestla (/root/reference/neural_speed/core/ne_layers.c:7783-7916), which reads the

@@ -15,6 +15,7 @@
 #include <string>
 
 #include "ns_api_int.h"
+#include "ns_attn.h"
 #include "ns_route.h"
 #include "ns_route_op.h"
 
@@ -390,6 +391,61 @@ int ns_hip_rope_qkv_append_rows(float* dQ, const float* dK, const float* dV, voi
   return hip_ok(launch_rope_qkv_append_rows(dQ, dK, dV, dKcache16, dVcache16, rows, heads, heads_kv, head_size, dPos, pos_cap, n_dims, mode, freq_base,
                                             freq_scale, attn_factor, cache_step_bs, cache_step_sl, cache_step_head, (hipStream_t)stream),
                 "rope/kv-append (rows) launch") ? 0 : -1;
+}
+// what the two writers of a paged cache ask of its description (the attention's plan states the same rules, ns_attn_plan.cpp); nullptr: in order
+static const char* paged_cache_refusal(const AttnPage& pg, int heads_kv, int head_size, long long c_sl, long long c_head) {
+  if (!pg.table) return "the block table is null";
+  if (pg.block_shift < 0) return "block_keys must be a power of two from 16 to 256";
+  if (pg.pool_blocks < 1) return "pool_blocks must be at least 1";
+  if (pg.table_stride < 1) return "table_stride must be at least 1";
+  if (c_sl < 0 || c_head < 0 || pg.block_step < 1 ||
+      (long long)((1 << pg.block_shift) - 1) * c_sl + (long long)(heads_kv - 1) * c_head + head_size > pg.block_step)
+    return "a block's keys and kv heads (cache_step_sl / cache_step_head) do not fit inside block_step";
+  return nullptr;
+}
+int ns_hip_rope_qkv_append_paged(float* dQ, const float* dK, const float* dV, void* dKpool16, void* dVpool16, int rows, int heads, int heads_kv,
+                                 int head_size, const int* dPos, int pos_cap, int n_dims, int mode, float freq_base, float freq_scale, float ext_factor,
+                                 float attn_factor, const int* dBlockTable, int table_stride, int block_keys, int pool_blocks, long long block_step,
+                                 long long cache_step_sl, long long cache_step_head, void* stream) {
+  if (!have_device()) return -1;
+  if (!dQ || !dK || !dV || !dKpool16 || !dVpool16 || !dPos || rows < 0 || heads <= 0 || heads_kv <= 0 || head_size <= 0 || (head_size & 1) ||
+      n_dims <= 0 || (n_dims & 1) || n_dims > head_size || pos_cap < 0) {
+    set_error("rope_qkv_append_paged: invalid argument");
+    return -1;
+  }
+  if ((mode & ~2) != 0 || ext_factor != 0.f || ((mode & 2) && head_size % n_dims != 0)) {
+    set_error("rope_qkv_append_paged: only modes 0 and 2 (NeoX, head_size a multiple of n_dims) without YaRN extrapolation");
+    return -1;
+  }
+  const AttnPage pg = {dBlockTable, table_stride, attn_block_shift(block_keys), pool_blocks, block_step};
+  if (const char* text = paged_cache_refusal(pg, heads_kv, head_size, cache_step_sl, cache_step_head)) {
+    set_error(std::string("rope_qkv_append_paged: ") + text);
+    return -1;
+  }
+  return hip_ok(launch_rope_qkv_append_paged(dQ, dK, dV, dKpool16, dVpool16, rows, heads, heads_kv, head_size, dPos, pos_cap, n_dims, mode, freq_base,
+                                             freq_scale, attn_factor, pg, cache_step_sl, cache_step_head, (hipStream_t)stream),
+                "rope/kv-append (paged) launch") ? 0 : -1;
+}
+int ns_hip_kv_paged_store(const void* dKslab16, const void* dVslab16, long long slab_step_sl, long long slab_step_head, int pos0, int n, int heads_kv,
+                          int head_size, void* dKpool16, void* dVpool16, const int* dTableRow, int table_len, int block_keys, int pool_blocks,
+                          long long block_step, long long cache_step_sl, long long cache_step_head, void* stream) {
+  if (!have_device()) return -1;
+  if (!dKslab16 || !dVslab16 || !dKpool16 || !dVpool16 || pos0 < 0 || n < 0 || heads_kv <= 0 || head_size <= 0) {
+    set_error("kv_paged_store: invalid argument");
+    return -1;
+  }
+  const AttnPage pg = {dTableRow, table_len, attn_block_shift(block_keys), pool_blocks, block_step};
+  if (const char* text = paged_cache_refusal(pg, heads_kv, head_size, cache_step_sl, cache_step_head)) {
+    set_error(std::string("kv_paged_store: ") + text);
+    return -1;
+  }
+  if ((long long)pos0 + n > ((long long)table_len << pg.block_shift)) {
+    set_error("kv_paged_store: rows [pos0, pos0 + n) reach behind the request's capacity (table_len * block_keys)");
+    return -1;
+  }
+  return hip_ok(launch_kv_paged_store(dKslab16, dVslab16, slab_step_sl, slab_step_head, pos0, n, heads_kv, head_size, dKpool16, dVpool16, pg,
+                                      cache_step_sl, cache_step_head, (hipStream_t)stream),
+                "kv paged store launch") ? 0 : -1;
 }
 // device twins of bestla_device_elewise_f32 (NE_OP_SILU) and bestla_device_dup_f32 (ne_bestla.h:103-109)
 int ns_hip_silu_f32(const float* dSrc, float* dDst, size_t n, void* stream) {

@@ -68,7 +68,7 @@ static AttnKnobs attn_knobs() {
 
 // scratch of a one-row plan, then its launch; *merged: attn_merge_kernel followed
 static hipError_t launch_onerow_plan(AttnPlan pl, const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, AttnKnobs kn, const Affine& aff, hipStream_t st,
-                                     std::string* why, bool device_tmp, void* dst16, bool* merged) {
+                                     std::string* why, bool device_tmp, void* dst16, bool* merged, const AttnPage* page = nullptr) {
   float* ws = nullptr;
   if (pl.partial_bytes) {
     // partials go to the caller's workspace (`tmp`, sized by bestla_fusion_attn_workspace_size: the reference's own contract, and the only choice
@@ -77,7 +77,7 @@ static hipError_t launch_onerow_plan(AttnPlan pl, const attn_fp32_fp16_fp16_fp32
     if (!ws) ws = static_cast<float*>(stream_scratch(st, pl.partial_bytes, SLOT_ATTN_PARTIALS));
     if (!ws) {  // scratch allocation failed: planned again as one range, still correct
       kn.no_partials = true;
-      pl = attn_plan(a, dst16, kn, aff, why);
+      pl = attn_plan(a, dst16, kn, aff, why, page);
     }
   }
   // (nullptr, e.g. first use on a capturing stream: the merge launch)
@@ -143,6 +143,41 @@ static hipError_t launch_attn_decode_rows(const attn_fp32_fp16_fp16_fp32_fwd_arg
     g_attn_launches[pl.path].fetch_add(1, std::memory_order_relaxed);
     g_attn_rows[pl.path == AP_RING ? 0 : 1].fetch_add(1, std::memory_order_relaxed);
     if (merged) g_attn_rows[2].fetch_add(1, std::memory_order_relaxed);
+  }
+  return e;
+}
+
+// ns_hip_attn_decode_paged: the per-request plan of the same shape and capacity over the pools of a paged cache (attn_plan's `page`); what differs
+// from launch_attn_decode_rows is the AttnPage handed on and the counters.
+static std::atomic<uint64_t> g_attn_paged[4];  // ns_hip_attn_paged_stats
+static hipError_t launch_attn_decode_paged(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const int* lens, int bias, const AttnPage& page, hipStream_t st,
+                                           std::string* why, void* dst16) {
+  if (a.sl_q != 1) {
+    *why = "attention, paged cache: one query row per request (sl_q must be 1)";
+    return hipErrorInvalidValue;
+  }
+  if (!lens) {
+    *why = "attention, paged cache: dKvLens is null";
+    return hipErrorInvalidValue;
+  }
+  if (a.sl_kv < 1) {
+    *why = "attention, paged cache: sl_kv is the capacity of a request (at least 1 key)";
+    return hipErrorInvalidValue;
+  }
+  const AttnKnobs kn = attn_knobs();
+  Affine aff;
+  aff.k = lens, aff.delta = 1, aff.cap = a.sl_kv, aff.inlaunch = 0, aff.rows = 1, aff.bias = bias;
+  const AttnPlan pl = attn_plan(a, dst16, kn, aff, why, &page);
+  if (pl.path != AP_RING && pl.path != AP_SPLIT_REGS) {
+    if (why->empty()) *why = "attention, paged cache: no split kernel takes this call";
+    return hipErrorInvalidValue;
+  }
+  bool merged = false;
+  const hipError_t e = launch_onerow_plan(pl, a, kn, aff, st, why, a.tmp != nullptr, dst16, &merged, &page);
+  if (e == hipSuccess) {
+    g_attn_launches[pl.path].fetch_add(1, std::memory_order_relaxed);
+    g_attn_paged[pl.path == AP_RING ? 0 : 1].fetch_add(1, std::memory_order_relaxed);
+    if (merged) g_attn_paged[2].fetch_add(1, std::memory_order_relaxed);
   }
   return e;
 }
@@ -228,6 +263,23 @@ int ns_hip_attn_decode_rows(const attn_fp32_fp16_fp16_fp32_fwd_args_t* a, const 
     return -1;
   }
   return 0;
+}
+
+int ns_hip_attn_decode_paged(const attn_fp32_fp16_fp16_fp32_fwd_args_t* a, const int* dKvLens, int kv_len_bias, const int* dBlockTable, int table_stride,
+                             int block_keys, int pool_blocks, long long block_step, void* dst16, void* stream) {
+  std::string why;
+  const AttnPage page = {dBlockTable, table_stride, attn_block_shift(block_keys), pool_blocks, block_step};
+  const hipError_t e = a ? launch_attn_decode_paged(*a, dKvLens, kv_len_bias, page, static_cast<hipStream_t>(stream), &why, dst16) : hipErrorInvalidValue;
+  if (e != hipSuccess) {
+    g_attn_paged[3].fetch_add(1, std::memory_order_relaxed);
+    set_error(why.empty() ? std::string("attention launch (paged cache): ") + (a ? hipGetErrorString(e) : "null arguments") : why);
+    return -1;
+  }
+  return 0;
+}
+
+void ns_hip_attn_paged_stats(unsigned long long out[4]) {
+  for (int i = 0; i < 4; i++) out[i] = g_attn_paged[i].load(std::memory_order_relaxed);
 }
 
 void ns_hip_attn_rows_stats(unsigned long long out[4]) {

@@ -93,6 +93,49 @@ __host__ __device__ __forceinline__ int attn_live_splits(const AttnSplitParams& 
   return max(1, (sl_kv + kps - 1) / kps);
 }
 
+// ---- a paged cache (ns_hip_attn_decode_paged, ns_hip_rope_qkv_append_paged, ns_hip_kv_paged_store) -------------------------------------------------
+// K and V live in two pools of pool_blocks blocks of (1 << block_shift) keys; block b starts block_step elements behind block b - 1, inside a block a
+// key's row is step_sl elements behind its predecessor's and a head's step_head_num behind the head before it (the caller's strides: position-major
+// and head-major blocks are both expressible).  table[request][table_stride] (DEVICE memory) names the physical block of a request's logical block.
+// The table is the caller's and read inside the launch, so nothing on the host can vouch for an entry: an id outside [0, pool_blocks) never becomes
+// an address (attn_page_at answers -1).  Two requests may name the same block.
+struct AttnPage {
+  const int* table;
+  int table_stride;  // entries per request: a request's capacity is table_stride << block_shift keys
+  int block_shift;   // log2 of the keys per block (4 .. 8)
+  int pool_blocks;
+  long long block_step;
+};
+// block_keys -> block_shift; -1: not a power of two from 16 to 256 (which every entry refuses)
+inline int attn_block_shift(int block_keys) {
+  for (int s = 4; s <= 8; s++)
+    if (block_keys == 1 << s) return s;
+  return -1;
+}
+// Argument block of the PAGED instantiations: the fields are added AROUND AttnSplitParams, so every other instantiation's argument block is what it was.
+struct AttnPagedParams {
+  AttnSplitParams sp;
+  AttnPage pg;
+};
+// Key n of a request -> its cell.  THE translation: the kernels, the append, the store and tests/tools/attn_paged_plan_main.cpp all go through these two.
+// attn_page_at: the element offset, from the pool's base, of key n's row in physical block `blk` (head 0, dim 0; step_sl: K's or V's row stride), or
+// -1 = no access: blk is not a block of the pool.
+__host__ __device__ __forceinline__ long long attn_page_at(const AttnPage& pg, int blk, int n, long long step_sl) {
+  if (unsigned(blk) >= unsigned(pg.pool_blocks)) return -1;
+  return (long long)blk * pg.block_step + (long long)(n & ((1 << pg.block_shift) - 1)) * step_sl;
+}
+// attn_page_cell: the same for key n of request b through the table; -1 also for a key outside the request's capacity.
+__host__ __device__ __forceinline__ long long attn_page_cell(const AttnPage& pg, int b, int n, long long step_sl) {
+  const int j = n >> pg.block_shift;
+  if (n < 0 || j >= pg.table_stride) return -1;
+  return attn_page_at(pg, pg.table[(long long)b * pg.table_stride + j], n, step_sl);
+}
+// The ring kernel addresses a pool through ONE 32-bit buffer descriptor over the whole pool (offsets are never wrapped): a pool it cannot address is
+// served by the register kernel, whose pointers are 64-bit.  256 elements of slack as in the slab rule (ns_attn_plan.cpp, attn_in32).
+__host__ __device__ __forceinline__ bool attn_page_in32(const AttnPage& pg) {
+  return ((unsigned long long)pg.pool_blocks * (unsigned long long)pg.block_step + 256ull) * 2ull < (1ull << 32);
+}
+
 // ---- the launch decision as a value (ns_attn_plan.cpp) -------------------------------------------------------------------------------------
 // Every tunable the decision reads.  attn_knobs() (ns_attn.cpp) fills it from ns_hip_set_tuning's atomics and the environment.
 struct AttnKnobs {
@@ -126,6 +169,8 @@ struct AttnPlan {
   dim3 grid, block;
   size_t lds = 0;                    // dynamic LDS bytes
   bool rows = false;                 // one-row paths: one live length per batch entry (the ROWS instantiations; sp.kmove an array, sp.kdelta its bias)
+  bool paged = false;                // ... over a paged cache (the PAGED instantiations; page: their AttnPage, sp.a.k / sp.a.v the pool bases)
+  AttnPage page = {};
   bool want_tickets = false;         // ranges merge inside the launch if the stream's ticket buffer can be had
   bool merge = false;                // attn_merge_kernel follows (also when tickets are wanted and cannot be had)
   size_t partial_bytes = 0;          // of sp.ws
@@ -133,7 +178,10 @@ struct AttnPlan {
 };
 bool attn_shape_ok(int head_num, int heads_kv, int head_size, int sl_q, int sl_kv, bool causal, std::string* why);
 // dst16: the optional fp16 shadow of dst (its alignment is part of the decision).  AP_REFUSED: *why says what is wrong with the call.
-AttnPlan attn_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst16, const AttnKnobs& knobs, const Affine& aff, std::string* why);
+// page != nullptr (with aff.rows): K / V are the pools of a paged cache — the plan of the per-request form of the same shape and capacity, plus the paging's
+// own refusals and the 32-bit rule of the pool (attn_page_in32) in place of the slab's.
+AttnPlan attn_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst16, const AttnKnobs& knobs, const Affine& aff, std::string* why,
+                   const AttnPage* page = nullptr);
 // what bestla_fusion_attn_workspace_size answers: it knows neither strides nor alignment, so the most any plan of the shape can need
 size_t attn_ws_bytes(const AttnKnobs& knobs, int batch, int head_num, int heads_kv, int head_size, int sl_q, int sl_kv);
 

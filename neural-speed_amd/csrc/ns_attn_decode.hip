@@ -293,8 +293,22 @@ __device__ __forceinline__ void attn_zero_rows(const AttnSplitParams& sp, int ch
 }
 
 // ROWS (both split kernels and the merge): one live length per batch entry (ns_hip_attn_decode_rows, AttnPlan::rows); false: the code as without it
-template <int G, int DPL, bool ROWS = false>  // G query heads per kv head; DPL head dims per lane (8: head_size <= 128, 16: <= 256)
-__global__ __launch_bounds__(kAttnThreads) void attn_split_kernel(const AttnSplitParams sp) {
+// PAGED (both split kernels, with ROWS): K / V are the pools of a paged cache (ns_hip_attn_decode_paged, AttnPlan::paged) — key j of request ibs is read
+// from the cell attn_page_cell names; the assignment of keys to lanes and steps and the order of the softmax updates are those of the slab form, so the
+// two give the same bits over the same keys.  A block id outside the pool is never turned into an address: such a key reads as zeros (its request's
+// row is then whatever that gives; no other request is touched).  A PAGED kernel takes an argument block of its own (AttnPagedParams: the page
+// description around AttnSplitParams); every other instantiation keeps the block, and the code, it had.
+template <bool PAGED>
+using AttnKernelArgs = std::conditional_t<PAGED, AttnPagedParams, AttnSplitParams>;
+__device__ __forceinline__ const AttnSplitParams& attn_sp(const AttnSplitParams& kp) { return kp; }
+__device__ __forceinline__ const AttnSplitParams& attn_sp(const AttnPagedParams& kp) { return kp.sp; }
+__device__ __forceinline__ AttnPage attn_pg(const AttnSplitParams&) { return AttnPage{}; }
+__device__ __forceinline__ const AttnPage& attn_pg(const AttnPagedParams& kp) { return kp.pg; }
+
+template <int G, int DPL, bool ROWS = false, bool PAGED = false>  // G query heads per kv head; DPL head dims per lane (8: head_size <= 128, 16: <= 256)
+__global__ __launch_bounds__(kAttnThreads) void attn_split_kernel(const AttnKernelArgs<PAGED> kp) {
+  const AttnSplitParams& sp = attn_sp(kp);
+  [[maybe_unused]] const AttnPage& pg = attn_pg(kp);
   const AttnParams& p = sp.a;
   __shared__ float ml_s[4][G][2];
   extern __shared__ float acc_s[];  // [4 waves][G][16 * DPL]
@@ -326,6 +340,7 @@ __global__ __launch_bounds__(kAttnThreads) void attn_split_kernel(const AttnSpli
   const int d0 = dl * DPL;
   const bool dact = d0 < hs;  // head sizes that are not a multiple of DPL are rejected by the host
 
+  // (PAGED: p.k / p.v are the pools' bases and attn_plan has set the batch strides to 0 — a request has no slab)
   const _Float16* kb = p.k + ibs * p.step_k_bs + ihkv * p.step_k_head_num + d0;
   const _Float16* vb = p.v + ibs * p.step_v_bs + ihkv * p.step_v_head_num + d0;
 
@@ -369,6 +384,20 @@ __global__ __launch_bounds__(kAttnThreads) void attn_split_kernel(const AttnSpli
 #pragma unroll
     for (int u = 0; u < U; u++) {
       const int j = jb + 16 * u;
+      if constexpr (PAGED) {  // the key's cell in either pool (the table entry is fetched once: the same address); -1: no access, the key reads as zeros
+        long long ck = -1, cv = -1;
+        if (dact && j < j1) ck = attn_page_cell(pg, ibs, j, p.step_k_sl), cv = attn_page_cell(pg, ibs, j, p.step_v_sl);
+#pragma unroll
+        for (int c = 0; c < DPL / 8; c++) {
+          kv[u][c] = half8_t{0, 0, 0, 0, 0, 0, 0, 0};
+          vv[u][c] = kv[u][c];
+          if (ck >= 0 && cv >= 0) {
+            kv[u][c] = __builtin_nontemporal_load(reinterpret_cast<const half8_t*>(kb + ck + 8 * c));
+            vv[u][c] = __builtin_nontemporal_load(reinterpret_cast<const half8_t*>(vb + cv + 8 * c));
+          }
+        }
+        continue;
+      }
       const bool live = dact && j < j1;
 #pragma unroll
       for (int c = 0; c < DPL / 8; c++) {
@@ -478,8 +507,16 @@ __global__ __launch_bounds__(kAttnThreads) void attn_split_kernel(const AttnSpli
 #ifndef NS_AS_ABL
 #define NS_AS_ABL 0  // timing ablations (diagnostic builds, wrong results): 1 no arithmetic in the key loop, 2 nothing behind the key loop, 3 no key loop at all (nothing streamed), 4 streamed but never read
 #endif
-template <int G, int LPK = 16, bool ROWS = false>  // LPK lanes per key: 16 (head sizes 72 .. 128) or 8 (40 .. 64: a 1 KiB request then holds 8 key rows, a wave step 8 keys)
-__global__ __launch_bounds__(kAttnThreads) void attn_stream_kernel(const AttnSplitParams sp) {
+// PAGED.  A wave's keys of one step are KPW <= 8 consecutive keys, a block holds 16 or more: they lie in at most two blocks, whatever the range's
+// start.  Both table entries of a step are wave-uniform and fetched by scalar loads (the scalar cache, counted by lgkmcnt: the hand-counted vmcnt
+// of the stream is untouched, and a refill's entries are requested one batch ahead, in front of the wait that batch has anyway); every lane picks
+// its key's block of the two and forms its offset into ONE descriptor that spans the pool.  A key at or behind the range's end, and a key whose
+// block id is not a block of the pool, gets the offset pool_bytes — outside the descriptor, so it fetches nothing.  The dependent load in front of
+// the stream is the price of the translation (docs/kernels/attention.md, "Decode over a paged cache").
+template <int G, int LPK = 16, bool ROWS = false, bool PAGED = false>  // LPK lanes per key: 16 (head sizes 72 .. 128) or 8 (40 .. 64: a 1 KiB request then holds 8 key rows, a wave step 8 keys)
+__global__ __launch_bounds__(kAttnThreads) void attn_stream_kernel(const AttnKernelArgs<PAGED> kp) {
+  const AttnSplitParams& sp = attn_sp(kp);
+  [[maybe_unused]] const AttnPage& pg = attn_pg(kp);
   constexpr int DPL = 8;
   constexpr int KPW = 64 / LPK;  // keys per wave and step
   constexpr int KPS = 4 * KPW;   // keys per workgroup and step
@@ -520,6 +557,29 @@ __global__ __launch_bounds__(kAttnThreads) void attn_stream_kernel(const AttnSpl
   //      ring would be usable only when the whole ring has landed) ----
   //      Written by hand: for a load it knows hipcc waits with vmcnt(0) at the first use, i.e. for the whole ring (it does not count
   //      the LDS-DMA requests behind it); the counted wait is in step 2.
+  // PAGED: the two table entries of wave step s (clamped to the table row: steps past the range's end fetch nothing anyway).  An asm, so that it is
+  // a scalar load whatever hipcc can prove of the table; its results are used behind an s_waitcnt lgkmcnt(0) only (the "+s" constraints behind each wait).
+  const int tshift = PAGED ? pg.block_shift : 0;
+  const int* trow = PAGED ? pg.table + (long long)ibs * pg.table_stride : nullptr;
+  auto fetch_ids = [&](int s, int& ba, int& bb) {
+    const int a = j0 + KPS * s + KPW * w;
+    const int ea = min(a >> tshift, pg.table_stride - 1), eb = min((a + KPW - 1) >> tshift, pg.table_stride - 1);
+    // (the addresses are wave-uniform, said explicitly; the halves go through uint32_t: readfirstlane returns an int, and a low half with bit 31
+    // set must not be sign-extended into the high one)
+    auto uniform64 = [](const int* ptr) {
+      const uint64_t v = reinterpret_cast<uint64_t>(ptr);
+      const uint32_t lo = __builtin_amdgcn_readfirstlane(uint32_t(v)), hi = __builtin_amdgcn_readfirstlane(uint32_t(v >> 32));
+      return (uint64_t(hi) << 32) | lo;
+    };
+    const uint64_t ua = uniform64(trow + ea), ub = uniform64(trow + eb);
+    asm volatile("s_load_dword %0, %1, 0x0" : "=s"(ba) : "s"(ua) : "memory");
+    asm volatile("s_load_dword %0, %1, 0x0" : "=s"(bb) : "s"(ub) : "memory");
+  };
+  int ida[kAsSteps], idb[kAsSteps];
+  if constexpr (PAGED) {
+#pragma unroll
+    for (int s = 0; s < kAsSteps; s++) fetch_ids(s, ida[s], idb[s]);
+  }
   typedef float f4_t __attribute__((ext_vector_type(4)));
   f4_t qa[G], qb[G];
 #pragma unroll
@@ -531,10 +591,12 @@ __global__ __launch_bounds__(kAttnThreads) void attn_stream_kernel(const AttnSpl
   }
   __builtin_amdgcn_sched_barrier(0);
   // ---- 1. the whole range (up to the ring's depth) is requested before anything else is touched ----
-  const _Float16* kh = p.k + ibs * p.step_k_bs + ihkv * p.step_k_head_num;
-  const _Float16* vh = p.v + ibs * p.step_v_bs + ihkv * p.step_v_head_num;
-  const uint32_t k_bytes = j1 > j0 ? uint32_t((size_t(j1 - 1) * p.step_k_sl + hs) * 2) : 0u;
-  const uint32_t v_bytes = j1 > j0 ? uint32_t((size_t(j1 - 1) * p.step_v_sl + hs) * 2) : 0u;
+  // (PAGED: the descriptors span the pools — attn_plan gives this kernel only pools of less than 4 GiB, attn_page_in32)
+  const uint32_t pool_bytes = PAGED ? uint32_t(size_t(pg.pool_blocks) * size_t(pg.block_step) * 2) : 0u;
+  const _Float16* kh = PAGED ? p.k : p.k + ibs * p.step_k_bs + ihkv * p.step_k_head_num;
+  const _Float16* vh = PAGED ? p.v : p.v + ibs * p.step_v_bs + ihkv * p.step_v_head_num;
+  const uint32_t k_bytes = PAGED ? pool_bytes : j1 > j0 ? uint32_t((size_t(j1 - 1) * p.step_k_sl + hs) * 2) : 0u;
+  const uint32_t v_bytes = PAGED ? pool_bytes : j1 > j0 ? uint32_t((size_t(j1 - 1) * p.step_v_sl + hs) * 2) : 0u;
   // (the descriptors are wave-uniform; said explicitly, or hipcc wraps every request into a readfirstlane loop)
   auto uniform_ptr = [](const _Float16* ptr) {
     const uint64_t v = reinterpret_cast<uint64_t>(ptr);
@@ -556,9 +618,34 @@ __global__ __launch_bounds__(kAttnThreads) void attn_stream_kernel(const AttnSpl
     }
 #endif
   };
+  // PAGED: step s with its two table entries — the lane's key, its block of the two, its cell through attn_page_at
+  auto issue_paged = [&](int s, int ba, int bb) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const int a = j0 + KPS * s + KPW * w, key = a + l / LPK;
+    const int blk = (key >> tshift) == (a >> tshift) ? ba : bb;
+    const long long ck = attn_page_at(pg, blk, key, p.step_k_sl), cv = attn_page_at(pg, blk, key, p.step_v_sl);
+    const bool on = key < j1 && ck >= 0;
+    const uint32_t ko = on ? uint32_t(ck + ihkv * p.step_k_head_num + d0) * 2u : pool_bytes;
+    const uint32_t vo = on ? uint32_t(cv + ihkv * p.step_v_head_num + d0) * 2u : pool_bytes;
+    const LdsPtr dst = ring + (s & (kAsSteps - 1)) * 2048;
+    if (dact) {
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, reinterpret_cast<__attribute__((address_space(3))) void*>(dst), 16, ko, 0, 0, 2);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, reinterpret_cast<__attribute__((address_space(3))) void*>(dst + 1024), 16, vo, 0, 0, 2);
+    }
+#endif
+  };
+  if constexpr (PAGED) {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
-  for (int s = 0; s < kAsSteps; s++)
-    if (s < nsteps) issue(s);
+    for (int s = 0; s < kAsSteps; s++) asm volatile("" : "+s"(ida[s]), "+s"(idb[s]));  // (uses stay behind the wait)
+#pragma unroll
+    for (int s = 0; s < kAsSteps; s++)
+      if (s < nsteps) issue_paged(s, ida[s], idb[s]);
+  } else {
+#pragma unroll
+    for (int s = 0; s < kAsSteps; s++)
+      if (s < nsteps) issue(s);
+  }
   __builtin_amdgcn_sched_barrier(0);
 
   // ---- 2. the query rows' first use (their wait is counted: the stream's requests are younger and stay in flight) ----
@@ -605,6 +692,11 @@ __global__ __launch_bounds__(kAttnThreads) void attn_stream_kernel(const AttnSpl
     }
   };
   for (int s0 = 0; s0 < nsteps; s0 += U) {
+    int ra[U], rb[U];  // PAGED: the table entries of the steps this batch's slots are refilled with, requested in front of the batch's own wait
+    if constexpr (PAGED) {
+#pragma unroll
+      for (int u = 0; u < U; u++) fetch_ids(s0 + kAsSteps + u, ra[u], rb[u]);
+    }
     wait_steps(min(nsteps - s0 - U, kAsSteps - U));
     if (NS_AS_ABL == 4) {
 #pragma unroll
@@ -623,9 +715,17 @@ __global__ __launch_bounds__(kAttnThreads) void attn_stream_kernel(const AttnSpl
     for (int u = 0; u < U; u++) asm volatile("" : "+v"(kr[u]), "+v"(vr[u]));  // (uses stay behind the wait)
     __builtin_amdgcn_sched_barrier(0);
     // the slots are free: the steps one ring ahead are requested before this batch is multiplied
+    if constexpr (PAGED) {
 #pragma unroll
-    for (int u = 0; u < U; u++)
-      if (s0 + kAsSteps + u < nsteps) issue(s0 + kAsSteps + u);
+      for (int u = 0; u < U; u++) asm volatile("" : "+s"(ra[u]), "+s"(rb[u]));  // (behind the lgkmcnt(0) above: the entries have arrived)
+#pragma unroll
+      for (int u = 0; u < U; u++)
+        if (s0 + kAsSteps + u < nsteps) issue_paged(s0 + kAsSteps + u, ra[u], rb[u]);
+    } else {
+#pragma unroll
+      for (int u = 0; u < U; u++)
+        if (s0 + kAsSteps + u < nsteps) issue(s0 + kAsSteps + u);
+    }
     __builtin_amdgcn_sched_barrier(0);
     if (NS_AS_ABL == 1) {
       acc[0][0] += __builtin_bit_cast(float, kr[0].x ^ vr[U - 1].y);
@@ -768,6 +868,25 @@ __global__ __launch_bounds__(128) void attn_merge_kernel(const AttnSplitParams s
 }
 
 // ---- launch of a plan (ns_attn_plan.cpp) -------------------------------------------------------------------------------------------------
+template <int G>
+static hipError_t launch_paged_g(const AttnPlan& pl, const AttnSplitParams& sp, hipStream_t st) {
+  const AttnPagedParams pp = {sp, pl.page};
+  if (pl.path == AP_RING)
+    return pl.lpk == 16 ? launch_lds<attn_stream_kernel<G, 16, true, true>>(int(kAsLdsBytes), pl.grid, pl.block, pl.lds, st, pp)
+                        : launch_lds<attn_stream_kernel<G, 8, true, true>>(int(kAsLdsBytes), pl.grid, pl.block, pl.lds, st, pp);
+  if (pl.dpl == 8) {
+    hipLaunchKernelGGL((attn_split_kernel<G, 8, true, true>), pl.grid, pl.block, pl.lds, st, pp);
+  } else {
+    hipLaunchKernelGGL((attn_split_kernel<G, 16, true, true>), pl.grid, pl.block, pl.lds, st, pp);
+  }
+  return hipGetLastError();
+}
+static hipError_t launch_paged(const AttnPlan& pl, const AttnSplitParams& sp, hipStream_t st) {
+  return pl.G == 1   ? launch_paged_g<1>(pl, sp, st)
+         : pl.G == 2 ? launch_paged_g<2>(pl, sp, st)
+         : pl.G == 4 ? launch_paged_g<4>(pl, sp, st)
+                     : launch_paged_g<8>(pl, sp, st);
+}
 template <int G, bool ROWS>
 static hipError_t launch_split_g(const AttnPlan& pl, const AttnSplitParams& sp, hipStream_t st) {
   if (pl.path == AP_RING)  // head sizes 72 .. 128: sixteen lanes per key, 40 .. 64: eight
@@ -796,7 +915,7 @@ hipError_t launch_attn_onerow(const AttnPlan& pl, float* ws, uint32_t* tickets, 
   }
   AttnSplitParams sp = pl.sp;
   sp.ws = ws, sp.tickets = tickets;
-  hipError_t e = pl.rows ? launch_split<true>(pl, sp, st) : launch_split<false>(pl, sp, st);
+  hipError_t e = pl.paged ? launch_paged(pl, sp, st) : pl.rows ? launch_split<true>(pl, sp, st) : launch_split<false>(pl, sp, st);
   if (e != hipSuccess) return e;
   if (sp.nsplit > 1 && !sp.tickets) e = launch_attn_merge(sp, pl.grid.z, st, pl.rows);  // (grid.z: the batch)
   return e;

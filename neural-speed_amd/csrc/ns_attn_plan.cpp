@@ -89,7 +89,26 @@ static bool attn_in32(int sl_kv, long long step_k_sl, long long step_v_sl) {
   return (size_t(sl_kv) * size_t(step_k_sl) + 256) * 2 < (size_t(1) << 32) && (size_t(sl_kv) * size_t(step_v_sl) + 256) * 2 < (size_t(1) << 32);
 }
 
-AttnPlan attn_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst16, const AttnKnobs& kn, const Affine& aff, std::string* why) {
+// What a paged call must satisfy beyond the per-request form (ns_hip_attn_decode_paged); nullptr: nothing to say against it.
+// The last rule is what makes every cell of a valid block id an address inside the pool: a block holds its keys' rows of every kv head.
+static const char* attn_page_refusal(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const AttnPage& pg) {
+  if (!pg.table) return "attention, paged cache: the block table is null";
+  if (pg.block_shift < 4 || pg.block_shift > 8) return "attention, paged cache: block_keys must be a power of two from 16 to 256";  // (attn_block_shift)
+  const int block_keys = 1 << pg.block_shift;
+  if (pg.pool_blocks < 1) return "attention, paged cache: pool_blocks must be at least 1";
+  if (pg.table_stride < 1 || (long long)pg.table_stride * block_keys != a.sl_kv)
+    return "attention, paged cache: sl_kv is the capacity of a request and must equal table_stride * block_keys";
+  if (pg.block_step < 1 || pg.block_step % 8 != 0) return "attention, paged cache: block_step must be a positive multiple of 8 elements (16-byte aligned blocks)";
+  const long long last = (long long)(block_keys - 1);
+  if (a.step_k_sl < 0 || a.step_v_sl < 0 || a.step_k_head_num < 0 || a.step_v_head_num < 0 ||
+      last * a.step_k_sl + (long long)(a.heads_kv - 1) * a.step_k_head_num + a.head_size > pg.block_step ||
+      last * a.step_v_sl + (long long)(a.heads_kv - 1) * a.step_v_head_num + a.head_size > pg.block_step)
+    return "attention, paged cache: a block's keys and kv heads (step_k / step_v strides) do not fit inside block_step";
+  return nullptr;
+}
+
+AttnPlan attn_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst16, const AttnKnobs& kn, const Affine& aff, std::string* why,
+                   const AttnPage* page) {
   AttnPlan pl;
   memset(&pl.sp, 0, sizeof(pl.sp));
   auto refuse = [&](const char* text) {
@@ -132,10 +151,16 @@ AttnPlan attn_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst
   if (aff.k && (a.sl_q != 1 || aff.cap < a.sl_kv))
     return refuse("attention: a moving context length is served for decode steps (one query row) within the cache's capacity");
   if (aff.k && aff.rows && aff.cap != a.sl_kv) return refuse("attention: per-request context lengths take sl_kv as the capacity of a request's slab");
+  // a paged cache (ns_hip_attn_decode_paged): the per-request form with K / V as pools; the batch strides of K / V are not used
+  if (page) {
+    if (!aff.k || !aff.rows) return refuse("attention, paged cache: served for per-request context lengths only");
+    if (const char* text = attn_page_refusal(a, *page)) return refuse(text);
+    pl.paged = true, pl.page = *page;
+    p.step_k_bs = p.step_v_bs = 0;  // (the kernels add ibs * step_bs to the pools' bases)
+  }
   // what every kernel but attn_kernel asks of K and V: a contiguous head dimension and 16-byte aligned rows
   const bool rows_ok = a.step_k_head_size == 1 && a.step_v_head_size == 1 && a.step_k_sl % 8 == 0 && a.step_v_sl % 8 == 0 &&
-                       a.step_k_head_num % 8 == 0 && a.step_v_head_num % 8 == 0 && a.step_k_bs % 8 == 0 &&
-                       a.step_v_bs % 8 == 0 && (reinterpret_cast<uintptr_t>(a.K) & 15) == 0 &&
+                       a.step_k_head_num % 8 == 0 && a.step_v_head_num % 8 == 0 && (page || (a.step_k_bs % 8 == 0 && a.step_v_bs % 8 == 0)) && (reinterpret_cast<uintptr_t>(a.K) & 15) == 0 &&
                        (reinterpret_cast<uintptr_t>(a.V) & 15) == 0;
 
   const bool biased = (a.attn_flags & (NS_ATTN_FLAG_IS_ALIBI8 | NS_ATTN_FLAG_IS_TANH30)) != 0;
@@ -223,7 +248,9 @@ AttnPlan attn_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst
   // the LDS rings: head sizes 40 .. 128 (72 .. 128: sixteen lanes per key; 40 .. 64: eight — with sixteen, half of a request's lanes would carry
   // nothing: measured slower from 4096 positions on), row offsets inside a 32-bit buffer descriptor, 16-byte query loads
   const bool q16 = (reinterpret_cast<uintptr_t>(a.Q) & 15) == 0 && a.step_q_bs % 4 == 0 && a.step_q_head_num % 4 == 0 && a.step_q_sl % 4 == 0;
-  const bool stream = a.head_size > 32 && a.head_size <= 128 && attn_in32(rule_kv, a.step_k_sl, a.step_v_sl) && q16 && kn.attn_stream != 0;
+  // (a paged cache: the ring kernel's descriptor spans the pool — attn_page_in32 in place of the slab's rule; a larger pool takes the register kernel)
+  const bool in32 = page ? attn_page_in32(*page) : attn_in32(rule_kv, a.step_k_sl, a.step_v_sl);
+  const bool stream = a.head_size > 32 && a.head_size <= 128 && in32 && q16 && kn.attn_stream != 0;
   const int lpk = a.head_size > 64 ? 16 : 8;
   const int batch_keys = (G * 8 <= 16 ? 4 : 2) * 4 * (64 / lpk);  // attn_stream_kernel's U x keys per workgroup step
   // head sizes above 128 (register kernel, 16 dims per lane) take the ring kernel's range rule too: 16 x 256 heads 14.6 -> 10.4 us at 512 keys,

@@ -450,6 +450,14 @@ hipError_t launch_rope_qkv_append(float* q, const float* k, const float* v, void
 hipError_t launch_rope_qkv_append_rows(float* q, const float* k, const float* v, void* kc, void* vc, int rows, int heads, int heads_kv, int head_size,
                                        const int* pos, int pos_cap, int n_dims, int mode, float freq_base, float freq_scale, float attn_factor,
                                        long long c_bs, long long c_sl, long long c_head, hipStream_t st);
+// ... over a paged cache (AttnPage, ns_attn.h): row r at the cell its table row names for pos[r]; the store copies rows [pos0, pos0 + n) of a slab into
+// one request's pages (pg.table: that request's table row)
+struct AttnPage;
+hipError_t launch_rope_qkv_append_paged(float* q, const float* k, const float* v, void* kc, void* vc, int rows, int heads, int heads_kv, int head_size,
+                                        const int* pos, int pos_cap, int n_dims, int mode, float freq_base, float freq_scale, float attn_factor,
+                                        const AttnPage& pg, long long c_sl, long long c_head, hipStream_t st);
+hipError_t launch_kv_paged_store(const void* ks, const void* vs, long long s_sl, long long s_head, int pos0, int n, int heads_kv, int head_size, void* kc,
+                                 void* vc, const AttnPage& pg, long long c_sl, long long c_head, hipStream_t st);
 hipError_t launch_aquant_u8(int row, int col, const float* src, int ld_src, uint8_t* dst, int ld_dst, float* scales,
                             int ld_scale, uint8_t* zps, int blocksize, float* blkreduce, hipStream_t st);
 // GEMM-sized form (16-byte loads, dword stores; bit-identical codes), optionally with the fp16 operand of the int8-reference GEMM

@@ -17,6 +17,7 @@
 #include <cfloat>
 #include <cstdlib>
 
+#include "ns_attn.h"
 #include "ns_common.h"
 #include "ns_route.h"
 
@@ -903,19 +904,12 @@ __global__ void rope_qkv_append_kernel(float* __restrict__ q, const float* __res
 // slab (kc / vc + r * c_bs).  rope_qkv_append_kernel's arithmetic with seq = 1 and n_past = pos[r], operation for operation, so a row holds the bits of
 // that launch on its slab.  pos is read HERE: a captured step moves with the array's contents; a position outside [0, pos_cap) marks an idle slot,
 // whose threads leave before they have read or written anything.
-__global__ void rope_qkv_append_rows_kernel(float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
-                                            _Float16* __restrict__ kc, _Float16* __restrict__ vc, int rows, int heads, int heads_kv, int head_size,
-                                            const int* __restrict__ pos, int pos_cap, int n_dims, int neox, float theta_scale, float freq_scale,
-                                            float attn_factor, long long c_bs, long long c_sl, long long c_head) {
-  const size_t npairs = neox ? size_t(head_size / n_dims) * (n_dims / 2) : size_t(head_size / 2);
-  const size_t nq = size_t(heads) * npairs, nk = size_t(heads_kv) * npairs, nv = size_t(heads_kv) * head_size;
-  const size_t gid = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (gid >= size_t(rows) * (nq + nk + nv)) return;
-  const size_t r = gid / (nq + nk + nv), it = gid % (nq + nk + nv);
-  const int n_past = pos[r];
-  if (n_past < 0 || n_past >= pos_cap) return;
-  q += r * heads * head_size, k += r * heads_kv * head_size, v += r * heads_kv * head_size;
-  kc += (long long)r * c_bs + (long long)n_past * c_sl, vc += (long long)r * c_bs + (long long)n_past * c_sl;
+// item `it` of one row (a rotated pair of Q or K, or an element of V): q / k / v point at the row, kc / vc at its cache cell (head 0).  Shared by the
+// slab form and the paged form below, so that the two hold the same bits.
+__device__ __forceinline__ void rope_append_row_item(float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
+                                                     _Float16* __restrict__ kc, _Float16* __restrict__ vc, size_t it, size_t nq, size_t nk, size_t npairs,
+                                                     int n_past, int head_size, int n_dims, int neox, float theta_scale, float freq_scale,
+                                                     float attn_factor, long long c_head) {
   if (it < nq + nk) {
     const bool is_k = it >= nq;
     const size_t g = is_k ? it - nq : it;
@@ -949,6 +943,64 @@ __global__ void rope_qkv_append_rows_kernel(float* __restrict__ q, const float* 
   } else {
     const size_t g = it - nq - nk;
     vc[(long long)(g / head_size) * c_head + (long long)(g % head_size)] = (_Float16)v[g];
+  }
+}
+__global__ void rope_qkv_append_rows_kernel(float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
+                                            _Float16* __restrict__ kc, _Float16* __restrict__ vc, int rows, int heads, int heads_kv, int head_size,
+                                            const int* __restrict__ pos, int pos_cap, int n_dims, int neox, float theta_scale, float freq_scale,
+                                            float attn_factor, long long c_bs, long long c_sl, long long c_head) {
+  const size_t npairs = neox ? size_t(head_size / n_dims) * (n_dims / 2) : size_t(head_size / 2);
+  const size_t nq = size_t(heads) * npairs, nk = size_t(heads_kv) * npairs, nv = size_t(heads_kv) * head_size;
+  const size_t gid = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (gid >= size_t(rows) * (nq + nk + nv)) return;
+  const size_t r = gid / (nq + nk + nv), it = gid % (nq + nk + nv);
+  const int n_past = pos[r];
+  if (n_past < 0 || n_past >= pos_cap) return;
+  q += r * heads * head_size, k += r * heads_kv * head_size, v += r * heads_kv * head_size;
+  kc += (long long)r * c_bs + (long long)n_past * c_sl, vc += (long long)r * c_bs + (long long)n_past * c_sl;
+  rope_append_row_item(q, k, v, kc, vc, it, nq, nk, npairs, n_past, head_size, n_dims, neox, theta_scale, freq_scale, attn_factor, c_head);
+}
+// ... and over a paged cache (ns_hip_rope_qkv_append_paged): row r's cell is the one its table row names for position pos[r] (attn_page_cell, ns_attn.h).
+// Idle: pos[r] outside [0, min(pos_cap, capacity)), or a table entry that is not a block of the pool — nothing of the row is read or written.
+__global__ void rope_qkv_append_paged_kernel(float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
+                                             _Float16* __restrict__ kc, _Float16* __restrict__ vc, int rows, int heads, int heads_kv, int head_size,
+                                             const int* __restrict__ pos, int pos_cap, int n_dims, int neox, float theta_scale, float freq_scale,
+                                             float attn_factor, AttnPage pg, long long c_sl, long long c_head) {
+  const size_t npairs = neox ? size_t(head_size / n_dims) * (n_dims / 2) : size_t(head_size / 2);
+  const size_t nq = size_t(heads) * npairs, nk = size_t(heads_kv) * npairs, nv = size_t(heads_kv) * head_size;
+  const size_t gid = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (gid >= size_t(rows) * (nq + nk + nv)) return;
+  const size_t r = gid / (nq + nk + nv), it = gid % (nq + nk + nv);
+  const int n_past = pos[r];
+  if (n_past < 0 || n_past >= pos_cap) return;
+  const long long cell = attn_page_cell(pg, int(r), n_past, c_sl);  // (-1 also for a position at or behind the capacity)
+  if (cell < 0) return;
+  q += r * heads * head_size, k += r * heads_kv * head_size, v += r * heads_kv * head_size;
+  rope_append_row_item(q, k, v, kc + cell, vc + cell, it, nq, nk, npairs, n_past, head_size, n_dims, neox, theta_scale, freq_scale, attn_factor, c_head);
+}
+// ns_hip_kv_paged_store: rows [pos0, pos0 + n) of a contiguous slab (what ns_hip_rope_qkv_append and the prefill epilogue write) into one request's
+// pages, K and V in one launch, bit for bit.  One thread per VEC elements of a row (8: 16-byte copies where every stride and pointer allows it).
+// pg.table is the request's table ROW (request 0 of a table of one row).  A row whose table entry is not a block of the pool is skipped.
+template <int VEC>
+__global__ void kv_paged_store_kernel(const _Float16* __restrict__ ks, const _Float16* __restrict__ vs, long long s_sl, long long s_head, int pos0, int n,
+                                      int heads_kv, int head_size, _Float16* __restrict__ kc, _Float16* __restrict__ vc, AttnPage pg, long long c_sl,
+                                      long long c_head) {
+  const size_t per_row = size_t(heads_kv) * (head_size / VEC);
+  const size_t gid = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (gid >= size_t(n) * per_row) return;
+  const int pos = pos0 + int(gid / per_row);
+  const size_t x = gid % per_row;
+  const int ih = int(x / (head_size / VEC)), e = int(x % (head_size / VEC)) * VEC;
+  const long long cell = attn_page_cell(pg, 0, pos, c_sl);
+  if (cell < 0) return;
+  const long long src = (long long)pos * s_sl + (long long)ih * s_head + e, dst = cell + (long long)ih * c_head + e;
+  if constexpr (VEC == 8) {
+    typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
+    *reinterpret_cast<half8_t*>(kc + dst) = *reinterpret_cast<const half8_t*>(ks + src);
+    *reinterpret_cast<half8_t*>(vc + dst) = *reinterpret_cast<const half8_t*>(vs + src);
+  } else {
+    kc[dst] = ks[src];
+    vc[dst] = vs[src];
   }
 }
 // (cos, sin) * attn_factor of the mode-0 pairs of positions n_past .. n_past + m - 1: the angle arithmetic of
@@ -1105,6 +1157,35 @@ hipError_t launch_rope_qkv_append_rows(float* q, const float* k, const float* v,
   hipLaunchKernelGGL(rope_qkv_append_rows_kernel, grid1d(total, 256), dim3(256), 0, st, q, k, v, static_cast<_Float16*>(kc), static_cast<_Float16*>(vc),
                      rows, heads, heads_kv, head_size, pos, pos_cap, n_dims, neox ? 1 : 0, powf(freq_base, -2.0f / n_dims), freq_scale, attn_factor, c_bs,
                      c_sl, c_head);
+  return hipGetLastError();
+}
+
+hipError_t launch_rope_qkv_append_paged(float* q, const float* k, const float* v, void* kc, void* vc, int rows, int heads, int heads_kv, int head_size,
+                                        const int* pos, int pos_cap, int n_dims, int mode, float freq_base, float freq_scale, float attn_factor,
+                                        const AttnPage& pg, long long c_sl, long long c_head, hipStream_t st) {
+  const bool neox = (mode & 2) != 0;
+  const size_t npairs = neox ? size_t(head_size / n_dims) * (n_dims / 2) : size_t(head_size / 2);
+  const size_t total = size_t(rows) * ((heads + heads_kv) * npairs + size_t(heads_kv) * head_size);
+  if (total == 0) return hipSuccess;
+  hipLaunchKernelGGL(rope_qkv_append_paged_kernel, grid1d(total, 256), dim3(256), 0, st, q, k, v, static_cast<_Float16*>(kc), static_cast<_Float16*>(vc),
+                     rows, heads, heads_kv, head_size, pos, pos_cap, n_dims, neox ? 1 : 0, powf(freq_base, -2.0f / n_dims), freq_scale, attn_factor, pg,
+                     c_sl, c_head);
+  return hipGetLastError();
+}
+hipError_t launch_kv_paged_store(const void* ks, const void* vs, long long s_sl, long long s_head, int pos0, int n, int heads_kv, int head_size, void* kc,
+                                 void* vc, const AttnPage& pg, long long c_sl, long long c_head, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  const auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  const bool vec = head_size % 8 == 0 && s_sl % 8 == 0 && s_head % 8 == 0 && c_sl % 8 == 0 && c_head % 8 == 0 && pg.block_step % 8 == 0 && al16(ks) &&
+                   al16(vs) && al16(kc) && al16(vc);
+  const size_t total = size_t(n) * heads_kv * (vec ? head_size / 8 : head_size);
+  if (vec) {
+    hipLaunchKernelGGL(kv_paged_store_kernel<8>, grid1d(total, 256), dim3(256), 0, st, static_cast<const _Float16*>(ks), static_cast<const _Float16*>(vs),
+                       s_sl, s_head, pos0, n, heads_kv, head_size, static_cast<_Float16*>(kc), static_cast<_Float16*>(vc), pg, c_sl, c_head);
+  } else {
+    hipLaunchKernelGGL(kv_paged_store_kernel<1>, grid1d(total, 256), dim3(256), 0, st, static_cast<const _Float16*>(ks), static_cast<const _Float16*>(vs),
+                       s_sl, s_head, pos0, n, heads_kv, head_size, static_cast<_Float16*>(kc), static_cast<_Float16*>(vc), pg, c_sl, c_head);
+  }
   return hipGetLastError();
 }
 
