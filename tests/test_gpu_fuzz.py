@@ -1,8 +1,15 @@
 """Seeded random sweep over shapes, row counts and formats: the forward through the reference entry point against the
 oracle's fp64 GEMM on the same blob.  Exercises every dispatch boundary (M = 1 / 16 / 17 / 32 / 33 / 64 / 65 and beyond:
 weight-streaming kernel variants, tiled GEMM with and without split-K), ragged N and K, all scale types."""
+import importlib.util
+import os
+
 import numpy as np
 import pytest
+
+_spec = importlib.util.spec_from_file_location("gemm_blocks", os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools", "gemm_blocks.py"))
+gb = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(gb)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-3
@@ -55,6 +62,8 @@ def test_random_forward(L, pkg, nso, i, qt, st, asym, core, bs, n, k, m):
     ref = nso.gemm_f64(np.ascontiguousarray(a[:, :k]), blob)
     e = nso.rel_l2(np.ascontiguousarray(out[:, :n]), ref)
     assert e < TOL, (qt, st, asym, bs, n, k, m, e)
+    # row by row and 16-column tile by tile as well (tests/tools/gemm_blocks.py)
+    gb.check_rows_tiles(np.ascontiguousarray(out[:, :n]), ref, TOL, str((qt, st, asym, bs, n, k, m)))
 
 
 INT_FORMATS = [f for f in FORMATS if f[0].startswith("S")]

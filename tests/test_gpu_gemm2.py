@@ -3,9 +3,15 @@ suite reaches it by raising that threshold above the call's rows: device-pointer
 weight, at the bar of tests/test_gpu_gemm3.py::test_gemm3_host_api.  Shapes: one partial row block (33 rows) and two with a partial one
 (150); a partial column block with a partial k-step (144 x 192) and a K split (128 x 1024: two splits of 8 chunks + the reduction pass)."""
 import ctypes as C
+import importlib.util
+import os
 
 import numpy as np
 import pytest
+
+_spec = importlib.util.spec_from_file_location("gemm_blocks", os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools", "gemm_blocks.py"))
+gb = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(gb)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-3  # test_gpu_gemm3.py::test_gemm3_host_api
@@ -56,6 +62,9 @@ def test_gemm2_kernel_device_forward(L, pkg, nso, problems, qt, n, k, m, form):
     err = nso.rel_l2(out, ref)
     print("gemm2_kernel %s %dx%d m=%d %s: rel_l2 %.3g" % (qt, n, k, m, form, err))
     assert err < TOL
+    # rows, 16-column tiles, (tile x 64-row block) and term errors as well (tests/tools/gemm_blocks.py); the fp16-only form against the
+    # references of what the kernel is given, the fp16-rounded activations
+    gb.check_blocks(nso, out, da16.float().cpu().numpy() if form == "f16only" else a, blob, "tiled", what="gemm2_kernel %s %s" % (qt, form))
     if form == "f32":
         assert torch.all(dc16 == -7.0)
     else:

@@ -2,9 +2,15 @@
 8-bit and 4-bit-float weights, every epilogue with and without aligned outputs, the fp16 shadow, the split-K path —
 against the oracle's fp64 GEMM on the same blob."""
 import ctypes as C
+import importlib.util
+import os
 
 import numpy as np
 import pytest
+
+_spec = importlib.util.spec_from_file_location("gemm_blocks", os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools", "gemm_blocks.py"))
+gb = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(gb)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-3
@@ -36,6 +42,8 @@ def test_gemm3_host_api(L, pkg, nso, bm, qt, st, asym, core, bs, n, k, m):
         out = np.zeros((m, n), np.float32)
         L.bestla_f32f32_forward(nso.ptr(a), nso.ptr(blob), nso.ptr(out), m, n, k, k, n, None)
         assert nso.rel_l2(out, ref) < TOL, (qt, bm, nso.rel_l2(out, ref))
+        # rows, 16-column tiles, (tile x 64-row block) and term errors as well (tests/tools/gemm_blocks.py)
+        gb.check_blocks(nso, out, a, blob, "tiled", what="gemm3 host api %s bm=%d" % (qt, bm), f4=qt.startswith("F4"))
     finally:
         L.ns_hip_set_tuning(b"g3_bm", 0)
         L.ns_hip_cache_clear()
@@ -75,6 +83,8 @@ def test_gemm3_epilogues_and_shadow(L, pkg, nso, bm, epi, aligned):
     ref = {"none": g, "add": g + dv, "mul": g * dv, "add_gelu": gelu(g + dv), "gelu": gelu(g), "silu": g / (1 + np.exp(-g))}[epi]
     out = dc.cpu().numpy()
     assert nso.rel_l2(out[:, :n], ref) < 2e-3 if epi == "mul" else nso.rel_l2(out[:, :n], ref) < TOL
+    # the epilogue form of the block checks: every row and every 16-column tile against the fp64 epilogue (tests/tools/gemm_blocks.py)
+    gb.check_rows_tiles(np.ascontiguousarray(out[:, :n]), ref, 2e-3 if epi == "mul" else TOL, "gemm3 epilogue %s bm=%d" % (epi, bm))
     if not aligned:
         assert np.all(out[:, n] == -7.0)  # nothing written past N
     assert np.allclose(dc16.float().cpu().numpy()[:, :n], out[:, :n], rtol=2e-3, atol=2e-3)

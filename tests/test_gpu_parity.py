@@ -8,9 +8,15 @@ the activations: against the oracle fed the same fp16-rounded activations the HI
 (integer weights: only fp32 accumulation order differs) / 6e-4 (f4 weights: LUT values are rounded to fp16).
 """
 import ctypes as C
+import importlib.util
+import os
 
 import numpy as np
 import pytest
+
+_spec = importlib.util.spec_from_file_location("gemm_blocks", os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools", "gemm_blocks.py"))
+gb = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(gb)
 
 pytestmark = pytest.mark.gpu
 
@@ -155,6 +161,9 @@ def _check(nso, out, a, blob, is_f4):
     assert e < TOL, "rel l2 vs fp32-activation oracle %g" % e
     tol16 = TOL_A16_F4 if is_f4 else (TOL_A16_GEMM if out.shape[0] > 64 else TOL_A16_INT)
     assert e16 < tol16, "rel l2 vs fp16-activation oracle %g" % e16
+    # row by row and 16-column tile by tile as well: one wrong row or tile must not hide behind the others (tests/tools/gemm_blocks.py)
+    gb.check_rows_tiles(out, ref, TOL, "fp32-activation oracle")
+    gb.check_rows_tiles(out, ref16, tol16, "fp16-activation oracle")
     return e, e16
 
 

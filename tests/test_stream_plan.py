@@ -2,7 +2,7 @@
 two weight-streaming kernels serves a call, in which decomposition, with which LDS layout, or with which of three refusals.  A host program
 (tests/tools/stream_plan_main.cpp, built with the library's compiler, nothing launched) prints both plans for a grid of calls; the rule they
 must follow — docs/kernels/gemvs.md, gemv.md and the comments of ns_gemvs.h / ns_gemv.h — is written out here independently and compared
-with EVERY line."""
+with EVERY line.  The last part of the grid is the group-size ladder of tests/test_gpu_group_sizes.py at that module's own shapes."""
 import os
 import re
 import shutil
@@ -87,13 +87,17 @@ def up(a, b):
 class Matrix:
     """one weight of the program: an allocation of codes | scales | zero points, [tile][k-step] records of 1024 bytes"""
 
-    def __init__(self, fmt, n, k):
+    def __init__(self, fmt, n, k, grp=0):
         f = FORMATS[0 if fmt >= 5 else fmt]
         self.kind, self.sps, self.sdt, self.asym = f["kind"], f["sps"], f["sdt"], f["asym"]
+        if grp:  # a group of whole k-steps, or one over K (-1): one scale per record, a scale row per group
+            self.sps = 1
         self.n, self.k = n, k
         self.kstep = 64 if self.kind in (INT8, F8) else 128
         self.ks, self.tiles = ceil_div(k, self.kstep), ceil_div(n, 16)
         self.blocksize, self.srows = self.kstep // self.sps, self.ks
+        if grp:
+            self.blocksize, self.srows = (self.ks * self.kstep, 1) if grp < 0 else (grp, ceil_div(k, grp))
         sbytes = self.sps * (4 if self.sdt == F32 else 2)
         self.qstride, self.sstride, self.zstride = 1024, 16 * sbytes, 16 * self.sps if self.asym else 0
         self.soff = self.tiles * self.ks * 1024
@@ -116,7 +120,7 @@ def matrices(i):
     nseg = {0: 1, 1: 2}.get(form, form)
     nq = i["n"] + 16 if i["rope"] and i["rbrk"] == 4 else i["n"]
     nk = nkv if form >= 2 and nkv else i["n"]
-    ms = [Matrix(i["fmt"], 0 if i["spec"] == 4 else nq, i["k"]), Matrix(i["fmt"], nk, i["k"]), Matrix(i["fmt"], nk, i["k"])]
+    ms = [Matrix(i["fmt"], 0 if i["spec"] == 4 else nq, i["k"], i["grp"]), Matrix(i["fmt"], nk, i["k"], i["grp"]), Matrix(i["fmt"], nk, i["k"], i["grp"])]
     if i["fmt"] >= 5:
         for j, w in enumerate(ms):
             w.clone(2 if i["fmt"] == 7 and j == 1 else 3, i["fmt"] == 6)
@@ -489,6 +493,46 @@ def test_the_grid_reaches_every_branch(plans, program):
     assert any(o["nw"] < decode_waves(o["grid"], o["ks"], i["form"] == 1, i["fnw"]) for i, o in gv if i["rope"] != 2)
     assert {o["asrc"] for _, o in gv} == {1, 2, 3, 4} and {o["modex"] & 3 for _, o in gv} == {0, 1, 2, 3}
     assert all(any(o["modex"] & bit for _, o in gv) for bit in (0x100, 0x200, 0x400, 0x800))
+
+
+def test_the_group_size_ladder_is_planned_as_the_gpu_module_says(plans):
+    """the calls of tests/test_gpu_group_sizes.py at its own shapes (263 columns, K = 1920 / 2048 / 1952, groups above one k-step): which of
+    them the two streaming kernels take, and with which words they refuse the others — the refusals that module's docstring lists.  No
+    refusal is about the group size but ONE: gemv_kernel's int8-reference variant takes power-of-two k-blocks only"""
+    lad = [(i, o) for i, o in plans if i["grp"]]
+    assert len(lad) > 5000 and {i["k"] for i, _ in lad} == {1920, 2048, 1952} and {i["grp"] for i, _ in lad} == {64, 128, 192, 256, 320, 384, 512, 640, -1}
+    whole_steps = "activations: aligned fp16 or fp32 rows; several rows need whole k-steps"
+    for i, o in lad:
+        kstep = 64 if i["fmt"] in (2, 4) else 128
+        g, k, m = i["grp"], i["k"], i["m"]
+        ratio = g // kstep
+        regime = "row 0" if g < 0 else "shift" if ratio & (ratio - 1) == 0 else "reciprocal"
+        if o["err"] == "OK":  # the scale-row rule of the regime
+            want = {"row 0": (0, 0), "shift": (1, ratio.bit_length() - 1), "reciprocal": (ceil_div(1 << 20, max(ratio, 1)), 20)}[regime]
+            assert (o["smul"], o["sshift"]) == want and o["srows"] == (1 if g < 0 else ceil_div(k, g)), (i, o)
+        if i["fn"] == "gemvs":  # pinned, 2 .. 16 rows: K in whole k-steps, then EVERY forced slices x waves combination as forced
+            if k % kstep:
+                assert o["err"] == "NOTSUP" and o["why"] == "K: a multiple of 8, and of the k-step for several rows", (i, o)
+            else:
+                assert o["err"] == "OK" and (not i["sl"] or (1 << o["slog"], o["ns"]) == (i["sl"], i["wv"])), (i, o)
+                assert o["tickets"] == int(i["sl"] > 1 and not i["fin"]), (i, o)
+        elif i["i8"]:  # int8-reference variant: power-of-two k-blocks (or one block); 3 rows need whole k-steps like every other call
+            if regime == "reciprocal":
+                assert o["err"] == "NOTSUP" and o["why"] == "int8-reference numerics: integer weights, up to 4 rows, power-of-two k-blocks, aligned codes", (i, o)
+            elif m > 1 and k % kstep:
+                assert o["err"] in ("NOTSUP", "NOTREADY") and (o["err"] == "NOTREADY" or o["why"] == whole_steps), (i, o)
+            else:
+                assert o["err"] in ("OK", "NOTREADY") and (o["err"] == "OK" or not i["i8q"]), (i, o)
+        elif m == 1:
+            assert o["err"] == "OK", (i, o)
+        elif k % kstep:  # several rows over K = 1952 (16 rows: whichever check comes first)
+            assert o["err"] == "NOTSUP" and o["why"] in (whole_steps, "the staged activations exceed 64 KiB") and (m == 16 or o["why"] == whole_steps), (i, o)
+        elif m == 16 and k == 2048:  # 16 x (2048 + 8) x 2 = 65,792 bytes
+            assert o["err"] == "NOTSUP" and o["why"] == "the staged activations exceed 64 KiB", (i, o)
+        elif m == 16 and i["act"] == 0:  # 16 fp32 rows of 1920 columns: 128 one-KiB pieces, the waves hold 64
+            assert o["err"] == "NOTSUP" and o["why"] == "more fp32 activation pieces than the waves hold in registers", (i, o)
+        else:
+            assert o["err"] == "OK", (i, o)
 
 
 def test_the_program_is_clean_under_sanitizers(program):

@@ -23,7 +23,7 @@ static T* at(uintptr_t a) {
 struct Weight {
   ns_weight w, native;
 };
-static void make_weight(int fmt, int n, int k, int i, Weight* out) {
+static void make_weight(int fmt, int n, int k, int i, Weight* out, int grp = 0) {
   ns_weight& w = out->w;
   const int f = fmt >= 5 ? 0 : fmt;
   const int kinds[] = {WK_INT4, WK_INT4, WK_INT8, WK_F4, WK_F8}, spss[] = {4, 1, 2, 2, 2};
@@ -33,6 +33,8 @@ static void make_weight(int fmt, int n, int k, int i, Weight* out) {
   w.kstep_len = kind_is_8bit(w.kind) ? 64 : 128;
   w.ksteps = (k + w.kstep_len - 1) / w.kstep_len, w.ntiles = (n + 15) / 16;
   w.blocksize = w.kstep_len / w.sps, w.srows = w.ksteps;
+  // grp: a group of whole k-steps (grp columns), or one group over K (-1) — one scale per record, a scale row per group (three arrays)
+  if (grp) w.sps = 1, w.blocksize = grp < 0 ? (k + w.kstep_len - 1) / w.kstep_len * w.kstep_len : grp, w.srows = grp < 0 ? 1 : (k + grp - 1) / grp;
   const uint32_t sbytes = w.sps * (w.scale_dt == DT_F32 ? 4 : 2);
   w.qstride = 1024, w.sstride = 16 * sbytes, w.zstride = w.asym ? 16 * w.sps : 0;
   w.codes_bytes = size_t(w.ntiles) * w.ksteps * 1024, w.scales_bytes = size_t(w.ntiles) * w.srows * w.sstride, w.zps_bytes = size_t(w.ntiles) * w.srows * w.zstride;
@@ -83,6 +85,7 @@ struct Case {
   int act = 1;   // 0 fp32 only, 1 fp32 + aligned fp16 shadow, 2 shadow 8 bytes off, 3 shadow with lda % 8 != 0, 4 none, 5 fp32 with lda % 4 != 0,
                  // 6 a leading dimension of 2^24
   int mis = 0;
+  int grp = 0;   // the weights' group in columns where it is above one k-step (-1: per-channel); 0: the format's own
   int spec = 0;  // 1 a scale-row rule that is no multiply-and-shift, 2 a weight of several spans, 3 an allocation of 2 GiB, 4 no columns,
                  // 5 a gate/up pair of three matrices
   int feat = 0;  // gemvs: 1 carried norm, 2 fused RoPE, 3 int8-reference numerics, 4 expert launch (presence only)
@@ -101,9 +104,9 @@ struct Case {
 };
 
 static void print_case(const char* fn, const Case& c) {
-  printf("fn=%s fmt=%d m=%d n=%d k=%d form=%d nkv=%d act=%d mis=%d spec=%d feat=%d link=%d rope=%d hs=%d rbrk=%d i8=%d i8bs=%d nblk=%d i8q=%d i8a=%d moe=%d pairs=%d "
+  printf("fn=%s fmt=%d grp=%d m=%d n=%d k=%d form=%d nkv=%d act=%d mis=%d spec=%d feat=%d link=%d rope=%d hs=%d rbrk=%d i8=%d i8bs=%d nblk=%d i8q=%d i8a=%d moe=%d pairs=%d "
          "nsel=%d mbrk=%d gvs=%d sl=%d wv=%d gr=%d tb=%d fin=%d dma=%d cus=%d gemv2=%d planes=%d fnw=%d i8k=%d | ",
-         fn, c.fmt, c.m, c.n, c.k, c.form, c.nkv, c.act, c.mis, c.spec, c.feat, c.link, c.rope, c.hs, c.rbrk, c.i8, c.i8bs, c.nblk, c.i8q, c.i8a, c.moe, c.pairs,
+         fn, c.fmt, c.grp, c.m, c.n, c.k, c.form, c.nkv, c.act, c.mis, c.spec, c.feat, c.link, c.rope, c.hs, c.rbrk, c.i8, c.i8bs, c.nblk, c.i8q, c.i8a, c.moe, c.pairs,
          c.nsel, c.mbrk, c.gvs, c.sl, c.wv, c.gr, c.tb, c.fin, c.dma, c.cus, c.gemv2, c.planes, c.fnw, c.i8k);
 }
 
@@ -121,9 +124,9 @@ static void make_call(const Case& c, Call* out) {
   Call& x = *out;
   const int nseg = c.form == 0 ? 1 : c.form == 1 ? 2 : c.form;
   const int nq = c.rope && c.rbrk == 4 ? c.n + 16 : c.n, nk = c.form >= 2 && c.nkv ? c.nkv : c.n;
-  make_weight(c.fmt, c.spec == 4 ? 0 : nq, c.k, 0, &x.w[0]);
-  make_weight(c.fmt, nk, c.k, 1, &x.w[1]);
-  make_weight(c.fmt, nk, c.k, 2, &x.w[2]);
+  make_weight(c.fmt, c.spec == 4 ? 0 : nq, c.k, 0, &x.w[0], c.grp);
+  make_weight(c.fmt, nk, c.k, 1, &x.w[1], c.grp);
+  make_weight(c.fmt, nk, c.k, 2, &x.w[2], c.grp);
   mismatch(&x.w[1].w, c.mis);
   if (c.spec == 1)  // one scale row per 1000 k-steps: (s * 1049) >> 20 is s / 1000 up to k-step 2998 only
     for (Weight& w : x.w) w.w.blocksize = 1000 * w.w.kstep_len, w.w.srows = (w.w.ksteps + 999) / 1000;
@@ -479,8 +482,53 @@ static void gemv_grid() {
         }
 }
 
+// the group-size ladder of tests/test_gpu_group_sizes.py at its own shapes (263 columns; K = 1920, 2048, 1952): what each pinned call of that
+// module is planned as.  4-bit records (formats 0, 1, 3): groups 128, 256, 384, 512, 640, per-channel; 8-bit and fp8 records (2, 4): 64, 128, 192,
+// 320, per-channel
+static void ladder_grid() {
+  for (int fmt = 0; fmt < 5; fmt++)
+    for (int gi = 0; gi < 6; gi++) {
+      const bool b8 = fmt == 2 || fmt == 4;
+      const int g4[] = {128, 256, 384, 512, 640, -1}, g8[] = {64, 128, 192, 320, -1, 0};
+      const int grp = b8 ? g8[gi] : g4[gi];
+      if (!grp) continue;
+      for (int k : {1920, 2048, 1952}) {
+        Case b;
+        b.fmt = fmt, b.grp = grp, b.n = 263, b.k = k;
+        // gemv_kernel: rows x shadow / fp32 only x forced waves; the fused launches; the int8-reference variant (k-block = the group)
+        for (int m : {1, 4, 8, 16})
+          for (int act : {0, 1})
+            for (int fnw : {0, 2, 16})
+              for (int form : {0, 1, 3}) {
+                if ((fnw && (m != 1 || form)) || (form && m != 1 && m != 8)) continue;
+                Case c = b;
+                c.m = m, c.act = act, c.fnw = fnw, c.form = form;
+                run_gemv(c);
+              }
+        for (int m : {1, 3})
+          for (int i8q : {0, 1}) {
+            if (fmt >= 3) continue;
+            Case c = b;
+            c.m = m, c.act = 0, c.i8 = 1, c.i8bs = grp < 0 ? k : grp, c.i8q = i8q;
+            run_gemv(c);
+          }
+        // gemvs_kernel pinned ("gvs" 3): rows x forced slices x forced streaming waves, finished in the launch and by the finalize launch
+        for (int m : {2, 8, 16})
+          for (int sl : {0, 1, 2, 4, 8})
+            for (int wv : {0, 3, 7})
+              for (int fin : {0, 1}) {
+                if ((sl == 0) != (wv == 0) || (sl == 0 && m != 8)) continue;
+                Case c = b;
+                c.m = m, c.gvs = 3, c.sl = sl, c.wv = wv, c.fin = fin;
+                run_gemvs(c);
+              }
+      }
+    }
+}
+
 int main() {
   gemvs_grid();
   gemv_grid();
+  ladder_grid();
   return 0;
 }
