@@ -703,6 +703,17 @@ int ns_hip_rope_qkv_append_paged(float* dQ, const float* dK, const float* dV, vo
                                  int head_size, const int* dPos, int pos_cap, int n_dims, int mode, float freq_base, float freq_scale, float ext_factor,
                                  float attn_factor, const int* dBlockTable, int table_stride, int block_keys, int pool_blocks, long long block_step,
                                  long long cache_step_sl, long long cache_step_head, void* stream);
+/* ns_hip_rope_qkv_append_paged_seq: ns_hip_rope_qkv_append_paged with a row -> request map, so that one request may bring several rows (a prompt chunk,
+ * drafted tokens) beside requests that bring one.  dRowReq is a DEVICE array of `rows` ints, read inside the launch: row r belongs to request dRowReq[r]
+ * and is written through that request's table row at position dPos[r].  Idle (nothing read or written, Q untouched): what the paged append skips, and
+ * a dRowReq[r] outside [0, requests), `requests` being the table's rows.  Same arithmetic: a row holds the bits ns_hip_rope_qkv_append_paged gives it
+ * when row r's table row is a copy of request dRowReq[r]'s.  Two rows of one call naming the same (request, position): unspecified.  One launch,
+ * capturable; refusals as the paged append's, and a null dRowReq. */
+int ns_hip_rope_qkv_append_paged_seq(float* dQ, const float* dK, const float* dV, void* dKpool16, void* dVpool16, int rows, int heads, int heads_kv,
+                                     int head_size, const int* dPos, int pos_cap, int n_dims, int mode, float freq_base, float freq_scale,
+                                     float ext_factor, float attn_factor, const int* dRowReq, int requests, const int* dBlockTable, int table_stride,
+                                     int block_keys, int pool_blocks, long long block_step, long long cache_step_sl, long long cache_step_head,
+                                     void* stream);
 /* ns_hip_attn_decode_paged: ns_hip_attn_decode_rows (same argument block, dKvLens, kv_len_bias, dst16) over the pools.  K / V of the block are the pool
  * bases, step_k_sl / step_k_head_num (and V's) the strides inside a block, sl_kv the capacity of a request, which must equal table_stride * block_keys;
  * step_k_bs / step_v_bs are not used.  Flags, scales, GQA, the head partition, tmp, zero rows for len_b = 0 and the refusals are those of the rows
@@ -724,6 +735,30 @@ int ns_hip_kv_paged_store(const void* dKslab16, const void* dVslab16, long long 
 /* Process-wide counts of ns_hip_attn_decode_paged, the four slots of ns_hip_attn_rows_stats: [0] launches on the LDS-ring kernel, [1] on the register
  * kernel, [2] merge launches, [3] refused calls. */
 void ns_hip_attn_paged_stats(unsigned long long out[4]);
+/* ns_hip_attn_block_paged: RAGGED QUERY BLOCKS over the pools — every request brings its own number of query rows (a prompt chunk beside running
+ * decodes, drafted tokens to verify, a follow-up turn), K / V of a kv head are read once per 64 (row, query head) slots and context range, not once per
+ * row.  The argument block is ns_hip_attn_decode_paged's, read as: batch_size = the requests, sl_kv = a request's capacity (= table_stride *
+ * block_keys), sl_q = max_q >= 1, the host's upper bound on the query rows of any one request in this call.  Q, dst and dst16 are PACKED: query row i
+ * of request b is row dQStart[b] + i, at row * step_q_sl + head * step_q_head_num (dst: its steps); step_q_bs / step_dst_bs are not used.  dQStart is a
+ * DEVICE array of batch_size + 1 ints, dKvLens one of batch_size ints, both read inside the launch:
+ *   q_len_b = clamp(dQStart[b + 1] - dQStart[b], 0, max_q),  kv_len_b = clamp(dKvLens[b] + kv_len_bias, 0, sl_kv) — the chunk's own keys included,
+ *   which the append has written.  Causal: row i sees keys [0, kv_len_b - q_len_b + i + 1); otherwise [0, kv_len_b).
+ * A row that sees no key is written as zeros; a request with q_len_b = 0 writes nothing; rows of dst no request names are not touched.  QK_scale,
+ * Q_sc .. dst_sc, GQA and dst16 as in the uniform entry.  Table entries as in ns_hip_attn_decode_paged: an id outside [0, pool_blocks) never becomes an
+ * address (that request's rows are unspecified, every other request's unchanged); entries at or behind ceil(kv_len_b / block_keys) may hold anything,
+ * and no byte behind kv_len_b reaches a result.
+ * Plan: grid and partials laid out for (max_q, capacity); every workgroup applies the range rule to its own request's live length
+ * (NS_ATTN_DYN_RANGES=0: ranges as laid out).  Two launches (ranges, merge), capturable.  Workspace: `tmp`, when given, is DEVICE memory of
+ * ns_hip_attn_block_paged_workspace_size(..) bytes; otherwise the stream's scratch, which a first use on a capturing stream cannot allocate.
+ * Refused (-1, ns_hip_last_error set, nothing written): what ns_hip_attn_decode_paged refuses of the cache's description, a null dQStart or dKvLens, a
+ * head size other than 64 / 128, ALiBi or the tanh cap, max_q < 1, heads_kv * ceil(max_q * (head_num / heads_kv) / 64) > 65535. */
+int ns_hip_attn_block_paged(const attn_fp32_fp16_fp16_fp32_fwd_args_t* dparams, const int* dQStart, const int* dKvLens, int kv_len_bias,
+                            const int* dBlockTable, int table_stride, int block_keys, int pool_blocks, long long block_step, void* dst16, void* stream);
+/* bytes of its partials (no device needed; 0: a shape the entry refuses) */
+size_t ns_hip_attn_block_paged_workspace_size(int batch, int head_num, int heads_kv, int head_size, int max_q, int capacity);
+/* Process-wide counts of ns_hip_attn_block_paged: [0] launches of the head-size-64 kernel, [1] of the head-size-128 kernel, [2] merge launches,
+ * [3] refused calls. */
+void ns_hip_attn_block_paged_stats(unsigned long long out[4]);
 
 /* ----------------------------------------------------------------------------------------------
  * Part 4b — mixture-of-experts matmul with the routing on the device.  Device twin of

@@ -271,6 +271,13 @@ def lib():
         L.ns_hip_kv_paged_store.argtypes = [vp, vp, C.c_longlong, C.c_longlong, i, i, i, i, vp, vp, vp, i, i, i, C.c_longlong, C.c_longlong, C.c_longlong, vp]
         L.ns_hip_attn_paged_stats.restype = None
         L.ns_hip_attn_paged_stats.argtypes = [vp]
+        L.ns_hip_rope_qkv_append_paged_seq.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, vp, i, i, i, f, f, f, f, vp, i, vp, i, i, i, C.c_longlong,
+                                                       C.c_longlong, C.c_longlong, vp]
+        L.ns_hip_attn_block_paged.argtypes = [vp, vp, vp, i, vp, i, i, i, C.c_longlong, vp, vp]
+        L.ns_hip_attn_block_paged_workspace_size.restype = sz
+        L.ns_hip_attn_block_paged_workspace_size.argtypes = [i, i, i, i, i, i]
+        L.ns_hip_attn_block_paged_stats.restype = None
+        L.ns_hip_attn_block_paged_stats.argtypes = [vp]
         L.ns_hip_blob_validate.argtypes = [vp, sz]
         L.ns_BTLAGemmPackBSize.restype = sz
         L.ns_BTLAGemmPackBSize.argtypes = [sz, sz, sz, u32, u32, b, i, vp]

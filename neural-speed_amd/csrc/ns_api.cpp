@@ -426,6 +426,30 @@ int ns_hip_rope_qkv_append_paged(float* dQ, const float* dK, const float* dV, vo
                                              freq_scale, attn_factor, pg, cache_step_sl, cache_step_head, (hipStream_t)stream),
                 "rope/kv-append (paged) launch") ? 0 : -1;
 }
+int ns_hip_rope_qkv_append_paged_seq(float* dQ, const float* dK, const float* dV, void* dKpool16, void* dVpool16, int rows, int heads, int heads_kv,
+                                     int head_size, const int* dPos, int pos_cap, int n_dims, int mode, float freq_base, float freq_scale,
+                                     float ext_factor, float attn_factor, const int* dRowReq, int requests, const int* dBlockTable, int table_stride,
+                                     int block_keys, int pool_blocks, long long block_step, long long cache_step_sl, long long cache_step_head,
+                                     void* stream) {
+  if (!have_device()) return -1;
+  if (!dQ || !dK || !dV || !dKpool16 || !dVpool16 || !dPos || !dRowReq || requests < 0 || rows < 0 || heads <= 0 || heads_kv <= 0 || head_size <= 0 ||
+      (head_size & 1) || n_dims <= 0 || (n_dims & 1) || n_dims > head_size || pos_cap < 0) {
+    set_error("rope_qkv_append_paged_seq: invalid argument");
+    return -1;
+  }
+  if ((mode & ~2) != 0 || ext_factor != 0.f || ((mode & 2) && head_size % n_dims != 0)) {
+    set_error("rope_qkv_append_paged_seq: only modes 0 and 2 (NeoX, head_size a multiple of n_dims) without YaRN extrapolation");
+    return -1;
+  }
+  const AttnPage pg = {dBlockTable, table_stride, attn_block_shift(block_keys), pool_blocks, block_step};
+  if (const char* text = paged_cache_refusal(pg, heads_kv, head_size, cache_step_sl, cache_step_head)) {
+    set_error(std::string("rope_qkv_append_paged_seq: ") + text);
+    return -1;
+  }
+  return hip_ok(launch_rope_qkv_append_paged_seq(dQ, dK, dV, dKpool16, dVpool16, rows, heads, heads_kv, head_size, dPos, pos_cap, dRowReq, requests, n_dims,
+                                                 mode, freq_base, freq_scale, attn_factor, pg, cache_step_sl, cache_step_head, (hipStream_t)stream),
+                "rope/kv-append (paged, row -> request map) launch") ? 0 : -1;
+}
 int ns_hip_kv_paged_store(const void* dKslab16, const void* dVslab16, long long slab_step_sl, long long slab_step_head, int pos0, int n, int heads_kv,
                           int head_size, void* dKpool16, void* dVpool16, const int* dTableRow, int table_len, int block_keys, int pool_blocks,
                           long long block_step, long long cache_step_sl, long long cache_step_head, void* stream) {

@@ -182,6 +182,28 @@ static hipError_t launch_attn_decode_paged(const attn_fp32_fp16_fp16_fp32_fwd_ar
   return e;
 }
 
+// ns_hip_attn_block_paged: plan (attn_block_paged_plan), partials in the caller's `tmp` (ns_hip_attn_block_paged_workspace_size bytes) or the stream's
+// scratch, the PAGED instantiation of the block-split kernel and its merge.
+static std::atomic<uint64_t> g_attn_block_paged[4];  // ns_hip_attn_block_paged_stats
+static hipError_t launch_attn_block_paged_call(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const int* q_start, const int* lens, int bias,
+                                               const AttnPage& page, hipStream_t st, std::string* why, void* dst16) {
+  const AttnBlockPagedPlan pl = attn_block_paged_plan(a, dst16, attn_knobs(), page, q_start, lens, bias, why);
+  if (!pl.ok) return hipErrorInvalidValue;
+  float* ws = reinterpret_cast<float*>(a.tmp);
+  if (!ws) ws = static_cast<float*>(stream_scratch(st, pl.partial_bytes, SLOT_ATTN_PARTIALS));
+  if (!ws) {
+    *why = "attention, query blocks over a paged cache: no memory for the partials (give tmp, or make one eager call before a capture)";
+    return hipErrorOutOfMemory;
+  }
+  const hipError_t e = launch_attn_block_paged(pl, ws, st);
+  if (e == hipSuccess) {
+    g_attn_launches[AP_BLOCK_SPLIT].fetch_add(1, std::memory_order_relaxed);
+    g_attn_block_paged[pl.hs_pad == 64 ? 0 : 1].fetch_add(1, std::memory_order_relaxed);
+    g_attn_block_paged[2].fetch_add(1, std::memory_order_relaxed);
+  }
+  return e;
+}
+
 // scratch a moving-length decode launch needs (partials for the longest context, the merge tickets): allocated BEFORE the route's capture
 bool attn_prepare_moving(hipStream_t st, int batch, int heads, int heads_kv, int head_size, int cap) {
   const size_t b = attn_ws_bytes(attn_knobs(), batch, heads, heads_kv, head_size, 1, cap);
@@ -276,6 +298,28 @@ int ns_hip_attn_decode_paged(const attn_fp32_fp16_fp16_fp32_fwd_args_t* a, const
     return -1;
   }
   return 0;
+}
+
+int ns_hip_attn_block_paged(const attn_fp32_fp16_fp16_fp32_fwd_args_t* a, const int* dQStart, const int* dKvLens, int kv_len_bias, const int* dBlockTable,
+                            int table_stride, int block_keys, int pool_blocks, long long block_step, void* dst16, void* stream) {
+  std::string why;
+  const AttnPage page = {dBlockTable, table_stride, attn_block_shift(block_keys), pool_blocks, block_step};
+  const hipError_t e =
+      a ? launch_attn_block_paged_call(*a, dQStart, dKvLens, kv_len_bias, page, static_cast<hipStream_t>(stream), &why, dst16) : hipErrorInvalidValue;
+  if (e != hipSuccess) {
+    g_attn_block_paged[3].fetch_add(1, std::memory_order_relaxed);
+    set_error(why.empty() ? std::string("attention launch (query blocks over a paged cache): ") + (a ? hipGetErrorString(e) : "null arguments") : why);
+    return -1;
+  }
+  return 0;
+}
+
+size_t ns_hip_attn_block_paged_workspace_size(int batch, int head_num, int heads_kv, int head_size, int max_q, int capacity) {
+  return attn_block_paged_ws_bytes(attn_knobs(), batch, head_num, heads_kv, head_size, max_q, capacity);
+}
+
+void ns_hip_attn_block_paged_stats(unsigned long long out[4]) {
+  for (int i = 0; i < 4; i++) out[i] = g_attn_block_paged[i].load(std::memory_order_relaxed);
 }
 
 void ns_hip_attn_paged_stats(unsigned long long out[4]) {

@@ -136,6 +136,35 @@ __host__ __device__ __forceinline__ bool attn_page_in32(const AttnPage& pg) {
   return ((unsigned long long)pg.pool_blocks * (unsigned long long)pg.block_step + 256ull) * 2ull < (1ull << 32);
 }
 
+// ---- ragged query blocks over a paged cache (ns_hip_attn_block_paged; attn_block_split_kernel's PAGED instantiations, ns_attn_block.hip) ---------
+// Argument block: sp as the block-split kernel reads it, with a.sl_q = max_q (the most query rows of one request), a.sl_kv = a request's capacity,
+// kmove / kdelta = dKvLens / its bias (attn_live_kv<true>), nsplit / keys_per_split = the ranges laid out for the capacity, dyn_min_keys = the block
+// rule's least keys per range for the workgroups to apply to the live length (0: ranges as laid out).  q_start[requests + 1]: request b's query rows
+// are the packed rows q_start[b] .. q_start[b + 1] - 1 of Q / dst.  Partials: ws[request][row of the request < max_q][head][nsplit][2 + head_size].
+struct AttnBlockPagedParams {
+  AttnSplitParams sp;
+  AttnPage pg;
+  const int* q_start;
+};
+// Keys per range and live ranges of a request with kv_len live keys, under a layout of nsplit ranges of kps_laid keys (a multiple of 64).  THE live
+// rule of that entry: the range workgroups and the merge both go through it, tests/test_attn_block_paged_plan.py walks every live length through it.
+// The ranges [i * kps, min((i + 1) * kps, kv_len)), i < live, tile [0, kv_len); kps is a multiple of 64 and live <= nsplit.
+struct AttnBlockLive {
+  int kps, live;
+};
+__host__ __device__ __forceinline__ AttnBlockLive attn_block_live(int kv_len, int nsplit, int kps_laid, int min_keys) {
+  if (kv_len <= 0) return {kps_laid, 0};
+  if (min_keys <= 0) return {kps_laid, (kv_len + kps_laid - 1) / kps_laid};
+  const int want = min(nsplit, max(1, (kv_len + min_keys - 1) / min_keys));
+  const int kps = ((kv_len + want - 1) / want + 63) / 64 * 64;
+  return {kps, (kv_len + kps - 1) / kps};
+}
+// query rows of request b in this call: clamp(q_start[b + 1] - q_start[b], 0, max_q)
+__host__ __device__ __forceinline__ int attn_block_q_len(const int* q_start, int b, int max_q) {
+  const long long n = (long long)q_start[b + 1] - q_start[b];
+  return n < 0 ? 0 : (n > max_q ? max_q : int(n));
+}
+
 // ---- the launch decision as a value (ns_attn_plan.cpp) -------------------------------------------------------------------------------------
 // Every tunable the decision reads.  attn_knobs() (ns_attn.cpp) fills it from ns_hip_set_tuning's atomics and the environment.
 struct AttnKnobs {
@@ -185,10 +214,26 @@ AttnPlan attn_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst
 // what bestla_fusion_attn_workspace_size answers: it knows neither strides nor alignment, so the most any plan of the shape can need
 size_t attn_ws_bytes(const AttnKnobs& knobs, int batch, int head_num, int heads_kv, int head_size, int sl_q, int sl_kv);
 
+// The plan of ns_hip_attn_block_paged: a pure function like attn_plan (tests/test_attn_block_paged_plan.py).  a.sl_q is max_q, a.sl_kv the capacity.
+// Ranges: the block rule of AP_BLOCK_SPLIT (kn.block_target / kn.block_min_keys) for the capacity and max_q rows of every request; kn.dyn_ranges:
+// the workgroups apply it to their request's live length.  !ok: *why says what is wrong with the call.  pp.sp.ws is null: the launcher's scratch.
+struct AttnBlockPagedPlan {
+  bool ok = false;
+  int hs_pad = 0;
+  AttnBlockPagedParams pp;
+  dim3 grid, block, merge_grid;  // (slot blocks of max_q rows * kv heads, nsplit, requests) x 256; (heads, max_q, requests) x 128
+  size_t partial_bytes = 0;
+};
+AttnBlockPagedPlan attn_block_paged_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst16, const AttnKnobs& knobs, const AttnPage& page,
+                                         const int* q_start, const int* kv_lens, int kv_len_bias, std::string* why);
+// what ns_hip_attn_block_paged_workspace_size answers: the plan's partial_bytes, from the shape alone (0: no plan of that shape)
+size_t attn_block_paged_ws_bytes(const AttnKnobs& knobs, int batch, int head_num, int heads_kv, int head_size, int max_q, int capacity);
+
 // ---- launches of a plan ----------------------------------------------------------------------------------------------------------------------
 hipError_t launch_attn_onerow(const AttnPlan& pl, float* ws, uint32_t* tickets, hipStream_t st);  // ns_attn_decode.hip: AP_GENERIC, AP_SPLIT_REGS, AP_RING (+ merge)
 hipError_t launch_attn_rows(const AttnPlan& pl, hipStream_t st);                                  // ns_attn_prefill.hip: AP_ROWS64, AP_ROWS128, AP_PIPELINED
 hipError_t launch_attn_block_split(const AttnPlan& pl, float* ws, hipStream_t st);                // ns_attn_block.hip: AP_BLOCK_SPLIT (+ merge)
+hipError_t launch_attn_block_paged(const AttnBlockPagedPlan& pl, float* ws, hipStream_t st);     // ns_attn_block.hip: the PAGED instantiation + its merge
 hipError_t launch_attn_merge(const AttnSplitParams& sp, unsigned batch, hipStream_t st, bool rows = false);  // ns_attn_decode.hip: attn_merge_kernel over sp.ws
 // touch_attn_module (ns_common.h) makes the runtime load all four code objects
 inline void touch_kernel(const void* kernel) {

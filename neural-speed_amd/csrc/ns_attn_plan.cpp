@@ -281,4 +281,88 @@ AttnPlan attn_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst
   return pl;
 }
 
+// ---- ragged query blocks over a paged cache (ns_hip_attn_block_paged) ------------------------------------------------------------------------------
+// The ranges of the 64-slot kernel for `requests` requests of up to max_q rows over `cap` keys: AP_BLOCK_SPLIT's rule above (two workgroups per CU,
+// kn.block_min_keys keys or more per range, whole 64-key blocks, no range that starts at or past cap), without its "two ranges or more" condition —
+// this entry has no other kernel to give a call to, one range is a plan like any other.
+static void block_paged_ranges(const AttnKnobs& kn, int requests, int heads_kv, int g_full, int max_q, int cap, size_t* slot_blocks, int* nsplit, int* kps) {
+  *slot_blocks = (size_t(max_q) * g_full + 63) / 64;
+  const size_t base = size_t(heads_kv) * *slot_blocks * requests;
+  int ns = int((size_t(std::max(1, kn.block_target)) + base - 1) / base);
+  const int min_keys = std::max(1, kn.block_min_keys);
+  ns = std::min(std::min(ns, std::max(1, (cap + min_keys - 1) / min_keys)), 64);
+  *kps = ((cap + ns - 1) / ns + 63) / 64 * 64;
+  *nsplit = (cap + *kps - 1) / *kps;
+}
+// what the shape alone can say against a call (the workspace size function knows nothing else)
+static const char* block_paged_shape_refusal(int requests, int head_num, int heads_kv, int head_size, int max_q, int cap) {
+  if (requests < 1 || requests > 65535) return "attention, query blocks over a paged cache: batch_size (the requests) must be 1 .. 65535";
+  if (head_size != 64 && head_size != 128) return "attention, query blocks over a paged cache: head_size must be 64 or 128";
+  if (heads_kv < 1 || head_num < 1 || head_num % heads_kv != 0 || head_num > 65535)
+    return "attention, query blocks over a paged cache: head_num must be a multiple of heads_kv (at most 65535)";
+  if (max_q < 1 || max_q > 65535) return "attention, query blocks over a paged cache: sl_q is max_q, the most query rows of one request (1 .. 65535)";
+  if (cap < 1) return "attention, query blocks over a paged cache: sl_kv is the capacity of a request (at least 1 key)";
+  if (size_t(heads_kv) * ((size_t(max_q) * (head_num / heads_kv) + 63) / 64) > 65535)
+    return "attention, query blocks over a paged cache: heads_kv * ceil(max_q * (head_num / heads_kv) / 64) above the grid limit of 65535";
+  return nullptr;
+}
+size_t attn_block_paged_ws_bytes(const AttnKnobs& kn, int batch, int head_num, int heads_kv, int head_size, int max_q, int capacity) {
+  if (block_paged_shape_refusal(batch, head_num, heads_kv, head_size, max_q, capacity)) return 0;
+  size_t slot_blocks;
+  int nsplit, kps;
+  block_paged_ranges(kn, batch, heads_kv, head_num / heads_kv, max_q, capacity, &slot_blocks, &nsplit, &kps);
+  return size_t(batch) * max_q * head_num * nsplit * (2 + head_size) * 4;
+}
+AttnBlockPagedPlan attn_block_paged_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst16, const AttnKnobs& kn, const AttnPage& page,
+                                         const int* q_start, const int* kv_lens, int kv_len_bias, std::string* why) {
+  AttnBlockPagedPlan pl;
+  memset(&pl.pp, 0, sizeof(pl.pp));
+  auto refuse = [&](const char* text) {
+    *why = text;
+    return pl;
+  };
+  if (a.Q_layout != ATTN_FWD_LAYOUT_PLAIN || a.K_layout != ATTN_FWD_LAYOUT_PLAIN || a.V_layout != ATTN_FWD_LAYOUT_PLAIN ||
+      a.dst_layout != ATTN_FWD_LAYOUT_PLAIN)
+    return refuse("attention: only ATTN_FWD_LAYOUT_PLAIN tensors are supported");
+  if (!q_start) return refuse("attention, query blocks over a paged cache: dQStart is null");
+  if (!kv_lens) return refuse("attention, query blocks over a paged cache: dKvLens is null");
+  if (const char* text = block_paged_shape_refusal(a.batch_size, a.head_num, a.heads_kv, a.head_size, a.sl_q, a.sl_kv)) return refuse(text);
+  if (a.attn_flags & (NS_ATTN_FLAG_IS_ALIBI8 | NS_ATTN_FLAG_IS_TANH30))
+    return refuse("attention, query blocks over a paged cache: ALiBi and the tanh cap are not served");
+  if (const char* text = attn_page_refusal(a, page)) return refuse(text);
+  // what the kernel asks of K and V, as every split kernel does: a contiguous head dimension and 16-byte aligned rows
+  if (a.step_k_head_size != 1 || a.step_v_head_size != 1 || a.step_k_sl % 8 != 0 || a.step_v_sl % 8 != 0 || a.step_k_head_num % 8 != 0 ||
+      a.step_v_head_num % 8 != 0 || (reinterpret_cast<uintptr_t>(a.K) & 15) != 0 || (reinterpret_cast<uintptr_t>(a.V) & 15) != 0)
+    return refuse("attention, query blocks over a paged cache: K / V rows must be contiguous in the head dimension and 16-byte aligned");
+  AttnSplitParams& sp = pl.pp.sp;
+  AttnParams& p = sp.a;
+  p.q = a.Q;
+  p.k = reinterpret_cast<const _Float16*>(a.K);
+  p.v = reinterpret_cast<const _Float16*>(a.V);
+  p.dst = a.dst;
+  p.dst16 = static_cast<_Float16*>(const_cast<void*>(dst16));
+  p.qk_scale = a.QK_scale * a.Q_sc * a.K_sc;
+  p.out_scale = a.V_sc / a.dst_sc;
+  p.flags = a.attn_flags;
+  p.head_num = a.head_num, p.heads_kv = a.heads_kv, p.head_size = a.head_size, p.sl_q = a.sl_q, p.sl_kv = a.sl_kv;
+  p.step_q_head_num = a.step_q_head_num, p.step_q_sl = a.step_q_sl;  // (packed rows: no batch step of Q or dst)
+  p.step_k_head_num = a.step_k_head_num, p.step_k_sl = a.step_k_sl, p.step_k_head_size = 1;
+  p.step_v_head_num = a.step_v_head_num, p.step_v_sl = a.step_v_sl, p.step_v_head_size = 1;
+  p.step_dst_head_num = a.step_dst_head_num, p.step_dst_sl = a.step_dst_sl;
+  p.hs_pad = a.head_size;
+  size_t slot_blocks;
+  block_paged_ranges(kn, a.batch_size, a.heads_kv, a.head_num / a.heads_kv, a.sl_q, a.sl_kv, &slot_blocks, &sp.nsplit, &sp.keys_per_split);
+  sp.g_full = a.head_num / a.heads_kv;
+  sp.kmove = kv_lens, sp.kdelta = kv_len_bias;
+  sp.dyn_min_keys = kn.dyn_ranges ? std::max(1, kn.block_min_keys) : 0;
+  pl.pp.pg = page, pl.pp.q_start = q_start;
+  pl.hs_pad = p.hs_pad;
+  pl.grid = dim3(unsigned(slot_blocks * a.heads_kv), unsigned(sp.nsplit), unsigned(a.batch_size));
+  pl.block = dim3(256);
+  pl.merge_grid = dim3(unsigned(a.head_num), unsigned(a.sl_q), unsigned(a.batch_size));
+  pl.partial_bytes = size_t(a.batch_size) * a.sl_q * a.head_num * sp.nsplit * (2 + a.head_size) * 4;
+  pl.ok = true;
+  return pl;
+}
+
 }  // namespace ns

@@ -456,6 +456,9 @@ struct AttnPage;
 hipError_t launch_rope_qkv_append_paged(float* q, const float* k, const float* v, void* kc, void* vc, int rows, int heads, int heads_kv, int head_size,
                                         const int* pos, int pos_cap, int n_dims, int mode, float freq_base, float freq_scale, float attn_factor,
                                         const AttnPage& pg, long long c_sl, long long c_head, hipStream_t st);
+hipError_t launch_rope_qkv_append_paged_seq(float* q, const float* k, const float* v, void* kc, void* vc, int rows, int heads, int heads_kv, int head_size,
+                                            const int* pos, int pos_cap, const int* row_req, int requests, int n_dims, int mode, float freq_base,
+                                            float freq_scale, float attn_factor, const AttnPage& pg, long long c_sl, long long c_head, hipStream_t st);
 hipError_t launch_kv_paged_store(const void* ks, const void* vs, long long s_sl, long long s_head, int pos0, int n, int heads_kv, int head_size, void* kc,
                                  void* vc, const AttnPage& pg, long long c_sl, long long c_head, hipStream_t st);
 hipError_t launch_aquant_u8(int row, int col, const float* src, int ld_src, uint8_t* dst, int ld_dst, float* scales,

@@ -978,6 +978,25 @@ __global__ void rope_qkv_append_paged_kernel(float* __restrict__ q, const float*
   q += r * heads * head_size, k += r * heads_kv * head_size, v += r * heads_kv * head_size;
   rope_append_row_item(q, k, v, kc + cell, vc + cell, it, nq, nk, npairs, n_past, head_size, n_dims, neox, theta_scale, freq_scale, attn_factor, c_head);
 }
+// ... with a row -> request map (ns_hip_rope_qkv_append_paged_seq): row r is a row of request row_req[r] and goes through THAT request's table row, so
+// one request may bring several rows (a prompt chunk, drafted tokens).  Idle as well: a request id outside [0, requests).
+__global__ void rope_qkv_append_paged_seq_kernel(float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
+                                                 _Float16* __restrict__ kc, _Float16* __restrict__ vc, int rows, int heads, int heads_kv, int head_size,
+                                                 const int* __restrict__ pos, int pos_cap, const int* __restrict__ row_req, int requests, int n_dims,
+                                                 int neox, float theta_scale, float freq_scale, float attn_factor, AttnPage pg, long long c_sl,
+                                                 long long c_head) {
+  const size_t npairs = neox ? size_t(head_size / n_dims) * (n_dims / 2) : size_t(head_size / 2);
+  const size_t nq = size_t(heads) * npairs, nk = size_t(heads_kv) * npairs, nv = size_t(heads_kv) * head_size;
+  const size_t gid = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (gid >= size_t(rows) * (nq + nk + nv)) return;
+  const size_t r = gid / (nq + nk + nv), it = gid % (nq + nk + nv);
+  const int n_past = pos[r], b = row_req[r];
+  if (n_past < 0 || n_past >= pos_cap || unsigned(b) >= unsigned(requests)) return;
+  const long long cell = attn_page_cell(pg, b, n_past, c_sl);
+  if (cell < 0) return;
+  q += r * heads * head_size, k += r * heads_kv * head_size, v += r * heads_kv * head_size;
+  rope_append_row_item(q, k, v, kc + cell, vc + cell, it, nq, nk, npairs, n_past, head_size, n_dims, neox, theta_scale, freq_scale, attn_factor, c_head);
+}
 // ns_hip_kv_paged_store: rows [pos0, pos0 + n) of a contiguous slab (what ns_hip_rope_qkv_append and the prefill epilogue write) into one request's
 // pages, K and V in one launch, bit for bit.  One thread per VEC elements of a row (8: 16-byte copies where every stride and pointer allows it).
 // pg.table is the request's table ROW (request 0 of a table of one row).  A row whose table entry is not a block of the pool is skipped.
@@ -1170,6 +1189,18 @@ hipError_t launch_rope_qkv_append_paged(float* q, const float* k, const float* v
   hipLaunchKernelGGL(rope_qkv_append_paged_kernel, grid1d(total, 256), dim3(256), 0, st, q, k, v, static_cast<_Float16*>(kc), static_cast<_Float16*>(vc),
                      rows, heads, heads_kv, head_size, pos, pos_cap, n_dims, neox ? 1 : 0, powf(freq_base, -2.0f / n_dims), freq_scale, attn_factor, pg,
                      c_sl, c_head);
+  return hipGetLastError();
+}
+hipError_t launch_rope_qkv_append_paged_seq(float* q, const float* k, const float* v, void* kc, void* vc, int rows, int heads, int heads_kv, int head_size,
+                                            const int* pos, int pos_cap, const int* row_req, int requests, int n_dims, int mode, float freq_base,
+                                            float freq_scale, float attn_factor, const AttnPage& pg, long long c_sl, long long c_head, hipStream_t st) {
+  const bool neox = (mode & 2) != 0;
+  const size_t npairs = neox ? size_t(head_size / n_dims) * (n_dims / 2) : size_t(head_size / 2);
+  const size_t total = size_t(rows) * ((heads + heads_kv) * npairs + size_t(heads_kv) * head_size);
+  if (total == 0) return hipSuccess;
+  hipLaunchKernelGGL(rope_qkv_append_paged_seq_kernel, grid1d(total, 256), dim3(256), 0, st, q, k, v, static_cast<_Float16*>(kc),
+                     static_cast<_Float16*>(vc), rows, heads, heads_kv, head_size, pos, pos_cap, row_req, requests, n_dims, neox ? 1 : 0,
+                     powf(freq_base, -2.0f / n_dims), freq_scale, attn_factor, pg, c_sl, c_head);
   return hipGetLastError();
 }
 hipError_t launch_kv_paged_store(const void* ks, const void* vs, long long s_sl, long long s_head, int pos0, int n, int heads_kv, int head_size, void* kc,
