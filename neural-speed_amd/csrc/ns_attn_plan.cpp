@@ -219,7 +219,9 @@ AttnPlan attn_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst
     // round 6: K / V tiles by DMA (attn_mfma3_kernel) for the exact head sizes without score bias, rows inside a 32-bit buffer descriptor; NS_ATTN_PIPE=0:
     // attn_mfma2_kernel.  Variant (NS_ATTN_PVAR): bit 0 = the next tile is requested behind K.Q^T instead of in front of it, bit 1 = raised priority while
     // K.Q^T issues — both gain from 4096 keys on (601-611 vs 558-585 TFLOPS causal, 742-751 vs 722 at 8192) and lose below (519-525 vs 529-530 at 2048)
-    if (kn.pipe && !biased && exact && attn_in32(a.sl_kv, a.step_k_sl, a.step_v_sl)) {
+    // (the rule over WHOLE tiles: attn_mfma3_kernel requests every row of its last 64-key tile, and the rows past the last key read as zeros only
+    // while their 32-bit offsets do not wrap back into the descriptor — their weights are 0, but 0 x whatever lies there is not)
+    if (kn.pipe && !biased && exact && attn_in32((a.sl_kv + kA2KB - 1) / kA2KB * kA2KB, a.step_k_sl, a.step_v_sl)) {
       pl.path = AP_PIPELINED;
       pl.xcd_map |= (kn.pvar >= 0 ? kn.pvar : (a.sl_kv >= 3072 ? 3 : 0)) << 8;
     } else {

@@ -220,7 +220,10 @@ __global__ __launch_bounds__(256) void attn_mfma_kernel(const AttnParams p) {
     float* dr = db + (long long)row * p.step_dst_sl + nn;
 #pragma unroll
     for (int dt = 0; dt < NDT; dt++) {
-      const float y = o[dt][r] * ir[r];
+      float y = o[dt][r] * ir[r];
+      // (y is the fp32 value from here on: without this hipcc folds product and conversion into one v_fma_mixlo_f16, and the shadow is the rounding of
+      // the exact product instead of the rounding of what dst holds — a last fp16 bit apart now and then)
+      if (p.dst16) asm volatile("" : "+v"(y));
       dr[16 * dt] = y;
       if (p.dst16) p.dst16[dr - p.dst + 16 * dt] = (_Float16)y;
     }

@@ -6,6 +6,7 @@ launched) prints the plans and walks the translation over every key of a few tab
 The grid is the 480 shapes of tests/test_attn_rows_plan.py times the block sizes 16, 32, 128 and 256.  A paged capacity is table_stride * block_keys,
 so each capacity of that grid (1, 255, 256, 300, 2048, 8192) is rounded up to whole blocks, and the per-request plan it is compared with is the one of
 that rounded capacity: the same shape and capacity, as the paged entry's contract says."""
+import importlib.util
 import os
 import subprocess
 
@@ -34,14 +35,14 @@ def lines(tmp_path_factory):
     subprocess.run([hipcc, "-std=c++20", "-x", "hip", "--offload-arch=gfx950", "--cuda-host-only", "-Wall", "-Werror", "-I", CSRC, MAIN, "-o", exe],
                    check=True, capture_output=True, text=True, timeout=300)
     out = subprocess.run([exe], check=True, capture_output=True, text=True, timeout=120).stdout
-    res = {"plan": [], "refuse": [], "rule32": [], "walk": []}
+    res = {"plan": [], "refuse": [], "rule32": [], "far32": [], "walk": []}
     for line in out.splitlines():
         kind, rest = line.split(" ", 1)
         parts = rest.split(" | ")
         head = {k: num(v) for k, v in (kv.split("=") for kv in parts[0].split())}
         if kind == "plan":
             res[kind].append((head, fields(parts[1]), fields(parts[2])))
-        elif kind in ("refuse", "rule32"):
+        elif kind in ("refuse", "rule32", "far32"):
             res[kind].append((head, fields(parts[1])))
         else:
             res[kind].append((head, {k: num(v) for k, v in (kv.split("=") for kv in parts[1].split())}))
@@ -93,6 +94,21 @@ def test_the_32_bit_rule_at_its_boundary(lines):
     assert got[(limit // step + 1, 2 * step, 256)] == ("SPLIT_REGS", 0, "")
     for (blocks, bstep, _), (_, in32, _) in got.items():
         assert in32 == int((blocks * bstep + 256) * 2 < 2 ** 32)
+
+
+def test_the_pools_of_the_far_address_tests_take_the_kernels_they_assert(lines):
+    """tests/test_gpu_attn_far_addresses.py asserts these kernels through ns_hip_attn_paged_stats on pools of 4 GiB and more: the largest pool the rule
+    accepts goes to the ring kernel, 1.4 * 2^31 elements to the register kernel.  If the rule moves, this fails first; the numbers are those of
+    tests/tools/attn_far_layout.py."""
+    spec = importlib.util.spec_from_file_location("attn_far_layout", os.path.join(ROOT, "tests", "tools", "attn_far_layout.py"))
+    FL = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(FL)
+    got = {(i["hs"], i["bk"], i["over"]): (i["pool_blocks"], i["block_step"], o["path"], o["in32"], o["why"]) for i, o in lines["far32"]}
+    assert len(got) == 2 * len(FL.PAGED_SHAPES)
+    for hs, bk in FL.PAGED_SHAPES:
+        step = FL.block_step(hs, bk)
+        assert got[(hs, bk, 0)] == (FL.pool_blocks("under", step, 0), step, "RING", 1, "")
+        assert got[(hs, bk, 1)] == (FL.pool_blocks("over", step, 0), step, "SPLIT_REGS", 0, "")
 
 
 def test_the_translation_over_every_key_of_a_few_tables(lines):

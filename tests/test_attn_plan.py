@@ -2,6 +2,7 @@
 arguments, grid, LDS, context ranges, partials.  A host program (tests/tools/attn_plan_main.cpp, built with the library's compiler, nothing
 launched) prints the plan for a grid of calls; the rule it must follow — the table "What tests which launch path" of
 docs/kernels/attention.md — is written out here independently."""
+import importlib.util
 import math
 import os
 import re
@@ -78,6 +79,8 @@ def strides(i):
         k = (rows, 1, k[2], k[3])
     if i["klay"] in (3, 4):
         k = v = (1, i["hkv"] * i["hs"] if i["klay"] == 3 else row, i["hs"], k[3] if i["klay"] == 3 else i["hkv"] * i["hs"])
+    if i["klay"] == 5:
+        k = v = (1, i["ksl"] or i["hkv"] * i["hs"], i["hs"], i["kbs"] or i["hkv"] * rows * i["hs"])
     return k, v
 
 
@@ -158,7 +161,7 @@ def expected(i):
         aligned = int(bool(i["dal"]) and i["d16"] != 2)  # (the row strides of dst are multiples of 4 floats in every case)
         xcd = int(not kn["no_xcd_map"] and (hkv * bs) % 8 == 0)
         e.update(grid=(nqb * hn * bs, 1, 1), lds=2 * stage_bytes(e["phs"]), sb=int(biased), pad=int(not exact and hs != 256), nqb=nqb, al=aligned)
-        if kn["pipe"] and not biased and exact and in32(slkv, k[1], v[1]):
+        if kn["pipe"] and not biased and exact and in32(ceil_div(slkv, 64) * 64, k[1], v[1]):  # (whole 64-key tiles: the kernel requests the last one whole)
             pvar = kn["pvar"] if kn["pvar"] >= 0 else (3 if slkv >= 3072 else 0)
             return dict(e, path="PIPELINED", xcd=xcd | pvar << 8)
         return dict(e, path="ROWS128", xcd=xcd)
@@ -215,8 +218,30 @@ def test_rows_beyond_a_32_bit_descriptor_take_the_register_staged_kernels(plans)
     far = [(i, o) for i, o in plans if i["klay"] == 4]
     by = {(i["slq"], i["slkv"]): (o["path"], o["hsp"], o["sb"], o["pad"]) for i, o in far}
     assert by[(128, 128)] == by[(257, 128)] == ("ROWS128", 128, 0, 0)  # attn_mfma2_kernel<128, false, false>
-    assert by[(128, 127)] == by[(257, 127)] == ("PIPELINED", 128, 0, 0)
+    # 127 keys lie inside a descriptor, the 128 rows of their two tiles do not: attn_mfma3_kernel requests whole tiles, and a row past the last key
+    # whose offset wraps is read from inside the descriptor (tests/test_gpu_attn_far_addresses.py, the slab rule's boundary)
+    assert by[(128, 127)] == by[(257, 127)] == ("ROWS128", 128, 0, 0)
+    assert by[(128, 64)] == by[(257, 64)] == ("PIPELINED", 128, 0, 0)
     assert by[(1, 128)][0] == "SPLIT_REGS" and by[(1, 127)][0] == "RING"
+
+
+def test_the_addresses_of_the_far_address_tests_take_the_paths_they_assert(plans):
+    """tests/test_gpu_attn_far_addresses.py asserts these paths through ns_hip_attn_stats on buffers of 4 GiB and more; if a 32-bit rule moves, this
+    fails first and says which number moved.  The numbers are those of tests/tools/attn_far_layout.py."""
+    spec = importlib.util.spec_from_file_location("attn_far_layout", os.path.join(ROOT, "tests", "tools", "attn_far_layout.py"))
+    FL = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(FL)
+    far = {(i["hs"], i["slq"], i["slkv"], i["bs"], i["ksl"], i["kbs"]): o["path"] for i, o in plans if i["klay"] == 5}
+    assert all((i["hn"], i["hkv"], i["flags"]) == (FL.HN, FL.HKV, CAUSAL) for i, _ in plans if i["klay"] == 5)
+    n = FL.EDGE_KEYS
+    (k_below, k_above), (t_below, t_above) = FL.edge_steps(n), FL.edge_steps(FL.tile_rows(n))
+    assert FL.tile_rows(n) == 320 and t_above < k_below
+    for hs in (64, 128):
+        assert far[(hs, 1, n, 1, k_below, 0)] == "RING" and far[(hs, 1, n, 1, k_above, 0)] == "SPLIT_REGS"  # test_slab_rule_boundary_decode
+        assert far[(hs, 130, n, 1, t_below, 0)] == "PIPELINED"  # test_slab_rule_boundary_prefill: below, above, between_keys_and_tiles
+        assert far[(hs, 130, n, 1, t_above, 0)] == "ROWS128" and far[(hs, 130, n, 1, k_below, 0)] == "ROWS128"
+        got = [far[(hs, slq, 200, 3, 0, FL.SLAB_STEP)] for slq in (1, 5, 40, 130)]  # test_forward_on_far_slabs: the batch step is no part of a rule
+        assert got == ["RING", "RING", "ROWS64", "PIPELINED"], got
 
 
 def test_refusals_say_why(plans):

@@ -3,6 +3,7 @@
 //   plan  <the call, key=value> | <the fields of the paged plan> | <the fields of the per-request (rows) plan of the same shape and capacity>
 //   refuse <what is wrong, key=value> | path=.. why=..
 //   rule32 pool_blocks=.. block_step=.. hs=.. | path=.. in32=..
+//   far32 hs=.. bk=.. over=.. pool_blocks=.. block_step=.. | path=.. in32=..
 //   walk  table=<name> | keys=.. cells=.. outside=.. collide=.. noaccess=.. wantno=.. shared=..
 // Host code only: no HIP call is made, no tensor exists — the pointers are made-up addresses, the tables live on the host.
 #include <algorithm>
@@ -122,6 +123,23 @@ static void run_rule32(int pool_blocks, long long block_step, int hs) {
   printf("rule32 pool_blocks=%d block_step=%lld hs=%d | path=%s in32=%d why=%s\n", pool_blocks, block_step, hs, path, int(attn_page_in32(pg)), why.c_str());
 }
 
+// the pools of tests/test_gpu_attn_far_addresses.py (tests/tools/attn_far_layout.py states the same numbers): 2 requests, 4 / 2 heads, position-major
+// blocks of bk keys, the largest pool the rule accepts ("under") and one of 1.4 * 2^31 elements ("over")
+static void run_far32(int hs, int bk) {
+  for (int over = 0; over < 2; over++) {
+    Case c;
+    c.hs = hs, c.bk = bk, c.hn = 4, c.hkv = 2, c.bs = 2, c.cap = bk == 16 ? 256 : 512;
+    const long long step = (long long)bk * c.hkv * hs;
+    c.pool_blocks = over ? int((long long)(1.4 * double(1ll << 31)) / step) : int(((1ll << 31) - 257) / step);
+    std::string why;
+    AttnPage pg;
+    const AttnPlan pl = paged_plan(c, &why, &pg);
+    const char* path = pl.path == AP_RING ? "RING" : pl.path == AP_SPLIT_REGS ? "SPLIT_REGS" : "OTHER";
+    printf("far32 hs=%d bk=%d over=%d pool_blocks=%d block_step=%lld | path=%s in32=%d why=%s\n", hs, bk, over, pg.pool_blocks, pg.block_step, path,
+           int(attn_page_in32(pg)), why.c_str());
+  }
+}
+
 // every key of every request of a table through attn_page_cell, for K's and V's row strides of both block layouts
 static void run_walk(const char* name, const std::vector<int>& table, int requests, int table_stride, int bk, int pool_blocks, int shared_blocks) {
   const int hkv = 2, hs = 64;
@@ -219,6 +237,8 @@ int main() {
   run_rule32(1, limit, 128);                         // ... at it
   run_rule32(1, limit + 8, 128);
   run_rule32(int(limit / step) + 1, 2 * step, 256);  // the register kernel's own shapes do not care
+  for (int hs : {64, 128})
+    for (int bk : {16, 128}) run_far32(hs, bk);
   // 4. the translation over every key of a few tables
   {
     const int bk = 16, ts = 6, req = 3, pool = req * ts + 5;

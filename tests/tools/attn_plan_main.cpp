@@ -13,7 +13,9 @@ using namespace ns;
 
 struct Case {
   int hs = 128, slq = 1, slkv = 2048, hn = 8, hkv = 8, bs = 1, flags = 0;
-  int klay = 0;  // K / V: 0 head-major rows, 1 transposed K, 2 row stride hs + 4 (no multiple of 8), 3 position-major rows, 4 rows 2^24 halves apart
+  int klay = 0;  // K / V: 0 head-major rows, 1 transposed K, 2 row stride hs + 4 (no multiple of 8), 3 position-major rows, 4 rows 2^24 halves apart,
+                 // 5 position-major rows ksl halves apart (0: dense) and batch entries kbs halves apart (0: dense) — tests/tools/attn_far_layout.py
+  long long ksl = 0, kbs = 0;
   int qal = 1, dal = 1, d16 = 0;  // Q / dst 16-byte aligned; fp16 shadow: 0 none, 1 aligned, 2 not
   float scale = 0.125f;
   const char* knob = "none";
@@ -50,6 +52,11 @@ static void run(const Case& c) {
     a.step_k_head_num = a.step_v_head_num = c.hs;
     if (c.klay == 4) a.step_k_bs = a.step_v_bs = c.hkv * c.hs;  // (strides that fit the arguments' ints; nothing is read)
   }
+  if (c.klay == 5) {
+    a.step_k_head_num = a.step_v_head_num = c.hs;
+    a.step_k_sl = a.step_v_sl = int(c.ksl ? c.ksl : (long long)c.hkv * c.hs);
+    a.step_k_bs = a.step_v_bs = int(c.kbs ? c.kbs : (long long)c.hkv * rows * c.hs);
+  }
   AttnKnobs kn;
   const struct {
     const char* name;
@@ -83,8 +90,8 @@ static void run(const Case& c) {
     }
   const size_t ws = attn_ws_bytes(kn, c.bs, c.hn, c.hkv, c.hs, c.slq, c.cap > 0 ? c.cap : c.slkv);
   const char* path[] = {"REFUSED", "GENERIC", "SPLIT_REGS", "RING", "ROWS64", "ROWS128", "PIPELINED"};
-  printf("hs=%d slq=%d slkv=%d hn=%d hkv=%d bs=%d flags=%d klay=%d qal=%d dal=%d d16=%d scale=%g knob=%s kval=%d cap=%d affil=%d | ", c.hs, c.slq, c.slkv,
-         c.hn, c.hkv, c.bs, c.flags, c.klay, c.qal, c.dal, c.d16, double(c.scale), c.knob, c.kval, c.cap, c.affil);
+  printf("hs=%d slq=%d slkv=%d hn=%d hkv=%d bs=%d flags=%d klay=%d qal=%d dal=%d d16=%d scale=%g knob=%s kval=%d cap=%d affil=%d ksl=%lld kbs=%lld | ", c.hs,
+         c.slq, c.slkv, c.hn, c.hkv, c.bs, c.flags, c.klay, c.qal, c.dal, c.d16, double(c.scale), c.knob, c.kval, c.cap, c.affil, c.ksl, c.kbs);
   printf("path=%s G=%d lpk=%d dpl=%d hsp=%d sb=%d pad=%d grid=%u,%u,%u block=%u lds=%zu nsplit=%d kps=%d chunks=%d gfull=%d hf=%d dyn=%d,%d,%d tick=%d merge=%d "
          "pbytes=%zu nqb=%d al=%d xcd=%d kmove=%d kdelta=%d phs=%d off=%d lf=%d qk=%g ws=%zu viol=%lld sum=%llu why=%s\n",
          path[pl.path], pl.G, pl.lpk, pl.dpl, pl.hs_pad, pl.sb, pl.pad, pl.grid.x, pl.grid.y, pl.grid.z, pl.block.x, pl.lds, sp.nsplit, sp.keys_per_split,
@@ -181,8 +188,30 @@ int main() {
   for (int slq : {1, 128, 257}) {
     c = Case(), c.klay = 4, c.slq = slq, c.slkv = 128;  // in32 false
     run(c);
-    c.slkv = 127;                                       // ... and just inside
+    c.slkv = 127;                                       // ... and just inside for its keys, not for the 128 rows of its two tiles
     run(c);
+    c.slkv = 64;                                        // ... inside for both
+    run(c);
+  }
+  // the addresses of tests/test_gpu_attn_far_addresses.py (tests/tools/attn_far_layout.py states the same numbers; 4 / 2 heads, causal): 300 keys at the
+  // largest row step inside a descriptor and one step of 8 more, for the keys (the ring kernel's rule) and for the 320 rows of their five tiles
+  // (attn_mfma3_kernel's); batch entries 2^30 + 2^21 halves apart, which no rule looks at
+  const long long edge300 = ((1ll << 31) - 257) / 300 / 8 * 8, edge320 = ((1ll << 31) - 257) / 320 / 8 * 8;
+  for (int hs : {64, 128}) {
+    Case f;
+    f.hs = hs, f.hn = 4, f.hkv = 2, f.flags = NS_ATTN_FLAG_IS_CAUSAL, f.klay = 5, f.slkv = 300;
+    for (long long ksl : {edge300, edge300 + 8}) {
+      c = f, c.slq = 1, c.ksl = ksl;
+      run(c);
+    }
+    for (long long ksl : {edge320, edge320 + 8, edge300}) {
+      c = f, c.slq = 130, c.ksl = ksl;
+      run(c);
+    }
+    for (int slq : {1, 5, 40, 130}) {
+      c = f, c.slq = slq, c.slkv = 200, c.bs = 3, c.kbs = (1ll << 30) + (1ll << 21);
+      run(c);
+    }
   }
   c = Case(), c.hn = c.hkv = 8192, c.slq = 15;  // 122880 workgroups per range: past the grid's y
   run(c);
