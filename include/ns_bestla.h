@@ -759,6 +759,27 @@ size_t ns_hip_attn_block_paged_workspace_size(int batch, int head_num, int heads
 /* Process-wide counts of ns_hip_attn_block_paged: [0] launches of the head-size-64 kernel, [1] of the head-size-128 kernel, [2] merge launches,
  * [3] refused calls. */
 void ns_hip_attn_block_paged_stats(unsigned long long out[4]);
+/* ns_hip_attn_prefill_paged: PROMPT-SIZED QUERY BLOCKS over the pools — ns_hip_attn_block_paged's arguments and, word for word, its contract (batch_size
+ * = the requests, sl_kv = the capacity = table_stride * block_keys, sl_q = max_q >= 1; Q, dst and dst16 packed through dQStart[batch_size + 1]; q_len_b,
+ * kv_len_b and the causal rule as there; a row that sees no key is zeros, a request without rows writes nothing, rows no request names are not touched;
+ * an id outside [0, pool_blocks) never becomes an address and is read as zeros, entries at or behind ceil(kv_len_b / block_keys) may hold anything, no
+ * byte behind kv_len_b reaches a result), served by the 128-row matrix-core kernel (128 query rows per workgroup, K / V tiles of 64 keys staged once per
+ * workgroup through LDS, each staged row fetched through its own table entry) instead of the context-split 64-slot kernel:
+ *   - ONE launch that writes dst itself: no partials, no merge; `tmp` and the stream's scratch are not used, and the entry is capturable without a
+ *     first eager call;
+ *   - any head size that is a multiple of 8 up to 128 (padded to 64 / 128), NS_ATTN_FLAG_IS_ALIBI8 (slopes by ns_hip_attn_set_head_partition) and
+ *     NS_ATTN_FLAG_IS_TANH30, any score scale (a call with QK_scale * Q_sc * K_sc <= 0 takes the instantiation that scales the scores up front).
+ * It is the form for a prompt or a prompt chunk; for a few rows over a long cache the block entry, which spreads the keys over workgroups, is the
+ * faster one (docs/kernels/attention.md gives the row count from which to prefer this entry).
+ * Refused (-1, ns_hip_last_error set, nothing written): what ns_hip_attn_decode_paged refuses of the cache's description, a null dQStart or dKvLens,
+ * non-PLAIN layouts, batch_size < 1, head_size % 8 != 0 or head_size > 128 (136 .. 256: the 256-wide form of the kernel would spill registers and is
+ * not built), head_num % heads_kv != 0, max_q < 1, sl_kv < 1, K / V rows not contiguous in the head dimension or not 16-byte aligned,
+ * ceil(max_q / 128) * head_num * batch_size >= 2^31, an ALiBi call whose heads do not fit the head partition. */
+int ns_hip_attn_prefill_paged(const attn_fp32_fp16_fp16_fp32_fwd_args_t* dparams, const int* dQStart, const int* dKvLens, int kv_len_bias,
+                              const int* dBlockTable, int table_stride, int block_keys, int pool_blocks, long long block_step, void* dst16, void* stream);
+/* Process-wide counts of ns_hip_attn_prefill_paged: launches by padded head size [0] 64, [1] 128, [2] 256 (none: not built); [3] launches of a
+ * biased instantiation (score bias or a score scale that is not positive), [4] of a padded one; [5] refused calls. */
+void ns_hip_attn_prefill_paged_stats(unsigned long long out[6]);
 
 /* ----------------------------------------------------------------------------------------------
  * Part 4b — mixture-of-experts matmul with the routing on the device.  Device twin of

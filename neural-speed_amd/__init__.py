@@ -278,6 +278,9 @@ def lib():
         L.ns_hip_attn_block_paged_workspace_size.argtypes = [i, i, i, i, i, i]
         L.ns_hip_attn_block_paged_stats.restype = None
         L.ns_hip_attn_block_paged_stats.argtypes = [vp]
+        L.ns_hip_attn_prefill_paged.argtypes = [vp, vp, vp, i, vp, i, i, i, C.c_longlong, vp, vp]
+        L.ns_hip_attn_prefill_paged_stats.restype = None
+        L.ns_hip_attn_prefill_paged_stats.argtypes = [vp]
         L.ns_hip_blob_validate.argtypes = [vp, sz]
         L.ns_BTLAGemmPackBSize.restype = sz
         L.ns_BTLAGemmPackBSize.argtypes = [sz, sz, sz, u32, u32, b, i, vp]

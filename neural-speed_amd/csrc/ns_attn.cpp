@@ -204,6 +204,21 @@ static hipError_t launch_attn_block_paged_call(const attn_fp32_fp16_fp16_fp32_fw
   return e;
 }
 
+// ns_hip_attn_prefill_paged: plan (attn_prefill_paged_plan) and ONE launch of the 128-row kernel's PAGED instantiation: no partials, no scratch
+static std::atomic<uint64_t> g_attn_prefill_paged[6];  // ns_hip_attn_prefill_paged_stats
+static hipError_t launch_attn_prefill_paged_call(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const int* q_start, const int* lens, int bias,
+                                                 const AttnPage& page, hipStream_t st, std::string* why, void* dst16) {
+  const AttnPrefillPagedPlan pl = attn_prefill_paged_plan(a, dst16, attn_knobs(), page, q_start, lens, bias, why);
+  if (!pl.ok) return hipErrorInvalidValue;
+  const hipError_t e = launch_attn_prefill_paged(pl, st);
+  if (e == hipSuccess) {
+    g_attn_prefill_paged[pl.hs_pad == 64 ? 0 : (pl.hs_pad == 128 ? 1 : 2)].fetch_add(1, std::memory_order_relaxed);
+    if (pl.sb) g_attn_prefill_paged[3].fetch_add(1, std::memory_order_relaxed);
+    if (pl.pad) g_attn_prefill_paged[4].fetch_add(1, std::memory_order_relaxed);
+  }
+  return e;
+}
+
 // scratch a moving-length decode launch needs (partials for the longest context, the merge tickets): allocated BEFORE the route's capture
 bool attn_prepare_moving(hipStream_t st, int batch, int heads, int heads_kv, int head_size, int cap) {
   const size_t b = attn_ws_bytes(attn_knobs(), batch, heads, heads_kv, head_size, 1, cap);
@@ -312,6 +327,24 @@ int ns_hip_attn_block_paged(const attn_fp32_fp16_fp16_fp32_fwd_args_t* a, const 
     return -1;
   }
   return 0;
+}
+
+int ns_hip_attn_prefill_paged(const attn_fp32_fp16_fp16_fp32_fwd_args_t* a, const int* dQStart, const int* dKvLens, int kv_len_bias, const int* dBlockTable,
+                              int table_stride, int block_keys, int pool_blocks, long long block_step, void* dst16, void* stream) {
+  std::string why;
+  const AttnPage page = {dBlockTable, table_stride, attn_block_shift(block_keys), pool_blocks, block_step};
+  const hipError_t e =
+      a ? launch_attn_prefill_paged_call(*a, dQStart, dKvLens, kv_len_bias, page, static_cast<hipStream_t>(stream), &why, dst16) : hipErrorInvalidValue;
+  if (e != hipSuccess) {
+    g_attn_prefill_paged[5].fetch_add(1, std::memory_order_relaxed);
+    set_error(why.empty() ? std::string("attention launch (prompt blocks over a paged cache): ") + (a ? hipGetErrorString(e) : "null arguments") : why);
+    return -1;
+  }
+  return 0;
+}
+
+void ns_hip_attn_prefill_paged_stats(unsigned long long out[6]) {
+  for (int i = 0; i < 6; i++) out[i] = g_attn_prefill_paged[i].load(std::memory_order_relaxed);
 }
 
 size_t ns_hip_attn_block_paged_workspace_size(int batch, int head_num, int heads_kv, int head_size, int max_q, int capacity) {

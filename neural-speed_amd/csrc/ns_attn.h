@@ -165,6 +165,26 @@ __host__ __device__ __forceinline__ int attn_block_q_len(const int* q_start, int
   return n < 0 ? 0 : (n > max_q ? max_q : int(n));
 }
 
+// ---- prompt-sized query blocks over a paged cache (ns_hip_attn_prefill_paged; attn_mfma2_body's PAGED instantiations, ns_attn_prefill.hip) --------
+// Argument block: a as the 128-row kernel reads it, with a.sl_q = max_q, a.sl_kv = a request's capacity, a.k / a.v the pool bases and no batch step
+// (Q, dst and dst16 are packed through q_start, as above); kv_lens[b] + kdelta, clamped to [0, capacity], are request b's live keys.
+struct AttnPrefillPagedParams {
+  AttnParams a;
+  AttnPage pg;
+  const int* q_start;
+  const int* kv_lens;
+  int kdelta;
+};
+// live keys of request b: attn_live_kv<true>'s clamp
+__host__ __device__ __forceinline__ int attn_prefill_kv_len(const int* kv_lens, int b, int kdelta, int cap) {
+  const long long len = (long long)kv_lens[b] + kdelta;
+  return len < 0 ? 0 : (len > cap ? cap : int(len));
+}
+// Row r of a 64-key tile that starts at pos0 -> the key whose cell a PAGED workgroup stages there: the row clamped to the request's last live key
+// (kv_len >= 1), so no cell behind kv_len is read and the table entry is that key's, (key >> block_shift) < ceil(kv_len / block_keys).  THE row
+// rule of that kernel: its fetch and tests/tools/attn_prefill_paged_plan_main.cpp both go through it, then through attn_page_at.
+__host__ __device__ __forceinline__ int attn_prefill_tile_key(int pos0, int r, int kv_len) { return min(pos0 + r, kv_len - 1); }
+
 // ---- the launch decision as a value (ns_attn_plan.cpp) -------------------------------------------------------------------------------------
 // Every tunable the decision reads.  attn_knobs() (ns_attn.cpp) fills it from ns_hip_set_tuning's atomics and the environment.
 struct AttnKnobs {
@@ -229,11 +249,26 @@ AttnBlockPagedPlan attn_block_paged_plan(const attn_fp32_fp16_fp16_fp32_fwd_args
 // what ns_hip_attn_block_paged_workspace_size answers: the plan's partial_bytes, from the shape alone (0: no plan of that shape)
 size_t attn_block_paged_ws_bytes(const AttnKnobs& knobs, int batch, int head_num, int heads_kv, int head_size, int max_q, int capacity);
 
+// The plan of ns_hip_attn_prefill_paged: a pure function like attn_block_paged_plan (tests/test_attn_prefill_paged_plan.py).  a.sl_q is max_q, a.sl_kv
+// the capacity.  One launch of attn_mfma2_body<hs_pad, sb, pad, 1, PAGED>: ceil(max_q / 128) query blocks x heads x requests workgroups; the query
+// blocks a request does not have leave at once.  No partials, no scratch.  !ok: *why says what is wrong with the call.
+struct AttnPrefillPagedPlan {
+  bool ok = false;
+  int hs_pad = 0, sb = 0, pad = 0;  // the template arguments
+  AttnPrefillPagedParams pp;
+  dim3 grid, block;
+  size_t lds = 0;
+  int nqb = 0, aligned = 0, xcd_map = 0;  // query blocks per (head, request), 16-byte stores of the output, XCD remap
+};
+AttnPrefillPagedPlan attn_prefill_paged_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst16, const AttnKnobs& knobs, const AttnPage& page,
+                                             const int* q_start, const int* kv_lens, int kv_len_bias, std::string* why);
+
 // ---- launches of a plan ----------------------------------------------------------------------------------------------------------------------
 hipError_t launch_attn_onerow(const AttnPlan& pl, float* ws, uint32_t* tickets, hipStream_t st);  // ns_attn_decode.hip: AP_GENERIC, AP_SPLIT_REGS, AP_RING (+ merge)
 hipError_t launch_attn_rows(const AttnPlan& pl, hipStream_t st);                                  // ns_attn_prefill.hip: AP_ROWS64, AP_ROWS128, AP_PIPELINED
 hipError_t launch_attn_block_split(const AttnPlan& pl, float* ws, hipStream_t st);                // ns_attn_block.hip: AP_BLOCK_SPLIT (+ merge)
 hipError_t launch_attn_block_paged(const AttnBlockPagedPlan& pl, float* ws, hipStream_t st);     // ns_attn_block.hip: the PAGED instantiation + its merge
+hipError_t launch_attn_prefill_paged(const AttnPrefillPagedPlan& pl, hipStream_t st);             // ns_attn_prefill.hip: the PAGED instantiations of the 128-row kernel
 hipError_t launch_attn_merge(const AttnSplitParams& sp, unsigned batch, hipStream_t st, bool rows = false);  // ns_attn_decode.hip: attn_merge_kernel over sp.ws
 // touch_attn_module (ns_common.h) makes the runtime load all four code objects
 inline void touch_kernel(const void* kernel) {

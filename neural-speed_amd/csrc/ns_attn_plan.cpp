@@ -367,4 +367,80 @@ AttnBlockPagedPlan attn_block_paged_plan(const attn_fp32_fp16_fp16_fp32_fwd_args
   return pl;
 }
 
+// ---- prompt-sized query blocks over a paged cache (ns_hip_attn_prefill_paged) ------------------------------------------------------------------------
+// One launch of the 128-row kernel's PAGED instantiation for every call the entry serves: there is no other kernel to give a call to, so one row is a
+// plan like any other.  The instantiation: the padded head size, SB for a biased call and for a score scale that is not positive (SB scales the
+// scores up front; the unbiased instantiations take the maximum of RAW scores), PAD for a head size that is not 64 / 128 / 256.
+AttnPrefillPagedPlan attn_prefill_paged_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst16, const AttnKnobs& kn, const AttnPage& page,
+                                             const int* q_start, const int* kv_lens, int kv_len_bias, std::string* why) {
+  AttnPrefillPagedPlan pl;
+  memset(&pl.pp, 0, sizeof(pl.pp));
+  auto refuse = [&](const char* text) {
+    *why = text;
+    return pl;
+  };
+  if (a.Q_layout != ATTN_FWD_LAYOUT_PLAIN || a.K_layout != ATTN_FWD_LAYOUT_PLAIN || a.V_layout != ATTN_FWD_LAYOUT_PLAIN ||
+      a.dst_layout != ATTN_FWD_LAYOUT_PLAIN)
+    return refuse("attention: only ATTN_FWD_LAYOUT_PLAIN tensors are supported");
+  if (!q_start) return refuse("attention, prompt blocks over a paged cache: dQStart is null");
+  if (!kv_lens) return refuse("attention, prompt blocks over a paged cache: dKvLens is null");
+  if (a.batch_size < 1) return refuse("attention, prompt blocks over a paged cache: batch_size (the requests) must be at least 1");
+  if (a.head_size < 8 || a.head_size % 8 != 0 || a.head_size > 256)
+    return refuse("attention, prompt blocks over a paged cache: head_size must be a multiple of 8, at most 256");
+  // (the head-size-256 PAGED instantiations of the 128-row kernel need scratch with the whole register file: not built — docs/open_items.md)
+  if (a.head_size > 128)
+    return refuse("attention, prompt blocks over a paged cache: head sizes above 128 are not served (the 256-wide kernel would spill registers)");
+  if (a.heads_kv < 1 || a.head_num < 1 || a.head_num % a.heads_kv != 0)
+    return refuse("attention, prompt blocks over a paged cache: head_num must be a multiple of heads_kv");
+  if (a.sl_q < 1) return refuse("attention, prompt blocks over a paged cache: sl_q is max_q, the most query rows of one request (at least 1)");
+  if (a.sl_kv < 1) return refuse("attention, prompt blocks over a paged cache: sl_kv is the capacity of a request (at least 1 key)");
+  if (const char* text = attn_page_refusal(a, page)) return refuse(text);
+  if (a.step_k_head_size != 1 || a.step_v_head_size != 1 || a.step_k_sl % 8 != 0 || a.step_v_sl % 8 != 0 || a.step_k_head_num % 8 != 0 ||
+      a.step_v_head_num % 8 != 0 || (reinterpret_cast<uintptr_t>(a.K) & 15) != 0 || (reinterpret_cast<uintptr_t>(a.V) & 15) != 0)
+    return refuse("attention, prompt blocks over a paged cache: K / V rows must be contiguous in the head dimension and 16-byte aligned");
+  const size_t nqb = (size_t(a.sl_q) + 127) / 128, wgs = nqb * size_t(a.head_num) * size_t(a.batch_size);
+  if (wgs >= (size_t(1) << 31))
+    return refuse("attention, prompt blocks over a paged cache: ceil(max_q / 128) * head_num * batch_size must stay below 2^31 workgroups");
+  AttnParams& p = pl.pp.a;
+  p.q = a.Q;
+  p.k = reinterpret_cast<const _Float16*>(a.K);
+  p.v = reinterpret_cast<const _Float16*>(a.V);
+  p.dst = a.dst;
+  p.dst16 = static_cast<_Float16*>(const_cast<void*>(dst16));
+  p.qk_scale = a.QK_scale * a.Q_sc * a.K_sc;
+  p.out_scale = a.V_sc / a.dst_sc;
+  p.flags = a.attn_flags;
+  p.head_num = a.head_num, p.heads_kv = a.heads_kv, p.head_size = a.head_size, p.sl_q = a.sl_q, p.sl_kv = a.sl_kv;
+  p.step_q_head_num = a.step_q_head_num, p.step_q_sl = a.step_q_sl;  // (packed rows: no batch step of Q or dst; the pools: none of K or V)
+  p.step_k_head_num = a.step_k_head_num, p.step_k_sl = a.step_k_sl, p.step_k_head_size = 1;
+  p.step_v_head_num = a.step_v_head_num, p.step_v_sl = a.step_v_sl, p.step_v_head_size = 1;
+  p.step_dst_head_num = a.step_dst_head_num, p.step_dst_sl = a.step_dst_sl;
+  p.hs_pad = a.head_size <= 64 ? 64 : 128;
+  // the slopes, as attn_plan sets them
+  const int all_heads = kn.alibi_heads > 0 ? kn.alibi_heads : a.head_num;
+  p.alibi_head_off = kn.alibi_heads > 0 ? kn.alibi_off : 0;
+  if ((a.attn_flags & NS_ATTN_FLAG_IS_ALIBI8) && (p.alibi_head_off < 0 || p.alibi_head_off + a.head_num > all_heads))
+    return refuse("attention: head partition (ns_hip_attn_set_head_partition) does not contain this call's heads");
+  const int lf = 1 << int(floor(log2(double(all_heads))));
+  p.alibi_log2_floor = lf;
+  p.alibi_m0 = powf(2.0f, -8.f / float(lf));
+  p.alibi_m1 = powf(2.0f, -4.f / float(lf));
+  const bool biased = (a.attn_flags & (NS_ATTN_FLAG_IS_ALIBI8 | NS_ATTN_FLAG_IS_TANH30)) != 0;
+  pl.pp.pg = page, pl.pp.q_start = q_start, pl.pp.kv_lens = kv_lens, pl.pp.kdelta = kv_len_bias;
+  pl.hs_pad = p.hs_pad;
+  pl.sb = biased || !(p.qk_scale > 0.f);
+  pl.pad = a.head_size != p.hs_pad;
+  pl.nqb = int(nqb);
+  pl.grid = dim3(unsigned(wgs));
+  pl.block = dim3(256);
+  pl.lds = size_t(2) * (pl.hs_pad == 64 ? a2_stage_bytes<64>() : a2_stage_bytes<128>());
+  pl.aligned = (reinterpret_cast<uintptr_t>(a.dst) & 15) == 0 && a.step_dst_sl % 4 == 0 && a.step_dst_head_num % 4 == 0 &&
+               (!dst16 || (reinterpret_cast<uintptr_t>(dst16) & 7) == 0);
+  // the remap is a bijection of the workgroup ids whatever a workgroup then does, so the ones that leave early do not disturb it, and the query
+  // blocks that stay still share their kv head's pages through one XCD's L2: the rule attn_plan uses, requests in the place of the batch
+  pl.xcd_map = !kn.no_xcd_map && (size_t(a.heads_kv) * a.batch_size) % 8 == 0;
+  pl.ok = true;
+  return pl;
+}
+
 }  // namespace ns

@@ -1,5 +1,6 @@
 // ns_attn_prefill.hip — fused attention, the matrix-core kernels for 16 or more query rows (attn_mfma_kernel: 64 rows per workgroup;
-// attn_mfma2_kernel, attn_mfma3_kernel: 128), and the launch of a plan that names one (ns_attn.h).
+// attn_mfma2_kernel, attn_mfma3_kernel: 128; attn_mfma2_paged_kernel: attn_mfma2_kernel's body over a paged cache, ns_hip_attn_prefill_paged), and the
+// launch of a plan that names one (ns_attn.h).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -261,8 +262,19 @@ typedef short ashort4_t __attribute__((ext_vector_type(4)));
 // tile traffic is spread over twice the rows; all 512 registers, one wave per SIMD) was built, is correct (the whole attention suite and the
 // shape fuzz pass on it) and is SLOWER: 4096 tokens 0.484 vs 0.268 ms, 8192 1.44 vs 0.85, 16384 4.89 vs 2.95 (profiles/r04bg_*) — two
 // co-resident waves per SIMD hide more than halving the LDS traffic saves, and the 128-wide form spills 24 registers.
-template <int HS, bool SB, bool PAD, int RG = 1>
-__device__ __forceinline__ void attn_mfma2_body(const AttnParams& p, const int nqb, const int aligned_dst, const int xcd_map) {
+// PAGED (ns_hip_attn_prefill_paged; argument block AttnPrefillPagedParams, ns_attn.h): prompt-sized query blocks over a paged cache.  A unit is a
+// (head, REQUEST) with its own packed query rows (q_start[b] ..) and its own live keys (kv_lens[b] + kdelta): the query blocks the request does not
+// have leave in front of any barrier, sl_q / sl_kv of everything below are the request's q_len / kv_len, and every staged K / V row comes from the
+// pools through that row's own table entry (attn_prefill_tile_key, attn_page_at: -1 is a load that is not issued and a register of zeros).  The
+// entries of tile b + 1 are requested in front of tile b's K / V loads and held in one register, so no K / V load waits for a table lookup except the
+// first tile's.  The arithmetic is the uniform body's, operation for operation; the uniform instantiations hold the instructions they held without
+// it (docs/kernels/attention.md, "Prompt-sized query blocks over a paged cache").
+__device__ __forceinline__ const AttnParams& attn_params_of(const AttnParams& p) { return p; }
+__device__ __forceinline__ const AttnParams& attn_params_of(const AttnPrefillPagedParams& pp) { return pp.a; }
+template <int HS, bool SB, bool PAD, int RG = 1, bool PAGED = false>
+__device__ __forceinline__ void attn_mfma2_body(const std::conditional_t<PAGED, AttnPrefillPagedParams, AttnParams>& pp, const int nqb, const int aligned_dst,
+                                                const int xcd_map) {
+  const AttnParams& p = attn_params_of(pp);
   constexpr int NJ = HS / 16, NDT = HS / 32, NCH = HS / 8, KROW = HS * 2, NSUB = HS / 16;
   constexpr int KTILE = kA2KB * KROW, STAGE = a2_stage_bytes<HS>();
   constexpr int KU = NCH / 4;               // 16-byte K chunks per thread and tile
@@ -294,13 +306,25 @@ __device__ __forceinline__ void attn_mfma2_body(const AttnParams& p, const int n
   const int qblk = causal && heavy_first ? nqb - 1 - int(ordn) : int(ordn);
   const int ihn = hb % p.head_num, ibs = hb / p.head_num;
   const int ihkv = ihn / (p.head_num / p.heads_kv);
-  const int off = p.sl_kv - p.sl_q;
   constexpr int WGR = 128 * RG;  // query rows per workgroup
+  // PAGED: the request's own geometry — its packed query rows, its live keys
+  int q_base = 0, q_len = 0, kv_len = 0;
+  if constexpr (PAGED) {
+    q_base = pp.q_start[ibs];
+    q_len = attn_block_q_len(pp.q_start, ibs, p.sl_q);
+    kv_len = attn_prefill_kv_len(pp.kv_lens, ibs, pp.kdelta, p.sl_kv);
+    if (qblk * WGR >= q_len) return;  // no row of this query block is a row of the request (workgroup-uniform, in front of any barrier)
+  }
+  // (read where they are used, so that the uniform instantiations hold the instructions they held without the PAGED ones)
+  auto sl_q = [&] { if constexpr (PAGED) return q_len; else return p.sl_q; };
+  auto sl_kv = [&] { if constexpr (PAGED) return kv_len; else return p.sl_kv; };
+  const int off = sl_kv() - sl_q();
   const int q0 = qblk * WGR + w * (32 * RG);
-  const float* qb = p.q + ibs * p.step_q_bs + ihn * p.step_q_head_num;
+  const float* qb = p.q + ibs * p.step_q_bs + ihn * p.step_q_head_num;  // (PAGED: packed rows and the pools — the plan's batch steps are 0)
   const _Float16* kb = p.k + ibs * p.step_k_bs + ihkv * p.step_k_head_num;
   const _Float16* vb = p.v + ibs * p.step_v_bs + ihkv * p.step_v_head_num;
   float* db = p.dst + ibs * p.step_dst_bs + ihn * p.step_dst_head_num;
+  if constexpr (PAGED) qb += (long long)q_base * p.step_q_sl, db += (long long)q_base * p.step_dst_sl;
 
   // PAD: HS is the PADDED head size of this instantiation (64 / 128 / 256) and the call's own head size hs < HS a multiple of 8:
   // query dims, K / V chunks and output dims from hs on are zeros / never stored (head sizes 80, 96, 112, 160, 192 ... ride on the
@@ -311,7 +335,7 @@ __device__ __forceinline__ void attn_mfma2_body(const AttnParams& p, const int n
   float m_run[RG], l_run[RG];  // l_run: this lane's half of the row sum
 #pragma unroll
   for (int rg = 0; rg < RG; rg++) {
-    const float* qr = qb + (long long)min(q0 + 32 * rg + n, p.sl_q - 1) * p.step_q_sl + 8 * h;
+    const float* qr = qb + (long long)min(q0 + 32 * rg + n, sl_q() - 1) * p.step_q_sl + 8 * h;
 #pragma unroll
     for (int j = 0; j < NJ; j++)
 #pragma unroll
@@ -329,14 +353,14 @@ __device__ __forceinline__ void attn_mfma2_body(const AttnParams& p, const int n
     const int gh = ihn + p.alibi_head_off;
     slope = gh < p.alibi_log2_floor ? powf(p.alibi_m0, float(gh + 1)) : powf(p.alibi_m1, float(2 * (gh - p.alibi_log2_floor) + 1));
   }
-  const int q_last_wg = min(qblk * WGR + WGR - 1, p.sl_q - 1);
-  const int kv_end = causal ? min(p.sl_kv, q_last_wg + off + 1) : p.sl_kv;                     // workgroup-uniform
+  const int q_last_wg = min(qblk * WGR + WGR - 1, sl_q() - 1);
+  const int kv_end = causal ? min(sl_kv(), q_last_wg + off + 1) : sl_kv();                     // workgroup-uniform
   int visible[RG];                                                                             // mha_dense_wrapper.h:1440-1441
 #pragma unroll
-  for (int rg = 0; rg < RG; rg++) visible[rg] = min(p.sl_kv, causal ? min(q0 + 32 * rg + n, p.sl_q - 1) + off + 1 : p.sl_kv);
-  const int vis_first = min(p.sl_kv, causal ? q0 + off + 1 : p.sl_kv);                          // the wave's first row
-  const int vis_last = min(p.sl_kv, causal ? min(q0 + 32 * RG - 1, p.sl_q - 1) + off + 1 : p.sl_kv);  // the wave's last row
-  const bool wave_live = q0 < p.sl_q;
+  for (int rg = 0; rg < RG; rg++) visible[rg] = min(sl_kv(), causal ? min(q0 + 32 * rg + n, sl_q() - 1) + off + 1 : sl_kv());
+  const int vis_first = min(sl_kv(), causal ? q0 + off + 1 : sl_kv());                          // the wave's first row
+  const int vis_last = min(sl_kv(), causal ? min(q0 + 32 * RG - 1, sl_q() - 1) + off + 1 : sl_kv());  // the wave's last row
+  const bool wave_live = q0 < sl_q();
 
   // ---- tile staging: global -> registers -> LDS ----
   ahalf8_t kst[KU], vst[VU];
@@ -367,7 +391,39 @@ __device__ __forceinline__ void attn_mfma2_body(const AttnParams& p, const int n
 #pragma unroll
     for (int u = 0; u < VU; u++) vst[u] = ahalf8_t{0, 0, 0, 0, 0, 0, 0, 0};
   }
+  // PAGED: one table entry per wave and staging step u, for K and V alike — the rows a wave stages at step u, K's and V's, are the aligned group of
+  // 16 / KU rows from tile row u * (64 / KU) + w * (16 / KU) on; a page holds 16 keys or more and tiles start at multiples of 64, so the keys the
+  // group's rows clamp to (attn_prefill_tile_key) all lie in the page of the key its FIRST row clamps to.  Lane l of a wave fetches the entry of step
+  // l % KU into ONE register (a vector load: it retires with the K / V loads issued behind it, which park() waits for anyway — a scalar load would
+  // share its counter with the LDS reads of the tile's products and stall them); step u reads it from lane u.  idv holds the entries of the tile
+  // the NEXT fetch requests (kv_len >= 1 wherever a tile is fetched: nb > 0).
+  static_assert(!PAGED || (KU == VU && 256 / NCH == 4 * VRW), "K and V rows of a staging step: the same group of a wave");
+  int idv = 0;
+  const int grp_l = (l % KU) * (64 / KU) + w * (16 / KU);  // first tile row of the group whose entry this lane fetches
+  auto fetch_ids = [&](int pos0) {
+    if constexpr (PAGED) return pp.pg.table[(long long)ibs * pp.pg.table_stride + (attn_prefill_tile_key(pos0, grp_l, kv_len) >> pp.pg.block_shift)];
+    return 0;
+  };
+  auto fetch_paged = [&](int pos0) {
+    if constexpr (PAGED) {
+      const int idv_n = fetch_ids(pos0 + kA2KB);  // (clamped to the last live key: a valid entry also behind the last tile)
+#pragma unroll
+      for (int u = 0; u < KU; u++) {
+        const int id = __builtin_amdgcn_readlane(idv, u);
+        if (k_in) {
+          const long long cell = attn_page_at(pp.pg, id, attn_prefill_tile_key(pos0, krow[u], kv_len), p.step_k_sl);
+          kst[u] = cell >= 0 ? *reinterpret_cast<const ahalf8_t*>(kb + cell + kcol) : ahalf8_t{0, 0, 0, 0, 0, 0, 0, 0};
+        }
+        if (v_in) {
+          const long long cell = attn_page_at(pp.pg, id, attn_prefill_tile_key(pos0, vrow[u], kv_len), p.step_v_sl);
+          vst[u] = cell >= 0 ? *reinterpret_cast<const ahalf8_t*>(vb + cell + vcol) : ahalf8_t{0, 0, 0, 0, 0, 0, 0, 0};
+        }
+      }
+      idv = idv_n;
+    }
+  };
   auto fetch = [&](int pos0) {
+    if constexpr (PAGED) return fetch_paged(pos0);
     if (pos0 + kA2KB <= p.sl_kv) {  // workgroup-uniform
       if (k_in) {
 #pragma unroll
@@ -406,6 +462,7 @@ __device__ __forceinline__ void attn_mfma2_body(const AttnParams& p, const int n
 
   const int nb = (kv_end + kA2KB - 1) / kA2KB;
   if (nb > 0) {
+    idv = fetch_ids(0);
     fetch(0);
     park(0);
   }
@@ -531,7 +588,7 @@ __device__ __forceinline__ void attn_mfma2_body(const AttnParams& p, const int n
   l_run[rg] += __shfl_xor(l_run[rg], 32, 64);
   const float inv = l_run[rg] > 0.f ? p.out_scale / l_run[rg] : 0.f;
   const int row = q0 + 32 * rg + n;
-  if (row < p.sl_q) {
+  if (row < sl_q()) {
     float* dr = db + (long long)row * p.step_dst_sl;
 #pragma unroll
     for (int dt = 0; dt < NDT; dt++) {
@@ -816,6 +873,14 @@ __global__ __launch_bounds__(256) void attn_mfma2_hs256_kernel(const AttnParams 
   attn_mfma2_body<256, SB, PAD>(p, nqb, aligned_dst, xcd_map);
 }
 
+// the PAGED instantiations (ns_hip_attn_prefill_paged): the same register budgets
+template <int HS, bool SB, bool PAD>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_mfma2_paged_kernel(const AttnPrefillPagedParams pp, const int nqb, const int aligned_dst,
+                                                                                                    const int xcd_map) {
+  attn_mfma2_body<HS, SB, PAD, 1, true>(pp, nqb, aligned_dst, xcd_map);
+}
+// (no head-size-256 form: with the whole register file it still needs 116 .. 196 bytes of scratch per lane — the plan refuses head sizes above 128)
+
 // ---- launch of a plan (ns_attn_plan.cpp): pl.hs_pad, pl.sb and pl.pad are the template arguments -----------------------------------------
 hipError_t launch_attn_rows(const AttnPlan& pl, hipStream_t st) {
   const AttnParams& p = pl.sp.a;
@@ -834,6 +899,18 @@ hipError_t launch_attn_rows(const AttnPlan& pl, hipStream_t st) {
     constexpr bool SB = decltype(sb_c)::value, PAD = decltype(pad_c)::value;
     if (pl.hs_pad == 256) return go(kernel_c<attn_mfma2_hs256_kernel<SB, PAD>>{});
     return pl.hs_pad == 64 ? go(kernel_c<attn_mfma2_kernel<64, SB, PAD>>{}) : go(kernel_c<attn_mfma2_kernel<128, SB, PAD>>{});
+  };
+  if (pl.sb) return pl.pad ? by_hs(std::true_type{}, std::true_type{}) : by_hs(std::true_type{}, std::false_type{});
+  return pl.pad ? by_hs(std::false_type{}, std::true_type{}) : by_hs(std::false_type{}, std::false_type{});
+}
+hipError_t launch_attn_prefill_paged(const AttnPrefillPagedPlan& pl, hipStream_t st) {
+  auto go = [&](auto kern_c) {
+    return launch_lds<decltype(kern_c)::value>(int(pl.lds), pl.grid, pl.block, pl.lds, st, pl.pp, pl.nqb, pl.aligned, pl.xcd_map);
+  };
+  auto by_hs = [&](auto sb_c, auto pad_c) {
+    constexpr bool SB = decltype(sb_c)::value, PAD = decltype(pad_c)::value;
+    if (pl.hs_pad != 64 && pl.hs_pad != 128) return hipErrorInvalidValue;  // (no plan names another)
+    return pl.hs_pad == 64 ? go(kernel_c<attn_mfma2_paged_kernel<64, SB, PAD>>{}) : go(kernel_c<attn_mfma2_paged_kernel<128, SB, PAD>>{});
   };
   if (pl.sb) return pl.pad ? by_hs(std::true_type{}, std::true_type{}) : by_hs(std::true_type{}, std::false_type{});
   return pl.pad ? by_hs(std::false_type{}, std::true_type{}) : by_hs(std::false_type{}, std::false_type{});
