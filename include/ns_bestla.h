@@ -735,6 +735,36 @@ int ns_hip_kv_paged_store(const void* dKslab16, const void* dVslab16, long long 
 /* Process-wide counts of ns_hip_attn_decode_paged, the four slots of ns_hip_attn_rows_stats: [0] launches on the LDS-ring kernel, [1] on the register
  * kernel, [2] merge launches, [3] refused calls. */
 void ns_hip_attn_paged_stats(unsigned long long out[4]);
+/* ---- the same three entries over an FP8 (E4M3) paged cache ----
+ * THE FP8 POOL: the geometry above word for word (pool_blocks, block_keys 16 .. 256, block_step, the row and head strides, the device table), with
+ * two differences: an element is one BYTE, an OCP E4M3 code (e4m3fn: bias 7, largest value 448, 0x7f / 0xff NaN, no infinity), and every stride counts
+ * elements, which are bytes.  A cell's value is code * K_sc (K pool) or code * V_sc (V pool): one positive finite scale per pool and call, which the
+ * caller keeps constant for the life of a pool.  Refused beyond what the fp16 entries refuse of the cache's description: head_size, the row stride, the
+ * head stride or block_step not a multiple of 16, a pool base that is not 16-byte aligned, a scale that is not positive and finite.
+ *
+ * ns_hip_rope_qkv_append_paged_f8: ns_hip_rope_qkv_append_paged's arguments plus the two scales; the same rotation, Q rotated in place exactly as there.
+ * With h the fp16 value that entry would have written to a cell, the cell receives e4m3_rne(clamp(float(h) * inv, -448, 448)), inv = 1.0f / scale in
+ * fp32, round to nearest even with subnormals; NaN gives 0x7f.  Idle rows and out-of-range table ids as in the fp16 append.  One launch, capturable. */
+int ns_hip_rope_qkv_append_paged_f8(float* dQ, const float* dK, const float* dV, void* dKpool8, void* dVpool8, int rows, int heads, int heads_kv,
+                                    int head_size, const int* dPos, int pos_cap, int n_dims, int mode, float freq_base, float freq_scale, float ext_factor,
+                                    float attn_factor, const int* dBlockTable, int table_stride, int block_keys, int pool_blocks, long long block_step,
+                                    long long cache_step_sl, long long cache_step_head, float k_scale, float v_scale, void* stream);
+/* ns_hip_kv_paged_store_f8: ns_hip_kv_paged_store with an fp16 source slab and an FP8 pool: every element by the append's conversion rule, so a token
+ * holds the same byte whichever way it entered the pool.  This is how a prompt enters an FP8 pool (prefilled by the uniform entry on an fp16 slab, then
+ * stored).  16-byte reads and 8-byte writes where the slab's strides and bases allow, one element at a time where they do not. */
+int ns_hip_kv_paged_store_f8(const void* dKslab16, const void* dVslab16, long long slab_step_sl, long long slab_step_head, int pos0, int n, int heads_kv,
+                             int head_size, void* dKpool8, void* dVpool8, const int* dTableRow, int table_len, int block_keys, int pool_blocks,
+                             long long block_step, long long cache_step_sl, long long cache_step_head, float k_scale, float v_scale, void* stream);
+/* ns_hip_attn_decode_paged_f8: ns_hip_attn_decode_paged's signature and contract over FP8 pools (K / V of the block: the pool bases; K_sc / V_sc: the
+ * pools' scales, folded as ever — qk_scale = QK_scale * Q_sc * K_sc, out_scale = V_sc / dst_sc): sl_q = 1, sl_kv = table_stride * block_keys, dKvLens +
+ * bias, an idle slot gives a zero row, dst16, tmp, ALiBi with the head partition, the tanh cap, GQA of any group; a request with an out-of-range id
+ * gets an unspecified row and every other request's row is unchanged; no byte behind a live length reaches a result.  The plan is the fp16 entry's for
+ * the same shape and capacity; head sizes 48 .. 128 stream through LDS rings while the pool stays below 2^32 bytes, every other multiple of 16 up to 256
+ * and every larger pool go through registers.  ns_hip_attn_paged_f8_stats: [0] ring launches, [1] register launches, [2] merge launches, [3] refused
+ * calls (the launches also count under ns_hip_attn_stats by family). */
+int ns_hip_attn_decode_paged_f8(const attn_fp32_fp16_fp16_fp32_fwd_args_t* dparams, const int* dKvLens, int kv_len_bias, const int* dBlockTable,
+                                int table_stride, int block_keys, int pool_blocks, long long block_step, void* dst16, void* stream);
+void ns_hip_attn_paged_f8_stats(unsigned long long out[4]);
 /* ns_hip_attn_block_paged: RAGGED QUERY BLOCKS over the pools — every request brings its own number of query rows (a prompt chunk beside running
  * decodes, drafted tokens to verify, a follow-up turn), K / V of a kv head are read once per 64 (row, query head) slots and context range, not once per
  * row.  The argument block is ns_hip_attn_decode_paged's, read as: batch_size = the requests, sl_kv = a request's capacity (= table_stride *

@@ -471,6 +471,59 @@ int ns_hip_kv_paged_store(const void* dKslab16, const void* dVslab16, long long 
                                       cache_step_sl, cache_step_head, (hipStream_t)stream),
                 "kv paged store launch") ? 0 : -1;
 }
+// ---- the two writers of an FP8 paged cache (ns_attn.h, "an FP8 paged cache"): the fp16 entries' checks, the FP8 pool's own, the two scales ----
+static const char* f8_writer_refusal(const AttnPage& pg, int heads_kv, int head_size, long long c_sl, long long c_head, const void* kpool,
+                                     const void* vpool, float k_scale, float v_scale) {
+  if (const char* text = paged_cache_refusal(pg, heads_kv, head_size, c_sl, c_head)) return text;
+  for (const void* pool : {kpool, vpool})
+    if (const char* text = attn_f8_pool_refusal(head_size, c_sl, c_head, pg.block_step, pool)) return text;
+  if (!(k_scale > 0.f) || !(v_scale > 0.f) || std::isinf(k_scale) || std::isinf(v_scale)) return "k_scale and v_scale must be positive and finite";
+  return nullptr;
+}
+int ns_hip_rope_qkv_append_paged_f8(float* dQ, const float* dK, const float* dV, void* dKpool8, void* dVpool8, int rows, int heads, int heads_kv,
+                                    int head_size, const int* dPos, int pos_cap, int n_dims, int mode, float freq_base, float freq_scale, float ext_factor,
+                                    float attn_factor, const int* dBlockTable, int table_stride, int block_keys, int pool_blocks, long long block_step,
+                                    long long cache_step_sl, long long cache_step_head, float k_scale, float v_scale, void* stream) {
+  if (!have_device()) return -1;
+  if (!dQ || !dK || !dV || !dKpool8 || !dVpool8 || !dPos || rows < 0 || heads <= 0 || heads_kv <= 0 || head_size <= 0 || (head_size & 1) ||
+      n_dims <= 0 || (n_dims & 1) || n_dims > head_size || pos_cap < 0) {
+    set_error("rope_qkv_append_paged_f8: invalid argument");
+    return -1;
+  }
+  if ((mode & ~2) != 0 || ext_factor != 0.f || ((mode & 2) && head_size % n_dims != 0)) {
+    set_error("rope_qkv_append_paged_f8: only modes 0 and 2 (NeoX, head_size a multiple of n_dims) without YaRN extrapolation");
+    return -1;
+  }
+  const AttnPage pg = {dBlockTable, table_stride, attn_block_shift(block_keys), pool_blocks, block_step};
+  if (const char* text = f8_writer_refusal(pg, heads_kv, head_size, cache_step_sl, cache_step_head, dKpool8, dVpool8, k_scale, v_scale)) {
+    set_error(std::string("rope_qkv_append_paged_f8: ") + text);
+    return -1;
+  }
+  return hip_ok(launch_rope_qkv_append_paged_f8(dQ, dK, dV, dKpool8, dVpool8, rows, heads, heads_kv, head_size, dPos, pos_cap, n_dims, mode, freq_base,
+                                                freq_scale, attn_factor, pg, cache_step_sl, cache_step_head, k_scale, v_scale, (hipStream_t)stream),
+                "rope/kv-append (FP8 paged) launch") ? 0 : -1;
+}
+int ns_hip_kv_paged_store_f8(const void* dKslab16, const void* dVslab16, long long slab_step_sl, long long slab_step_head, int pos0, int n, int heads_kv,
+                             int head_size, void* dKpool8, void* dVpool8, const int* dTableRow, int table_len, int block_keys, int pool_blocks,
+                             long long block_step, long long cache_step_sl, long long cache_step_head, float k_scale, float v_scale, void* stream) {
+  if (!have_device()) return -1;
+  if (!dKslab16 || !dVslab16 || !dKpool8 || !dVpool8 || pos0 < 0 || n < 0 || heads_kv <= 0 || head_size <= 0) {
+    set_error("kv_paged_store_f8: invalid argument");
+    return -1;
+  }
+  const AttnPage pg = {dTableRow, table_len, attn_block_shift(block_keys), pool_blocks, block_step};
+  if (const char* text = f8_writer_refusal(pg, heads_kv, head_size, cache_step_sl, cache_step_head, dKpool8, dVpool8, k_scale, v_scale)) {
+    set_error(std::string("kv_paged_store_f8: ") + text);
+    return -1;
+  }
+  if ((long long)pos0 + n > ((long long)table_len << pg.block_shift)) {
+    set_error("kv_paged_store_f8: rows [pos0, pos0 + n) reach behind the request's capacity (table_len * block_keys)");
+    return -1;
+  }
+  return hip_ok(launch_kv_paged_store_f8(dKslab16, dVslab16, slab_step_sl, slab_step_head, pos0, n, heads_kv, head_size, dKpool8, dVpool8, pg,
+                                         cache_step_sl, cache_step_head, k_scale, v_scale, (hipStream_t)stream),
+                "kv paged store (FP8) launch") ? 0 : -1;
+}
 // device twins of bestla_device_elewise_f32 (NE_OP_SILU) and bestla_device_dup_f32 (ne_bestla.h:103-109)
 int ns_hip_silu_f32(const float* dSrc, float* dDst, size_t n, void* stream) {
   if (!have_device()) return -1;

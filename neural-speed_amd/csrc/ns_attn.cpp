@@ -182,6 +182,33 @@ static hipError_t launch_attn_decode_paged(const attn_fp32_fp16_fp16_fp32_fwd_ar
   return e;
 }
 
+// ns_hip_attn_decode_paged_f8: attn_decode_paged_f8_plan, scratch as launch_onerow_plan takes it, the E4M3 kernels (launch_attn_onerow_f8)
+static std::atomic<uint64_t> g_attn_paged_f8[4];  // ns_hip_attn_paged_f8_stats
+static hipError_t launch_attn_decode_paged_f8(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const int* lens, int bias, const AttnPage& page, hipStream_t st,
+                                              std::string* why, void* dst16) {
+  AttnKnobs kn = attn_knobs();
+  AttnPlan pl = attn_decode_paged_f8_plan(a, dst16, kn, lens, bias, page, why);
+  if (pl.path == AP_REFUSED) return hipErrorInvalidValue;
+  float* ws = nullptr;
+  if (pl.partial_bytes) {
+    ws = reinterpret_cast<float*>(a.tmp);
+    if (!ws) ws = static_cast<float*>(stream_scratch(st, pl.partial_bytes, SLOT_ATTN_PARTIALS));
+    if (!ws) {  // scratch allocation failed: planned again as one range, still correct
+      kn.no_partials = true;
+      pl = attn_decode_paged_f8_plan(a, dst16, kn, lens, bias, page, why);
+      if (pl.path == AP_REFUSED) return hipErrorInvalidValue;
+    }
+  }
+  uint32_t* tickets = pl.want_tickets ? static_cast<uint32_t*>(stream_scratch_zeroed(st, kAttnTicketCap * 4, SLOT_ATTN_TICKETS)) : nullptr;
+  const hipError_t e = launch_attn_onerow_f8(pl, ws, tickets, st);
+  if (e == hipSuccess) {
+    g_attn_launches[pl.path].fetch_add(1, std::memory_order_relaxed);
+    g_attn_paged_f8[pl.path == AP_RING ? 0 : 1].fetch_add(1, std::memory_order_relaxed);
+    if (pl.sp.nsplit > 1 && !tickets) g_attn_paged_f8[2].fetch_add(1, std::memory_order_relaxed);
+  }
+  return e;
+}
+
 // ns_hip_attn_block_paged: plan (attn_block_paged_plan), partials in the caller's `tmp` (ns_hip_attn_block_paged_workspace_size bytes) or the stream's
 // scratch, the PAGED instantiation of the block-split kernel and its merge.
 static std::atomic<uint64_t> g_attn_block_paged[4];  // ns_hip_attn_block_paged_stats
@@ -313,6 +340,24 @@ int ns_hip_attn_decode_paged(const attn_fp32_fp16_fp16_fp32_fwd_args_t* a, const
     return -1;
   }
   return 0;
+}
+
+int ns_hip_attn_decode_paged_f8(const attn_fp32_fp16_fp16_fp32_fwd_args_t* a, const int* dKvLens, int kv_len_bias, const int* dBlockTable, int table_stride,
+                                int block_keys, int pool_blocks, long long block_step, void* dst16, void* stream) {
+  std::string why;
+  const AttnPage page = {dBlockTable, table_stride, attn_block_shift(block_keys), pool_blocks, block_step};
+  const hipError_t e =
+      a ? launch_attn_decode_paged_f8(*a, dKvLens, kv_len_bias, page, static_cast<hipStream_t>(stream), &why, dst16) : hipErrorInvalidValue;
+  if (e != hipSuccess) {
+    g_attn_paged_f8[3].fetch_add(1, std::memory_order_relaxed);
+    set_error(why.empty() ? std::string("attention launch (FP8 paged cache): ") + (a ? hipGetErrorString(e) : "null arguments") : why);
+    return -1;
+  }
+  return 0;
+}
+
+void ns_hip_attn_paged_f8_stats(unsigned long long out[4]) {
+  for (int i = 0; i < 4; i++) out[i] = g_attn_paged_f8[i].load(std::memory_order_relaxed);
 }
 
 int ns_hip_attn_block_paged(const attn_fp32_fp16_fp16_fp32_fwd_args_t* a, const int* dQStart, const int* dKvLens, int kv_len_bias, const int* dBlockTable,

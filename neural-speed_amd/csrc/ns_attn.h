@@ -136,6 +136,32 @@ __host__ __device__ __forceinline__ bool attn_page_in32(const AttnPage& pg) {
   return ((unsigned long long)pg.pool_blocks * (unsigned long long)pg.block_step + 256ull) * 2ull < (1ull << 32);
 }
 
+// ---- an FP8 paged cache (ns_hip_attn_decode_paged_f8, ns_hip_rope_qkv_append_paged_f8, ns_hip_kv_paged_store_f8) ------------------------------------
+// The pools of the paged cache above with one BYTE per element, an OCP E4M3 code (e4m3fn: bias 7, largest value 448, 0x7f / 0xff NaN, no infinity);
+// every stride of the description counts elements, which are bytes.  A cell's value is code * K_sc (V_sc): one positive finite scale per pool.
+// The ring kernel's rule in BYTES (attn_stream8_kernel: one 32-bit descriptor over the pool, the offset pool_bytes standing for "no access").
+__host__ __device__ __forceinline__ bool attn_page_in32_f8(const AttnPage& pg) {
+  return (unsigned long long)pg.pool_blocks * (unsigned long long)pg.block_step + 256ull < (1ull << 32);
+}
+// THE conversion of the two writers: the code of x, round to nearest even, subnormals kept, |x| above 448 clamped to 448, NaN -> 0x7f.  Host and
+// device (tests/test_attn_paged_f8_plan.py walks every fp16 value through it).  The subnormal branch rounds by an fp32 addition: 2^14 has an ulp of
+// 2^-9, E4M3's subnormal step.
+__host__ __device__ __forceinline__ unsigned char e4m3_rne(float x) {
+  if (x != x) return 0x7f;
+  x = x < -448.f ? -448.f : (x > 448.f ? 448.f : x);
+  const uint32_t b = __builtin_bit_cast(uint32_t, x), sign = (b >> 24) & 0x80u, a = b & 0x7fffffffu;
+  if (a >= 0x3c800000u) return (unsigned char)(sign | (((a + 0x7ffffu + ((a >> 20) & 1u)) >> 20) - (120u << 3)));  // 2^-6 and above: 20 bits dropped
+#if defined(__HIP_DEVICE_COMPILE__)
+  const float r = __fadd_rn(__builtin_bit_cast(float, a), 16384.f);
+#else
+  const volatile float r = __builtin_bit_cast(float, a) + 16384.f;
+#endif
+  return (unsigned char)(sign | (__builtin_bit_cast(uint32_t, float(r)) - 0x46800000u));
+}
+// what a writer stores for the fp32 value y: through the fp16 value the fp16 entry would have written, so that append and store agree on a token
+__host__ __device__ __forceinline__ unsigned char e4m3_cell(float y, float inv) { return e4m3_rne(float((_Float16)y) * inv); }
+__host__ __device__ __forceinline__ unsigned char e4m3_cell(_Float16 h, float inv) { return e4m3_rne(float(h) * inv); }
+
 // ---- ragged query blocks over a paged cache (ns_hip_attn_block_paged; attn_block_split_kernel's PAGED instantiations, ns_attn_block.hip) ---------
 // Argument block: sp as the block-split kernel reads it, with a.sl_q = max_q (the most query rows of one request), a.sl_kv = a request's capacity,
 // kmove / kdelta = dKvLens / its bias (attn_live_kv<true>), nsplit / keys_per_split = the ranges laid out for the capacity, dyn_min_keys = the block
@@ -220,6 +246,7 @@ struct AttnPlan {
   bool rows = false;                 // one-row paths: one live length per batch entry (the ROWS instantiations; sp.kmove an array, sp.kdelta its bias)
   bool paged = false;                // ... over a paged cache (the PAGED instantiations; page: their AttnPage, sp.a.k / sp.a.v the pool bases)
   AttnPage page = {};
+  bool f8 = false;                   // ... whose pools hold E4M3 codes (attn_decode_paged_f8_plan only: attn_stream8_kernel / attn_split8_kernel)
   bool want_tickets = false;         // ranges merge inside the launch if the stream's ticket buffer can be had
   bool merge = false;                // attn_merge_kernel follows (also when tickets are wanted and cannot be had)
   size_t partial_bytes = 0;          // of sp.ws
@@ -231,6 +258,14 @@ bool attn_shape_ok(int head_num, int heads_kv, int head_size, int sl_q, int sl_k
 // own refusals and the 32-bit rule of the pool (attn_page_in32) in place of the slab's.
 AttnPlan attn_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst16, const AttnKnobs& knobs, const Affine& aff, std::string* why,
                    const AttnPage* page = nullptr);
+// The plan of ns_hip_attn_decode_paged_f8: the paged fp16 plan of the same shape and capacity (grid, head groups, ranges, dyn_* constants, partials,
+// merge, tickets) with the kernel family (f8) and the 32-bit rule in bytes (attn_page_in32_f8) in place of the fp16 ones, plus the FP8 pool's own
+// refusals.  A pure function (tests/test_attn_paged_f8_plan.py).  AP_RING: attn_stream8_kernel<G, lpk>, AP_SPLIT_REGS: attn_split8_kernel<G, dpl>.
+AttnPlan attn_decode_paged_f8_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst16, const AttnKnobs& knobs, const int* kv_lens,
+                                   int kv_len_bias, const AttnPage& page, std::string* why);
+// what the FP8 pool asks beyond the paged cache's description (the plan and the two writers): nullptr = in order.  A lane's 16-byte request must
+// stay inside a row.
+const char* attn_f8_pool_refusal(int head_size, long long step_sl, long long step_head, long long block_step, const void* pool);  // (one pool)
 // what bestla_fusion_attn_workspace_size answers: it knows neither strides nor alignment, so the most any plan of the shape can need
 size_t attn_ws_bytes(const AttnKnobs& knobs, int batch, int head_num, int heads_kv, int head_size, int sl_q, int sl_kv);
 
@@ -265,12 +300,13 @@ AttnPrefillPagedPlan attn_prefill_paged_plan(const attn_fp32_fp16_fp16_fp32_fwd_
 
 // ---- launches of a plan ----------------------------------------------------------------------------------------------------------------------
 hipError_t launch_attn_onerow(const AttnPlan& pl, float* ws, uint32_t* tickets, hipStream_t st);  // ns_attn_decode.hip: AP_GENERIC, AP_SPLIT_REGS, AP_RING (+ merge)
+hipError_t launch_attn_onerow_f8(const AttnPlan& pl, float* ws, uint32_t* tickets, hipStream_t st);  // ns_attn_decode_f8.hip: a plan with f8 set (+ merge)
 hipError_t launch_attn_rows(const AttnPlan& pl, hipStream_t st);                                  // ns_attn_prefill.hip: AP_ROWS64, AP_ROWS128, AP_PIPELINED
 hipError_t launch_attn_block_split(const AttnPlan& pl, float* ws, hipStream_t st);                // ns_attn_block.hip: AP_BLOCK_SPLIT (+ merge)
 hipError_t launch_attn_block_paged(const AttnBlockPagedPlan& pl, float* ws, hipStream_t st);     // ns_attn_block.hip: the PAGED instantiation + its merge
 hipError_t launch_attn_prefill_paged(const AttnPrefillPagedPlan& pl, hipStream_t st);             // ns_attn_prefill.hip: the PAGED instantiations of the 128-row kernel
 hipError_t launch_attn_merge(const AttnSplitParams& sp, unsigned batch, hipStream_t st, bool rows = false);  // ns_attn_decode.hip: attn_merge_kernel over sp.ws
-// touch_attn_module (ns_common.h) makes the runtime load all four code objects
+// touch_attn_module (ns_common.h) makes the runtime load every one of these code objects
 inline void touch_kernel(const void* kernel) {
   hipFuncAttributes fa;
   (void)hipFuncGetAttributes(&fa, kernel);
@@ -279,6 +315,7 @@ inline void touch_kernel(const void* kernel) {
 void touch_attn_rows_module();  // ns_attn_prefill.hip
 void touch_attn_block_module(); // ns_attn_block.hip
 void touch_kvcache_module();    // ns_kvcache.hip
+void touch_attn_f8_module();    // ns_attn_decode_f8.hip
 // Is a HIP device visible?  who != nullptr: if not, the error is set and "Err: invalid parameters (<who>: no HIP device visible ...)" goes to stderr.
 bool attn_device_visible(const char* who);
 

@@ -443,4 +443,53 @@ AttnPrefillPagedPlan attn_prefill_paged_plan(const attn_fp32_fp16_fp16_fp32_fwd_
   return pl;
 }
 
+// ---- decode over an FP8 paged cache (ns_hip_attn_decode_paged_f8) ------------------------------------------------------------------------------------
+const char* attn_f8_pool_refusal(int head_size, long long step_sl, long long step_head, long long block_step, const void* pool) {
+  if (head_size < 16 || head_size % 16 != 0) return "FP8 paged cache: head_size must be a multiple of 16";
+  if (step_sl % 16 != 0 || step_head % 16 != 0) return "FP8 paged cache: the row and head strides must be multiples of 16 elements (bytes)";
+  if (block_step % 16 != 0) return "FP8 paged cache: block_step must be a multiple of 16 elements (bytes)";
+  if ((reinterpret_cast<uintptr_t>(pool) & 15) != 0) return "FP8 paged cache: the pool bases must be 16-byte aligned";
+  return nullptr;
+}
+// The fp16 plan is asked about a pool of ONE block: the paged cache's own refusals (attn_page_refusal) are made here first, on the real pool, and
+// the fp16 32-bit rule — twice too strict for bytes — then cannot decide the family (it can only for a single block of 2^31 elements or
+// more, which stays with the register form).  The byte rule decides instead: a pool the ring form's descriptor cannot span is planned again as the
+// fp16 entry plans a pool it cannot span, through registers with their own range rule.
+AttnPlan attn_decode_paged_f8_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst16, const AttnKnobs& kn, const int* kv_lens,
+                                   int kv_len_bias, const AttnPage& page, std::string* why) {
+  AttnPlan none;
+  memset(&none.sp, 0, sizeof(none.sp));
+  auto refuse = [&](const char* text) {
+    *why = text;
+    return none;
+  };
+  if (a.sl_q != 1) return refuse("attention, FP8 paged cache: one query row per request (sl_q must be 1)");
+  if (!kv_lens) return refuse("attention, FP8 paged cache: dKvLens is null");
+  if (a.sl_kv < 1) return refuse("attention, FP8 paged cache: sl_kv is the capacity of a request (at least 1 key)");
+  if (!(a.K_sc > 0.f) || !(a.V_sc > 0.f) || std::isinf(a.K_sc) || std::isinf(a.V_sc))
+    return refuse("attention, FP8 paged cache: K_sc and V_sc, the pools' scales, must be positive and finite");
+  if (a.head_size > 256) return refuse("attention: head_size must be 1..256");
+  if (a.step_k_head_size != 1 || a.step_v_head_size != 1) return refuse("attention, FP8 paged cache: K / V rows must be contiguous in the head dimension");
+  if (const char* text = attn_f8_pool_refusal(a.head_size, a.step_k_sl, a.step_k_head_num, page.block_step, a.K)) return refuse(text);
+  if (const char* text = attn_f8_pool_refusal(a.head_size, a.step_v_sl, a.step_v_head_num, page.block_step, a.V)) return refuse(text);
+  if (const char* text = attn_page_refusal(a, page)) return refuse(text);  // (of the REAL pool: attn_plan below sees a pool of one block)
+  AttnPage one = page;
+  one.pool_blocks = 1;
+  Affine aff;
+  aff.k = kv_lens, aff.delta = 1, aff.cap = a.sl_kv, aff.inlaunch = 0, aff.rows = 1, aff.bias = kv_len_bias;
+  AttnPlan pl = attn_plan(a, dst16, kn, aff, why, &one);
+  if (pl.path == AP_RING && !attn_page_in32_f8(page)) {
+    AttnKnobs regs = kn;
+    regs.attn_stream = 0;
+    pl = attn_plan(a, dst16, regs, aff, why, &one);
+  }
+  if (pl.path != AP_RING && pl.path != AP_SPLIT_REGS) {
+    if (pl.path != AP_REFUSED || why->empty()) return refuse("attention, FP8 paged cache: no split kernel takes this call");
+    return none;
+  }
+  pl.page = page;
+  pl.f8 = true;
+  return pl;
+}
+
 }  // namespace ns

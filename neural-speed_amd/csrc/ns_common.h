@@ -456,6 +456,12 @@ struct AttnPage;
 hipError_t launch_rope_qkv_append_paged(float* q, const float* k, const float* v, void* kc, void* vc, int rows, int heads, int heads_kv, int head_size,
                                         const int* pos, int pos_cap, int n_dims, int mode, float freq_base, float freq_scale, float attn_factor,
                                         const AttnPage& pg, long long c_sl, long long c_head, hipStream_t st);
+hipError_t launch_rope_qkv_append_paged_f8(float* q, const float* k, const float* v, void* kc, void* vc, int rows, int heads, int heads_kv, int head_size,
+                                           const int* pos, int pos_cap, int n_dims, int mode, float freq_base, float freq_scale, float attn_factor,
+                                           const AttnPage& pg, long long c_sl, long long c_head, float k_scale, float v_scale, hipStream_t st);
+hipError_t launch_kv_paged_store_f8(const void* ks, const void* vs, long long s_sl, long long s_head, int pos0, int n, int heads_kv, int head_size,
+                                    void* kc, void* vc, const AttnPage& pg, long long c_sl, long long c_head, float k_scale, float v_scale,
+                                    hipStream_t st);
 hipError_t launch_rope_qkv_append_paged_seq(float* q, const float* k, const float* v, void* kc, void* vc, int rows, int heads, int heads_kv, int head_size,
                                             const int* pos, int pos_cap, const int* row_req, int requests, int n_dims, int mode, float freq_base,
                                             float freq_scale, float attn_factor, const AttnPage& pg, long long c_sl, long long c_head, hipStream_t st);

@@ -906,10 +906,23 @@ __global__ void rope_qkv_append_kernel(float* __restrict__ q, const float* __res
 // whose threads leave before they have read or written anything.
 // item `it` of one row (a rotated pair of Q or K, or an element of V): q / k / v point at the row, kc / vc at its cache cell (head 0).  Shared by the
 // slab form and the paged form below, so that the two hold the same bits.
+// CELL: what a cache cell receives for the fp32 value y — the fp16 value (every fp16 cache), or its E4M3 code under the pool's scale (CellF8)
+struct CellF16 {
+  typedef _Float16 type;
+  __device__ __forceinline__ _Float16 k(float y) const { return (_Float16)y; }
+  __device__ __forceinline__ _Float16 v(float y) const { return (_Float16)y; }
+};
+struct CellF8 {  // ns_hip_rope_qkv_append_paged_f8: e4m3_cell (ns_attn.h) through the fp16 value the fp16 append writes; inv = 1 / scale
+  typedef unsigned char type;
+  float k_inv, v_inv;
+  __device__ __forceinline__ unsigned char k(float y) const { return e4m3_cell(y, k_inv); }
+  __device__ __forceinline__ unsigned char v(float y) const { return e4m3_cell(y, v_inv); }
+};
+template <class CELL = CellF16>
 __device__ __forceinline__ void rope_append_row_item(float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
-                                                     _Float16* __restrict__ kc, _Float16* __restrict__ vc, size_t it, size_t nq, size_t nk, size_t npairs,
-                                                     int n_past, int head_size, int n_dims, int neox, float theta_scale, float freq_scale,
-                                                     float attn_factor, long long c_head) {
+                                                     typename CELL::type* __restrict__ kc, typename CELL::type* __restrict__ vc, size_t it, size_t nq,
+                                                     size_t nk, size_t npairs, int n_past, int head_size, int n_dims, int neox, float theta_scale,
+                                                     float freq_scale, float attn_factor, long long c_head, const CELL cell = CELL{}) {
   if (it < nq + nk) {
     const bool is_k = it >= nq;
     const size_t g = is_k ? it - nq : it;
@@ -933,16 +946,16 @@ __device__ __forceinline__ void rope_append_row_item(float* __restrict__ q, cons
     const float x0 = x[ia], x1 = x[ib];
     const float y0 = __fsub_rn(__fmul_rn(x0, c), __fmul_rn(x1, s)), y1 = __fadd_rn(__fmul_rn(x0, s), __fmul_rn(x1, c));
     if (is_k) {
-      _Float16* d = kc + (long long)ih * c_head;
-      d[ia] = (_Float16)y0;
-      d[ib] = (_Float16)y1;
+      typename CELL::type* d = kc + (long long)ih * c_head;
+      d[ia] = cell.k(y0);
+      d[ib] = cell.k(y1);
     } else {
       q[ih * head_size + ia] = y0;
       q[ih * head_size + ib] = y1;
     }
   } else {
     const size_t g = it - nq - nk;
-    vc[(long long)(g / head_size) * c_head + (long long)(g % head_size)] = (_Float16)v[g];
+    vc[(long long)(g / head_size) * c_head + (long long)(g % head_size)] = cell.v(v[g]);
   }
 }
 __global__ void rope_qkv_append_rows_kernel(float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
@@ -977,6 +990,25 @@ __global__ void rope_qkv_append_paged_kernel(float* __restrict__ q, const float*
   if (cell < 0) return;
   q += r * heads * head_size, k += r * heads_kv * head_size, v += r * heads_kv * head_size;
   rope_append_row_item(q, k, v, kc + cell, vc + cell, it, nq, nk, npairs, n_past, head_size, n_dims, neox, theta_scale, freq_scale, attn_factor, c_head);
+}
+// ... over an FP8 paged cache (ns_hip_rope_qkv_append_paged_f8): the kernel above with byte cells — the same rotation, a cell receives the E4M3 code
+// of the fp16 value that kernel writes (CellF8)
+__global__ void rope_qkv_append_paged_f8_kernel(float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
+                                                unsigned char* __restrict__ kc, unsigned char* __restrict__ vc, int rows, int heads, int heads_kv,
+                                                int head_size, const int* __restrict__ pos, int pos_cap, int n_dims, int neox, float theta_scale,
+                                                float freq_scale, float attn_factor, AttnPage pg, long long c_sl, long long c_head, CellF8 cell) {
+  const size_t npairs = neox ? size_t(head_size / n_dims) * (n_dims / 2) : size_t(head_size / 2);
+  const size_t nq = size_t(heads) * npairs, nk = size_t(heads_kv) * npairs, nv = size_t(heads_kv) * head_size;
+  const size_t gid = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (gid >= size_t(rows) * (nq + nk + nv)) return;
+  const size_t r = gid / (nq + nk + nv), it = gid % (nq + nk + nv);
+  const int n_past = pos[r];
+  if (n_past < 0 || n_past >= pos_cap) return;
+  const long long at = attn_page_cell(pg, int(r), n_past, c_sl);
+  if (at < 0) return;
+  q += r * heads * head_size, k += r * heads_kv * head_size, v += r * heads_kv * head_size;
+  rope_append_row_item<CellF8>(q, k, v, kc + at, vc + at, it, nq, nk, npairs, n_past, head_size, n_dims, neox, theta_scale, freq_scale, attn_factor,
+                               c_head, cell);
 }
 // ... with a row -> request map (ns_hip_rope_qkv_append_paged_seq): row r is a row of request row_req[r] and goes through THAT request's table row, so
 // one request may bring several rows (a prompt chunk, drafted tokens).  Idle as well: a request id outside [0, requests).
@@ -1020,6 +1052,38 @@ __global__ void kv_paged_store_kernel(const _Float16* __restrict__ ks, const _Fl
   } else {
     kc[dst] = ks[src];
     vc[dst] = vs[src];
+  }
+}
+// ns_hip_kv_paged_store_f8: the same rows of an fp16 slab into the pages of an FP8 pool, each element as e4m3_cell gives it — the byte the FP8 append
+// gives the same token.  VEC 8: 16-byte reads and 8-byte writes (the pool's side is always aligned: attn_f8_pool_refusal); 1: any slab.
+template <int VEC>
+__global__ void kv_paged_store_f8_kernel(const _Float16* __restrict__ ks, const _Float16* __restrict__ vs, long long s_sl, long long s_head, int pos0,
+                                         int n, int heads_kv, int head_size, unsigned char* __restrict__ kc, unsigned char* __restrict__ vc, AttnPage pg,
+                                         long long c_sl, long long c_head, float k_inv, float v_inv) {
+  const size_t per_row = size_t(heads_kv) * (head_size / VEC);
+  const size_t gid = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (gid >= size_t(n) * per_row) return;
+  const int pos = pos0 + int(gid / per_row);
+  const size_t x = gid % per_row;
+  const int ih = int(x / (head_size / VEC)), e = int(x % (head_size / VEC)) * VEC;
+  const long long cell = attn_page_cell(pg, 0, pos, c_sl);
+  if (cell < 0) return;
+  const long long src = (long long)pos * s_sl + (long long)ih * s_head + e, dst = cell + (long long)ih * c_head + e;
+  if constexpr (VEC == 8) {
+    typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
+    typedef uint32_t u2_t __attribute__((ext_vector_type(2)));
+    const half8_t hk = *reinterpret_cast<const half8_t*>(ks + src), hv = *reinterpret_cast<const half8_t*>(vs + src);
+    u2_t ck = {0u, 0u}, cv = {0u, 0u};
+#pragma unroll
+    for (int c = 0; c < 8; c++) {
+      ck[c / 4] |= uint32_t(e4m3_cell(hk[c], k_inv)) << (8 * (c % 4));
+      cv[c / 4] |= uint32_t(e4m3_cell(hv[c], v_inv)) << (8 * (c % 4));
+    }
+    *reinterpret_cast<u2_t*>(kc + dst) = ck;
+    *reinterpret_cast<u2_t*>(vc + dst) = cv;
+  } else {
+    kc[dst] = e4m3_cell(ks[src], k_inv);
+    vc[dst] = e4m3_cell(vs[src], v_inv);
   }
 }
 // (cos, sin) * attn_factor of the mode-0 pairs of positions n_past .. n_past + m - 1: the angle arithmetic of
@@ -1189,6 +1253,38 @@ hipError_t launch_rope_qkv_append_paged(float* q, const float* k, const float* v
   hipLaunchKernelGGL(rope_qkv_append_paged_kernel, grid1d(total, 256), dim3(256), 0, st, q, k, v, static_cast<_Float16*>(kc), static_cast<_Float16*>(vc),
                      rows, heads, heads_kv, head_size, pos, pos_cap, n_dims, neox ? 1 : 0, powf(freq_base, -2.0f / n_dims), freq_scale, attn_factor, pg,
                      c_sl, c_head);
+  return hipGetLastError();
+}
+hipError_t launch_rope_qkv_append_paged_f8(float* q, const float* k, const float* v, void* kc, void* vc, int rows, int heads, int heads_kv, int head_size,
+                                           const int* pos, int pos_cap, int n_dims, int mode, float freq_base, float freq_scale, float attn_factor,
+                                           const AttnPage& pg, long long c_sl, long long c_head, float k_scale, float v_scale, hipStream_t st) {
+  const bool neox = (mode & 2) != 0;
+  const size_t npairs = neox ? size_t(head_size / n_dims) * (n_dims / 2) : size_t(head_size / 2);
+  const size_t total = size_t(rows) * ((heads + heads_kv) * npairs + size_t(heads_kv) * head_size);
+  if (total == 0) return hipSuccess;
+  const CellF8 cell = {1.0f / k_scale, 1.0f / v_scale};  // (the reciprocals: once, here, in fp32)
+  hipLaunchKernelGGL(rope_qkv_append_paged_f8_kernel, grid1d(total, 256), dim3(256), 0, st, q, k, v, static_cast<unsigned char*>(kc),
+                     static_cast<unsigned char*>(vc), rows, heads, heads_kv, head_size, pos, pos_cap, n_dims, neox ? 1 : 0, powf(freq_base, -2.0f / n_dims),
+                     freq_scale, attn_factor, pg, c_sl, c_head, cell);
+  return hipGetLastError();
+}
+hipError_t launch_kv_paged_store_f8(const void* ks, const void* vs, long long s_sl, long long s_head, int pos0, int n, int heads_kv, int head_size,
+                                    void* kc, void* vc, const AttnPage& pg, long long c_sl, long long c_head, float k_scale, float v_scale,
+                                    hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  const auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  const bool vec = s_sl % 8 == 0 && s_head % 8 == 0 && al16(ks) && al16(vs);  // the slab decides; the pool's side is aligned whatever the call
+  const size_t total = size_t(n) * heads_kv * (vec ? head_size / 8 : head_size);
+  const float k_inv = 1.0f / k_scale, v_inv = 1.0f / v_scale;
+  if (vec) {
+    hipLaunchKernelGGL(kv_paged_store_f8_kernel<8>, grid1d(total, 256), dim3(256), 0, st, static_cast<const _Float16*>(ks),
+                       static_cast<const _Float16*>(vs), s_sl, s_head, pos0, n, heads_kv, head_size, static_cast<unsigned char*>(kc),
+                       static_cast<unsigned char*>(vc), pg, c_sl, c_head, k_inv, v_inv);
+  } else {
+    hipLaunchKernelGGL(kv_paged_store_f8_kernel<1>, grid1d(total, 256), dim3(256), 0, st, static_cast<const _Float16*>(ks),
+                       static_cast<const _Float16*>(vs), s_sl, s_head, pos0, n, heads_kv, head_size, static_cast<unsigned char*>(kc),
+                       static_cast<unsigned char*>(vc), pg, c_sl, c_head, k_inv, v_inv);
+  }
   return hipGetLastError();
 }
 hipError_t launch_rope_qkv_append_paged_seq(float* q, const float* k, const float* v, void* kc, void* vc, int rows, int heads, int heads_kv, int head_size,
