@@ -789,6 +789,28 @@ size_t ns_hip_attn_block_paged_workspace_size(int batch, int head_num, int heads
 /* Process-wide counts of ns_hip_attn_block_paged: [0] launches of the head-size-64 kernel, [1] of the head-size-128 kernel, [2] merge launches,
  * [3] refused calls. */
 void ns_hip_attn_block_paged_stats(unsigned long long out[4]);
+/* ---- ragged query blocks over an FP8 (E4M3) paged cache: with these two an FP8 pool takes prompt chunks, drafted tokens and mixed steps itself ----
+ * ns_hip_attn_block_paged_f8: ns_hip_attn_block_paged's signature and, word for word, its contract (packed Q / dst / dst16 through dQStart, dKvLens +
+ * bias, max_q, the causal rule, zero rows, idle requests, the table-entry rules, tmp of ns_hip_attn_block_paged_workspace_size bytes or the stream's
+ * scratch, two launches, capturable) over THE FP8 POOL described above: K / V of the block are the pool bases, every stride counts bytes, K_sc / V_sc are
+ * the pools' scales, folded as ever (qk_scale = QK_scale * Q_sc * K_sc, out_scale = V_sc / dst_sc).  The plan (grid, ranges, partials, merge) is the
+ * fp16 entry's for the same shape.  The codes are decoded exactly to fp16 and multiplied as fp16 matrix-core operands, Q is not quantised: the output
+ * is what ns_hip_attn_block_paged gives over fp16 pools holding the same values, up to the order of fp32 sums.  No byte behind kv_len_b reaches a result.
+ * Refused (-1, ns_hip_last_error set, nothing written): what ns_hip_attn_block_paged refuses, and what the FP8 pool adds (head_size, the row stride,
+ * the head stride or block_step not a multiple of 16, a pool base that is not 16-byte aligned, a scale that is not positive and finite).
+ * ns_hip_attn_block_paged_f8_stats: [0] launches of the head-size-64 kernel, [1] of the head-size-128 kernel, [2] merge launches, [3] refused calls
+ * (the launches also count under ns_hip_attn_stats by family). */
+int ns_hip_attn_block_paged_f8(const attn_fp32_fp16_fp16_fp32_fwd_args_t* dparams, const int* dQStart, const int* dKvLens, int kv_len_bias,
+                               const int* dBlockTable, int table_stride, int block_keys, int pool_blocks, long long block_step, void* dst16, void* stream);
+void ns_hip_attn_block_paged_f8_stats(unsigned long long out[4]);
+/* ns_hip_rope_qkv_append_paged_seq_f8: ns_hip_rope_qkv_append_paged_seq's arguments plus the two scales, over FP8 pools: the row -> request map and the
+ * idle rules of that entry, the rotation and the conversion rule of ns_hip_rope_qkv_append_paged_f8 — a row holds the byte that entry gives it when row
+ * r's table row is a copy of request dRowReq[r]'s, and Q holds the same bits.  One launch, capturable; refusals: the seq append's and the FP8 append's. */
+int ns_hip_rope_qkv_append_paged_seq_f8(float* dQ, const float* dK, const float* dV, void* dKpool8, void* dVpool8, int rows, int heads, int heads_kv,
+                                        int head_size, const int* dPos, int pos_cap, int n_dims, int mode, float freq_base, float freq_scale,
+                                        float ext_factor, float attn_factor, const int* dRowReq, int requests, const int* dBlockTable, int table_stride,
+                                        int block_keys, int pool_blocks, long long block_step, long long cache_step_sl, long long cache_step_head,
+                                        float k_scale, float v_scale, void* stream);
 /* ns_hip_attn_prefill_paged: PROMPT-SIZED QUERY BLOCKS over the pools — ns_hip_attn_block_paged's arguments and, word for word, its contract (batch_size
  * = the requests, sl_kv = the capacity = table_stride * block_keys, sl_q = max_q >= 1; Q, dst and dst16 packed through dQStart[batch_size + 1]; q_len_b,
  * kv_len_b and the causal rule as there; a row that sees no key is zeros, a request without rows writes nothing, rows no request names are not touched;

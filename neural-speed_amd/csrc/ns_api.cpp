@@ -503,6 +503,31 @@ int ns_hip_rope_qkv_append_paged_f8(float* dQ, const float* dK, const float* dV,
                                                 freq_scale, attn_factor, pg, cache_step_sl, cache_step_head, k_scale, v_scale, (hipStream_t)stream),
                 "rope/kv-append (FP8 paged) launch") ? 0 : -1;
 }
+int ns_hip_rope_qkv_append_paged_seq_f8(float* dQ, const float* dK, const float* dV, void* dKpool8, void* dVpool8, int rows, int heads, int heads_kv,
+                                        int head_size, const int* dPos, int pos_cap, int n_dims, int mode, float freq_base, float freq_scale,
+                                        float ext_factor, float attn_factor, const int* dRowReq, int requests, const int* dBlockTable, int table_stride,
+                                        int block_keys, int pool_blocks, long long block_step, long long cache_step_sl, long long cache_step_head,
+                                        float k_scale, float v_scale, void* stream) {
+  if (!have_device()) return -1;
+  if (!dQ || !dK || !dV || !dKpool8 || !dVpool8 || !dPos || !dRowReq || requests < 0 || rows < 0 || heads <= 0 || heads_kv <= 0 || head_size <= 0 ||
+      (head_size & 1) || n_dims <= 0 || (n_dims & 1) || n_dims > head_size || pos_cap < 0) {
+    set_error("rope_qkv_append_paged_seq_f8: invalid argument");
+    return -1;
+  }
+  if ((mode & ~2) != 0 || ext_factor != 0.f || ((mode & 2) && head_size % n_dims != 0)) {
+    set_error("rope_qkv_append_paged_seq_f8: only modes 0 and 2 (NeoX, head_size a multiple of n_dims) without YaRN extrapolation");
+    return -1;
+  }
+  const AttnPage pg = {dBlockTable, table_stride, attn_block_shift(block_keys), pool_blocks, block_step};
+  if (const char* text = f8_writer_refusal(pg, heads_kv, head_size, cache_step_sl, cache_step_head, dKpool8, dVpool8, k_scale, v_scale)) {
+    set_error(std::string("rope_qkv_append_paged_seq_f8: ") + text);
+    return -1;
+  }
+  return hip_ok(launch_rope_qkv_append_paged_seq_f8(dQ, dK, dV, dKpool8, dVpool8, rows, heads, heads_kv, head_size, dPos, pos_cap, dRowReq, requests, n_dims,
+                                                    mode, freq_base, freq_scale, attn_factor, pg, cache_step_sl, cache_step_head, k_scale, v_scale,
+                                                    (hipStream_t)stream),
+                "rope/kv-append (FP8 paged, row -> request map) launch") ? 0 : -1;
+}
 int ns_hip_kv_paged_store_f8(const void* dKslab16, const void* dVslab16, long long slab_step_sl, long long slab_step_head, int pos0, int n, int heads_kv,
                              int head_size, void* dKpool8, void* dVpool8, const int* dTableRow, int table_len, int block_keys, int pool_blocks,
                              long long block_step, long long cache_step_sl, long long cache_step_head, float k_scale, float v_scale, void* stream) {

@@ -231,6 +231,27 @@ static hipError_t launch_attn_block_paged_call(const attn_fp32_fp16_fp16_fp32_fw
   return e;
 }
 
+// ns_hip_attn_block_paged_f8: the same over FP8 pools — attn_block_paged_f8_plan, the same partials, attn_block_split8_kernel and the same merge
+static std::atomic<uint64_t> g_attn_block_paged_f8[4];  // ns_hip_attn_block_paged_f8_stats
+static hipError_t launch_attn_block_paged_f8_call(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const int* q_start, const int* lens, int bias,
+                                                  const AttnPage& page, hipStream_t st, std::string* why, void* dst16) {
+  const AttnBlockPagedPlan pl = attn_block_paged_f8_plan(a, dst16, attn_knobs(), page, q_start, lens, bias, why);
+  if (!pl.ok) return hipErrorInvalidValue;
+  float* ws = reinterpret_cast<float*>(a.tmp);
+  if (!ws) ws = static_cast<float*>(stream_scratch(st, pl.partial_bytes, SLOT_ATTN_PARTIALS));
+  if (!ws) {
+    *why = "attention, query blocks over an FP8 paged cache: no memory for the partials (give tmp, or make one eager call before a capture)";
+    return hipErrorOutOfMemory;
+  }
+  const hipError_t e = launch_attn_block_paged_f8(pl, ws, st);
+  if (e == hipSuccess) {
+    g_attn_launches[AP_BLOCK_SPLIT].fetch_add(1, std::memory_order_relaxed);
+    g_attn_block_paged_f8[pl.hs_pad == 64 ? 0 : 1].fetch_add(1, std::memory_order_relaxed);
+    g_attn_block_paged_f8[2].fetch_add(1, std::memory_order_relaxed);
+  }
+  return e;
+}
+
 // ns_hip_attn_prefill_paged: plan (attn_prefill_paged_plan) and ONE launch of the 128-row kernel's PAGED instantiation: no partials, no scratch
 static std::atomic<uint64_t> g_attn_prefill_paged[6];  // ns_hip_attn_prefill_paged_stats
 static hipError_t launch_attn_prefill_paged_call(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const int* q_start, const int* lens, int bias,
@@ -372,6 +393,24 @@ int ns_hip_attn_block_paged(const attn_fp32_fp16_fp16_fp32_fwd_args_t* a, const 
     return -1;
   }
   return 0;
+}
+
+int ns_hip_attn_block_paged_f8(const attn_fp32_fp16_fp16_fp32_fwd_args_t* a, const int* dQStart, const int* dKvLens, int kv_len_bias, const int* dBlockTable,
+                               int table_stride, int block_keys, int pool_blocks, long long block_step, void* dst16, void* stream) {
+  std::string why;
+  const AttnPage page = {dBlockTable, table_stride, attn_block_shift(block_keys), pool_blocks, block_step};
+  const hipError_t e =
+      a ? launch_attn_block_paged_f8_call(*a, dQStart, dKvLens, kv_len_bias, page, static_cast<hipStream_t>(stream), &why, dst16) : hipErrorInvalidValue;
+  if (e != hipSuccess) {
+    g_attn_block_paged_f8[3].fetch_add(1, std::memory_order_relaxed);
+    set_error(why.empty() ? std::string("attention launch (query blocks over an FP8 paged cache): ") + (a ? hipGetErrorString(e) : "null arguments") : why);
+    return -1;
+  }
+  return 0;
+}
+
+void ns_hip_attn_block_paged_f8_stats(unsigned long long out[4]) {
+  for (int i = 0; i < 4; i++) out[i] = g_attn_block_paged_f8[i].load(std::memory_order_relaxed);
 }
 
 int ns_hip_attn_prefill_paged(const attn_fp32_fp16_fp16_fp32_fwd_args_t* a, const int* dQStart, const int* dKvLens, int kv_len_bias, const int* dBlockTable,

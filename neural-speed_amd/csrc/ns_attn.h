@@ -172,6 +172,9 @@ struct AttnBlockPagedParams {
   AttnPage pg;
   const int* q_start;
 };
+// the block-split kernels' geometry (attn_block_split_kernel, ns_attn_block.hip; attn_block_split8_kernel, ns_attn_block_f8.hip)
+constexpr int kBlkKB = 64;            // kv positions per block
+constexpr int kBlkVStr = kBlkKB + 4;  // halves per V^T row in LDS: keeps the 8-byte reads aligned, skews banks
 // Keys per range and live ranges of a request with kv_len live keys, under a layout of nsplit ranges of kps_laid keys (a multiple of 64).  THE live
 // rule of that entry: the range workgroups and the merge both go through it, tests/test_attn_block_paged_plan.py walks every live length through it.
 // The ranges [i * kps, min((i + 1) * kps, kv_len)), i < live, tile [0, kv_len); kps is a multiple of 64 and live <= nsplit.
@@ -278,9 +281,15 @@ struct AttnBlockPagedPlan {
   AttnBlockPagedParams pp;
   dim3 grid, block, merge_grid;  // (slot blocks of max_q rows * kv heads, nsplit, requests) x 256; (heads, max_q, requests) x 128
   size_t partial_bytes = 0;
+  bool f8 = false;               // the pools hold E4M3 codes (attn_block_paged_f8_plan only: attn_block_split8_kernel)
 };
 AttnBlockPagedPlan attn_block_paged_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst16, const AttnKnobs& knobs, const AttnPage& page,
                                          const int* q_start, const int* kv_lens, int kv_len_bias, std::string* why);
+// The plan of ns_hip_attn_block_paged_f8: the fp16 plan of the same shape above (grid, ranges, dyn_* constants, partials, merge grid) with the kernel
+// family (f8) in place of the fp16 one, plus the FP8 pool's own refusals (attn_f8_pool_refusal, the scales).  A pure function
+// (tests/test_attn_block_paged_f8_plan.py).  pp.sp.a.k / .v are the pools' bases: bytes behind the fp16 pointer type.
+AttnBlockPagedPlan attn_block_paged_f8_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst16, const AttnKnobs& knobs, const AttnPage& page,
+                                            const int* q_start, const int* kv_lens, int kv_len_bias, std::string* why);
 // what ns_hip_attn_block_paged_workspace_size answers: the plan's partial_bytes, from the shape alone (0: no plan of that shape)
 size_t attn_block_paged_ws_bytes(const AttnKnobs& knobs, int batch, int head_num, int heads_kv, int head_size, int max_q, int capacity);
 
@@ -304,6 +313,8 @@ hipError_t launch_attn_onerow_f8(const AttnPlan& pl, float* ws, uint32_t* ticket
 hipError_t launch_attn_rows(const AttnPlan& pl, hipStream_t st);                                  // ns_attn_prefill.hip: AP_ROWS64, AP_ROWS128, AP_PIPELINED
 hipError_t launch_attn_block_split(const AttnPlan& pl, float* ws, hipStream_t st);                // ns_attn_block.hip: AP_BLOCK_SPLIT (+ merge)
 hipError_t launch_attn_block_paged(const AttnBlockPagedPlan& pl, float* ws, hipStream_t st);     // ns_attn_block.hip: the PAGED instantiation + its merge
+hipError_t launch_attn_block_paged_merge(const AttnBlockPagedParams& pp, dim3 merge_grid, hipStream_t st);  // ns_attn_block.hip: attn_block_paged_merge_kernel over pp.sp.ws
+hipError_t launch_attn_block_paged_f8(const AttnBlockPagedPlan& pl, float* ws, hipStream_t st);  // ns_attn_block_f8.hip: a plan with f8 set + that merge
 hipError_t launch_attn_prefill_paged(const AttnPrefillPagedPlan& pl, hipStream_t st);             // ns_attn_prefill.hip: the PAGED instantiations of the 128-row kernel
 hipError_t launch_attn_merge(const AttnSplitParams& sp, unsigned batch, hipStream_t st, bool rows = false);  // ns_attn_decode.hip: attn_merge_kernel over sp.ws
 // touch_attn_module (ns_common.h) makes the runtime load every one of these code objects
@@ -316,6 +327,7 @@ void touch_attn_rows_module();  // ns_attn_prefill.hip
 void touch_attn_block_module(); // ns_attn_block.hip
 void touch_kvcache_module();    // ns_kvcache.hip
 void touch_attn_f8_module();    // ns_attn_decode_f8.hip
+void touch_attn_block_f8_module();  // ns_attn_block_f8.hip
 // Is a HIP device visible?  who != nullptr: if not, the error is set and "Err: invalid parameters (<who>: no HIP device visible ...)" goes to stderr.
 bool attn_device_visible(const char* who);
 

@@ -36,8 +36,6 @@ typedef _Float16 bhalf8_t __attribute__((ext_vector_type(8)));
 typedef _Float16 bhalf4_t __attribute__((ext_vector_type(4)));
 typedef _Float16 bhalf2_t __attribute__((ext_vector_type(2)));
 typedef float bfloatx4 __attribute__((ext_vector_type(4)));
-constexpr int kBlkKB = 64;            // kv positions per block
-constexpr int kBlkVStr = kBlkKB + 4;  // halves per V^T row in LDS: keeps the 8-byte reads aligned, skews banks
 
 __device__ __forceinline__ const AttnSplitParams& split_params(const AttnSplitParams& sp) { return sp; }
 __device__ __forceinline__ const AttnSplitParams& split_params(const AttnBlockPagedParams& pp) { return pp.sp; }
@@ -374,6 +372,11 @@ __global__ __launch_bounds__(128) void attn_block_paged_merge_kernel(const AttnB
   }
 }
 
+// (the partials do not know the cache's type: ns_attn_block_f8.hip launches the same merge behind its range kernel)
+hipError_t launch_attn_block_paged_merge(const AttnBlockPagedParams& pp, dim3 merge_grid, hipStream_t st) {
+  hipLaunchKernelGGL(attn_block_paged_merge_kernel, merge_grid, dim3(128), 0, st, pp);
+  return hipGetLastError();
+}
 hipError_t launch_attn_block_paged(const AttnBlockPagedPlan& pl, float* ws, hipStream_t st) {
   AttnBlockPagedParams pp = pl.pp;
   pp.sp.ws = ws, pp.sp.tickets = nullptr;
@@ -382,9 +385,7 @@ hipError_t launch_attn_block_paged(const AttnBlockPagedPlan& pl, float* ws, hipS
   else
     hipLaunchKernelGGL((attn_block_split_kernel<128, true>), pl.grid, pl.block, 0, st, pp);
   const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(attn_block_paged_merge_kernel, pl.merge_grid, dim3(128), 0, st, pp);
-  return hipGetLastError();
+  return e != hipSuccess ? e : launch_attn_block_paged_merge(pp, pl.merge_grid, st);
 }
 void touch_attn_block_module() { touch_kernel(reinterpret_cast<const void*>(attn_block_split_kernel<128>)); }
 

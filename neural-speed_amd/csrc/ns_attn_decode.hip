@@ -780,6 +780,7 @@ void touch_attn_module() {  // (one kernel of every attention file: each has a c
   touch_attn_block_module();
   touch_kvcache_module();
   touch_attn_f8_module();
+  touch_attn_block_f8_module();
 }
 
 }  // namespace ns
