@@ -832,6 +832,22 @@ int ns_hip_attn_prefill_paged(const attn_fp32_fp16_fp16_fp32_fwd_args_t* dparams
 /* Process-wide counts of ns_hip_attn_prefill_paged: launches by padded head size [0] 64, [1] 128, [2] 256 (none: not built); [3] launches of a
  * biased instantiation (score bias or a score scale that is not positive), [4] of a padded one; [5] refused calls. */
 void ns_hip_attn_prefill_paged_stats(unsigned long long out[6]);
+/* ns_hip_attn_prefill_paged_f8: ns_hip_attn_prefill_paged's signature and, word for word, its contract (packed Q / dst / dst16 through dQStart, dKvLens
+ * + bias, max_q, the causal rule, zero rows, idle requests, the table-entry rules, ONE launch with no `tmp` and no scratch, capturable without a first
+ * eager call, ALiBi with the head partition, the tanh cap, any score scale) over THE FP8 POOL described above: K / V of the block are the pool bases,
+ * every stride counts bytes, K_sc / V_sc are the pools' scales, folded as ever (qk_scale = QK_scale * Q_sc * K_sc, out_scale = V_sc / dst_sc).  Head
+ * sizes: the multiples of 16 up to 128 (48, 80, 96, 112 padded to 64 / 128).  The plan is the fp16 entry's for the same call.  Every code is decoded
+ * exactly to fp16 once per workgroup, on its way into the LDS image the fp16 kernel keeps, and everything behind that image is the fp16 kernel's: the
+ * output holds THE BITS ns_hip_attn_prefill_paged gives over fp16 pools holding the codes' values under the same argument block.  Every cell address is
+ * 64-bit; no byte behind kv_len_b reaches a result.  With it an FP8 pool prefills the models the block entry refuses (head sizes 80 / 96, ALiBi, the
+ * tanh cap) and takes a prompt chunk in one launch; docs/kernels/attention.md gives the row count from which to prefer it to the block entry.
+ * Refused (-1, ns_hip_last_error set, nothing written): what the FP8 pool asks (head_size, the row stride, the head stride or block_step not a multiple
+ * of 16, a pool base that is not 16-byte aligned, a scale that is not positive and finite), then what ns_hip_attn_prefill_paged refuses.
+ * ns_hip_attn_prefill_paged_f8_stats: the fp16 entry's layout — launches by padded head size [0] 64, [1] 128, [2] 256 (none); [3] launches of a biased
+ * instantiation, [4] of a padded one; [5] refused calls.  The fp16 entry's counters do not move. */
+int ns_hip_attn_prefill_paged_f8(const attn_fp32_fp16_fp16_fp32_fwd_args_t* dparams, const int* dQStart, const int* dKvLens, int kv_len_bias,
+                                 const int* dBlockTable, int table_stride, int block_keys, int pool_blocks, long long block_step, void* dst16, void* stream);
+void ns_hip_attn_prefill_paged_f8_stats(unsigned long long out[6]);
 
 /* ----------------------------------------------------------------------------------------------
  * Part 4b — mixture-of-experts matmul with the routing on the device.  Device twin of

@@ -214,6 +214,32 @@ __host__ __device__ __forceinline__ int attn_prefill_kv_len(const int* kv_lens, 
 // rule of that kernel: its fetch and tests/tools/attn_prefill_paged_plan_main.cpp both go through it, then through attn_page_at.
 __host__ __device__ __forceinline__ int attn_prefill_tile_key(int pos0, int r, int kv_len) { return min(pos0 + r, kv_len - 1); }
 
+// ---- ... over an FP8 paged cache (ns_hip_attn_prefill_paged_f8; attn_mfma2_body's F8 instantiations, ns_attn_prefill.hip) ---------------------------
+// The staging map of a 64-key tile of CODES: a thread's 16-byte load is 16 dims of one key row, HS / 64 loads of K and as many of V per thread.  At
+// step u wave w stages the aligned group of 1024 / HS rows (16 at head size 64, 8 at 128) that starts at tile row attn_prefill8_group — tiles start at
+// multiples of 64 and a page holds 16 keys or more, so a group lies in ONE page and one table entry per wave and step serves K and V.  Inside the group
+// K's lanes go row by row (a row's columns in neighbouring lanes: its fp16 chunks 2 col, 2 col + 1 land in one swizzled LDS row), V's subtile by
+// subtile (8 neighbouring lanes = 8 rows of one 16-dim column: 256 contiguous bytes of the subtile's LDS image).  Host and device:
+// tests/tools/attn_prefill_paged_f8_plan_main.cpp walks every (tile, wave, step, lane) through these and the two address forms below.
+template <int HS>
+__host__ __device__ constexpr int attn_prefill8_group(int w, int u) { return (4 * u + w) * (1024 / HS); }
+template <int HS>
+__host__ __device__ constexpr int attn_prefill8_krow(int l) { return l / (HS / 16); }  // row inside the group, 16-dim column
+template <int HS>
+__host__ __device__ constexpr int attn_prefill8_kcol(int l) { return l % (HS / 16); }
+template <int HS>
+__host__ __device__ constexpr int attn_prefill8_vrow(int l) { return (l & 7) + 8 * (l / (HS / 2)); }
+template <int HS>
+__host__ __device__ constexpr int attn_prefill8_vcol(int l) { return (l >> 3) % (HS / 16); }
+// A WHOLE tile (pos0 + 64 <= kv_len: no row clamps): the wave-uniform part of a group's cells — block `blk`, the row of the group's first key
+// `first` inside it — or -1 = no access.  A lane adds (its row inside the group) * step_sl + head + 16 * column, computed once per launch.  Equal to
+// attn_page_at of the lane's own key through that key's own table entry (the group lies in one page).  The tile that reaches past kv_len goes row by
+// row through attn_prefill_tile_key and attn_page_at, as the fp16 form does for every tile.  All of it 64-bit: no 32-bit pool rule.
+__host__ __device__ __forceinline__ long long attn_prefill8_group_base(const AttnPage& pg, int blk, int first, long long step_sl) {
+  if (unsigned(blk) >= unsigned(pg.pool_blocks)) return -1;
+  return (long long)blk * pg.block_step + (long long)(first & ((1 << pg.block_shift) - 1)) * step_sl;
+}
+
 // ---- the launch decision as a value (ns_attn_plan.cpp) -------------------------------------------------------------------------------------
 // Every tunable the decision reads.  attn_knobs() (ns_attn.cpp) fills it from ns_hip_set_tuning's atomics and the environment.
 struct AttnKnobs {
@@ -303,9 +329,15 @@ struct AttnPrefillPagedPlan {
   dim3 grid, block;
   size_t lds = 0;
   int nqb = 0, aligned = 0, xcd_map = 0;  // query blocks per (head, request), 16-byte stores of the output, XCD remap
+  bool f8 = false;                  // the pools hold E4M3 codes (attn_prefill_paged_f8_plan only: attn_mfma2_paged8_kernel)
 };
 AttnPrefillPagedPlan attn_prefill_paged_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst16, const AttnKnobs& knobs, const AttnPage& page,
                                              const int* q_start, const int* kv_lens, int kv_len_bias, std::string* why);
+// The plan of ns_hip_attn_prefill_paged_f8: the FP8 pool's own refusals (the scales, attn_f8_pool_refusal) first, then the fp16 plan of the call as it
+// stands, every decision of which is kept (grid, nqb, sb, pad, hs_pad, lds, aligned, xcd_map), with the kernel family (f8) in place of the fp16 one.
+// A pure function (tests/test_attn_prefill_paged_f8_plan.py).  pp.a.k / .v are the pools' bases: bytes behind the fp16 pointer type.
+AttnPrefillPagedPlan attn_prefill_paged_f8_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst16, const AttnKnobs& knobs, const AttnPage& page,
+                                                const int* q_start, const int* kv_lens, int kv_len_bias, std::string* why);
 
 // ---- launches of a plan ----------------------------------------------------------------------------------------------------------------------
 hipError_t launch_attn_onerow(const AttnPlan& pl, float* ws, uint32_t* tickets, hipStream_t st);  // ns_attn_decode.hip: AP_GENERIC, AP_SPLIT_REGS, AP_RING (+ merge)
@@ -316,6 +348,7 @@ hipError_t launch_attn_block_paged(const AttnBlockPagedPlan& pl, float* ws, hipS
 hipError_t launch_attn_block_paged_merge(const AttnBlockPagedParams& pp, dim3 merge_grid, hipStream_t st);  // ns_attn_block.hip: attn_block_paged_merge_kernel over pp.sp.ws
 hipError_t launch_attn_block_paged_f8(const AttnBlockPagedPlan& pl, float* ws, hipStream_t st);  // ns_attn_block_f8.hip: a plan with f8 set + that merge
 hipError_t launch_attn_prefill_paged(const AttnPrefillPagedPlan& pl, hipStream_t st);             // ns_attn_prefill.hip: the PAGED instantiations of the 128-row kernel
+hipError_t launch_attn_prefill_paged_f8(const AttnPrefillPagedPlan& pl, hipStream_t st);          // ns_attn_prefill.hip: a plan with f8 set
 hipError_t launch_attn_merge(const AttnSplitParams& sp, unsigned batch, hipStream_t st, bool rows = false);  // ns_attn_decode.hip: attn_merge_kernel over sp.ws
 // touch_attn_module (ns_common.h) makes the runtime load every one of these code objects
 inline void touch_kernel(const void* kernel) {

@@ -514,4 +514,26 @@ AttnBlockPagedPlan attn_block_paged_f8_plan(const attn_fp32_fp16_fp16_fp32_fwd_a
   return pl;
 }
 
+// ---- prompt-sized query blocks over an FP8 paged cache (ns_hip_attn_prefill_paged_f8) ----------------------------------------------------------------
+// As above: the FP8 pool's refusals first — so a head size that is a multiple of 8 and not of 16 is refused in the pool's words, not the fp16 plan's —
+// and what passes them is a layout the fp16 plan takes as it stands: its alignment rule (row and head strides multiples of 8 elements, 16-byte aligned
+// bases) is implied by the byte rule's multiples of 16, so no legal byte layout is refused.  Everything the fp16 plan decides is kept.
+AttnPrefillPagedPlan attn_prefill_paged_f8_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst16, const AttnKnobs& kn, const AttnPage& page,
+                                                const int* q_start, const int* kv_lens, int kv_len_bias, std::string* why) {
+  AttnPrefillPagedPlan none;
+  memset(&none.pp, 0, sizeof(none.pp));
+  auto refuse = [&](const char* text) {
+    *why = text;
+    return none;
+  };
+  if (!(a.K_sc > 0.f) || !(a.V_sc > 0.f) || std::isinf(a.K_sc) || std::isinf(a.V_sc))
+    return refuse("attention, FP8 paged cache: K_sc and V_sc, the pools' scales, must be positive and finite");
+  if (a.step_k_head_size != 1 || a.step_v_head_size != 1) return refuse("attention, FP8 paged cache: K / V rows must be contiguous in the head dimension");
+  if (const char* text = attn_f8_pool_refusal(a.head_size, a.step_k_sl, a.step_k_head_num, page.block_step, a.K)) return refuse(text);
+  if (const char* text = attn_f8_pool_refusal(a.head_size, a.step_v_sl, a.step_v_head_num, page.block_step, a.V)) return refuse(text);
+  AttnPrefillPagedPlan pl = attn_prefill_paged_plan(a, dst16, kn, page, q_start, kv_lens, kv_len_bias, why);
+  pl.f8 = pl.ok;
+  return pl;
+}
+
 }  // namespace ns

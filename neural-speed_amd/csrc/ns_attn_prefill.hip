@@ -1,6 +1,6 @@
 // ns_attn_prefill.hip — fused attention, the matrix-core kernels for 16 or more query rows (attn_mfma_kernel: 64 rows per workgroup;
-// attn_mfma2_kernel, attn_mfma3_kernel: 128; attn_mfma2_paged_kernel: attn_mfma2_kernel's body over a paged cache, ns_hip_attn_prefill_paged), and the
-// launch of a plan that names one (ns_attn.h).
+// attn_mfma2_kernel, attn_mfma3_kernel: 128; attn_mfma2_paged_kernel: attn_mfma2_kernel's body over a paged cache, ns_hip_attn_prefill_paged;
+// attn_mfma2_paged8_kernel: the same over pools of E4M3 codes, ns_hip_attn_prefill_paged_f8), and the launch of a plan that names one (ns_attn.h).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -271,7 +271,28 @@ typedef short ashort4_t __attribute__((ext_vector_type(4)));
 // it (docs/kernels/attention.md, "Prompt-sized query blocks over a paged cache").
 __device__ __forceinline__ const AttnParams& attn_params_of(const AttnParams& p) { return p; }
 __device__ __forceinline__ const AttnParams& attn_params_of(const AttnPrefillPagedParams& pp) { return pp.a; }
-template <int HS, bool SB, bool PAD, int RG = 1, bool PAGED = false>
+// F8 (ns_hip_attn_prefill_paged_f8; PAGED only): the pools hold E4M3 codes, one byte per element.  Only the way from the pools to LDS differs:
+//   load    16 codes per 16-byte load — 16 dims of one key row; HS / 64 loads of K and of V per thread and tile (the fp16 form: HS / 32), in the
+//           staging map of ns_attn.h (attn_prefill8_*): a wave's rows of a step are ONE aligned group of 1024 / HS rows, inside one page.
+//   address a whole tile (pos0 + 64 <= kv_len, workgroup-uniform) takes one address per wave and step: the block id from v_readlane of the prefetched
+//           entry, its range check and id * block_step + (row in the page) * step_sl in scalar registers (attn_prefill8_group_base), plus the lane's
+//           part, computed once in front of the loop.  Only the tile that reaches past kv_len goes row by row through attn_prefill_tile_key /
+//           attn_page_at.  64-bit throughout.
+//   decode  once per workgroup, at park: E4M3 -> fp16 is exact (v_cvt_scalef32_pk_f16_fp8, scale 1.0); a thread's 16 K codes are the fp16 chunks
+//           2 col, 2 col + 1 of its row, written to the swizzled slots the fp16 form writes them to; its 16 V codes are the 32 bytes of one subtile
+//           row.  The LDS image is byte for byte the fp16 kernel's over the decoded values, and so is every operation behind it.
+// A staged row is clamped to kv_len - 1 (a live cell) and id -1 is a register of zero CODES, so no byte behind a live length is decoded.
+typedef uint32_t auint4_t __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ ahalf8_t a2_e4m3x8_to_h8(uint32_t w0, uint32_t w1) {  // eight codes (memory order) -> eight halves, exact
+  typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+  const h2 a = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w0, 1.0f, false), b = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w0, 1.0f, true);
+  const h2 c = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w1, 1.0f, false), d = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w1, 1.0f, true);
+  return ahalf8_t{a.x, a.y, b.x, b.y, c.x, c.y, d.x, d.y};
+}
+#ifndef NS_A2_F8_NODECODE
+#define NS_A2_F8_NODECODE 0  // timing ablation (diagnostic build, wrong results): 1 = the F8 forms park the raw codes, no conversion
+#endif
+template <int HS, bool SB, bool PAD, int RG = 1, bool PAGED = false, bool F8 = false>
 __device__ __forceinline__ void attn_mfma2_body(const std::conditional_t<PAGED, AttnPrefillPagedParams, AttnParams>& pp, const int nqb, const int aligned_dst,
                                                 const int xcd_map) {
   const AttnParams& p = attn_params_of(pp);
@@ -398,8 +419,10 @@ __device__ __forceinline__ void attn_mfma2_body(const std::conditional_t<PAGED, 
   // share its counter with the LDS reads of the tile's products and stall them); step u reads it from lane u.  idv holds the entries of the tile
   // the NEXT fetch requests (kv_len >= 1 wherever a tile is fetched: nb > 0).
   static_assert(!PAGED || (KU == VU && 256 / NCH == 4 * VRW), "K and V rows of a staging step: the same group of a wave");
+  static_assert(!F8 || (PAGED && RG == 1 && HS <= 128), "F8: a form of the PAGED instantiations");
+  constexpr int KU8 = F8 ? HS / 64 : 1;  // F8: 16-byte loads of K, and of V, per thread and tile
   int idv = 0;
-  const int grp_l = (l % KU) * (64 / KU) + w * (16 / KU);  // first tile row of the group whose entry this lane fetches
+  const int grp_l = F8 ? attn_prefill8_group<HS>(w, l % KU8) : (l % KU) * (64 / KU) + w * (16 / KU);  // first tile row of the group whose entry this lane fetches
   auto fetch_ids = [&](int pos0) {
     if constexpr (PAGED) return pp.pg.table[(long long)ibs * pp.pg.table_stride + (attn_prefill_tile_key(pos0, grp_l, kv_len) >> pp.pg.block_shift)];
     return 0;
@@ -455,6 +478,71 @@ __device__ __forceinline__ void attn_mfma2_body(const std::conditional_t<PAGED, 
 #pragma unroll
     for (int u = 0; u < VU; u++) *reinterpret_cast<ahalf8_t*>(sb + KTILE + vsub * kA2VSub + vrow[u] * 32 + vhf * 16) = vst[u];
   };
+  // ---- F8: the same two steps over codes (nothing of it is part of another instantiation) ----
+  auint4_t kc8[KU8], vc8[KU8];  // the codes as loaded: half the fp16 form's staging registers
+  int kr8 = 0, kcl8 = 0, vr8 = 0, vcl8 = 0, wu = 0;  // this lane's row inside a group and 16-dim column, for K and for V; the wave, in a scalar register
+  bool k_in8 = true, v_in8 = true;                   // head sizes are multiples of 16: a thread's column exists as a whole
+  const unsigned char* kb8 = nullptr;                // the head's cells + the lane's part of a group's addresses
+  const unsigned char* vb8 = nullptr;
+  if constexpr (F8) {
+    kr8 = attn_prefill8_krow<HS>(l), kcl8 = attn_prefill8_kcol<HS>(l), vr8 = attn_prefill8_vrow<HS>(l), vcl8 = attn_prefill8_vcol<HS>(l);
+    k_in8 = !PAD || 16 * kcl8 < hs, v_in8 = !PAD || 16 * vcl8 < hs;
+    wu = __builtin_amdgcn_readfirstlane(w);
+    kb8 = reinterpret_cast<const unsigned char*>(p.k) + (long long)ihkv * p.step_k_head_num + 16 * kcl8 + (long long)kr8 * p.step_k_sl;
+    vb8 = reinterpret_cast<const unsigned char*>(p.v) + (long long)ihkv * p.step_v_head_num + 16 * vcl8 + (long long)vr8 * p.step_v_sl;
+#pragma unroll
+    for (int u = 0; u < KU8; u++) kc8[u] = vc8[u] = auint4_t{0u, 0u, 0u, 0u};  // (a column the head does not have: zero codes, once)
+  }
+  auto fetch8 = [&](int pos0) {
+    if constexpr (F8) {
+      const int idv_n = fetch_ids(pos0 + kA2KB);  // (clamped to the last live key: a valid entry also behind the last tile)
+      if (pos0 + kA2KB <= kv_len) {  // workgroup-uniform: a whole tile, one address per wave and step
+#pragma unroll
+        for (int u = 0; u < KU8; u++) {
+          const int id = __builtin_amdgcn_readlane(idv, u), first = pos0 + attn_prefill8_group<HS>(wu, u);
+          const long long kbase = attn_prefill8_group_base(pp.pg, id, first, p.step_k_sl), vbase = attn_prefill8_group_base(pp.pg, id, first, p.step_v_sl);
+          if (k_in8) kc8[u] = kbase >= 0 ? *reinterpret_cast<const auint4_t*>(kb8 + kbase) : auint4_t{0u, 0u, 0u, 0u};
+          if (v_in8) vc8[u] = vbase >= 0 ? *reinterpret_cast<const auint4_t*>(vb8 + vbase) : auint4_t{0u, 0u, 0u, 0u};
+        }
+      } else {  // the tile that reaches past kv_len: every row clamped to the last live key, through its page
+#pragma unroll
+        for (int u = 0; u < KU8; u++) {
+          const int id = __builtin_amdgcn_readlane(idv, u), first = attn_prefill8_group<HS>(w, u);
+          if (k_in8) {
+            const long long cell = attn_page_at(pp.pg, id, attn_prefill_tile_key(pos0, first + kr8, kv_len), p.step_k_sl);
+            kc8[u] = cell >= 0 ? *reinterpret_cast<const auint4_t*>(kb8 + (cell - (long long)kr8 * p.step_k_sl)) : auint4_t{0u, 0u, 0u, 0u};
+          }
+          if (v_in8) {
+            const long long cell = attn_page_at(pp.pg, id, attn_prefill_tile_key(pos0, first + vr8, kv_len), p.step_v_sl);
+            vc8[u] = cell >= 0 ? *reinterpret_cast<const auint4_t*>(vb8 + (cell - (long long)vr8 * p.step_v_sl)) : auint4_t{0u, 0u, 0u, 0u};
+          }
+        }
+      }
+      idv = idv_n;
+    }
+  };
+  auto park8 = [&](int stage) {
+    if constexpr (F8) {
+      unsigned char* sb = smem2 + stage * STAGE;
+      auto put = [&](unsigned char* at, uint32_t w0, uint32_t w1) {
+        if (NS_A2_F8_NODECODE)
+          *reinterpret_cast<auint4_t*>(at) = auint4_t{w0, w1, w0, w1};
+        else
+          *reinterpret_cast<ahalf8_t*>(at) = a2_e4m3x8_to_h8(w0, w1);
+      };
+#pragma unroll
+      for (int u = 0; u < KU8; u++) {
+        const int kr = attn_prefill8_group<HS>(w, u) + kr8, vr = attn_prefill8_group<HS>(w, u) + vr8;
+        const int swz = HS >= 128 ? (kr & 15) : ((kr >> 1) & 7);
+        unsigned char* kd = sb + kr * KROW;  // the row's fp16 chunks 2 col, 2 col + 1 -> its swizzled 16-byte slots
+        put(kd + (((2 * kcl8) ^ swz) << 4), kc8[u].x, kc8[u].y);
+        put(kd + (((2 * kcl8 + 1) ^ swz) << 4), kc8[u].z, kc8[u].w);
+        unsigned char* vd = sb + KTILE + vcl8 * kA2VSub + vr * 32;  // one 32-byte row of subtile col
+        put(vd, vc8[u].x, vc8[u].y);
+        put(vd + 16, vc8[u].z, vc8[u].w);
+      }
+    }
+  };
   // operand addresses inside a stage
   const int swz_n = HS >= 128 ? (n & 15) : ((n >> 1) & 7);
   const int k_rd = n * KROW;                                                        // + 32 T rows, slot (2 j + h) ^ swizzle
@@ -463,14 +551,21 @@ __device__ __forceinline__ void attn_mfma2_body(const std::conditional_t<PAGED, 
   const int nb = (kv_end + kA2KB - 1) / kA2KB;
   if (nb > 0) {
     idv = fetch_ids(0);
-    fetch(0);
-    park(0);
+    if constexpr (F8) {
+      fetch8(0);
+      park8(0);
+    } else {
+      fetch(0);
+      park(0);
+    }
   }
   __syncthreads();
   for (int b = 0; b < nb; b++) {
     const int pos0 = b * kA2KB;
     const unsigned char* sb = smem2 + (b & 1) * STAGE;
-    if (b + 1 < nb && NS_A2_ABL < 4) fetch(pos0 + kA2KB);
+    if (b + 1 < nb && NS_A2_ABL < 4) {
+      if constexpr (F8) fetch8(pos0 + kA2KB); else fetch(pos0 + kA2KB);
+    }
     if (wave_live && pos0 < vis_last) {
       // operands travel LDS -> registers one group of four MFMAs ahead of their use (two register sets, fenced: left alone hipcc
       // re-uses ONE operand register and serialises read -> wait -> MFMA, ~100 exposed cycles per MFMA)
@@ -580,7 +675,9 @@ __device__ __forceinline__ void attn_mfma2_body(const std::conditional_t<PAGED, 
         }
       }
     }
-    if (b + 1 < nb && NS_A2_ABL < 4) park((b + 1) & 1);
+    if (b + 1 < nb && NS_A2_ABL < 4) {
+      if constexpr (F8) park8((b + 1) & 1); else park((b + 1) & 1);
+    }
     if (NS_A2_ABL < 5) __syncthreads();
   }
 #pragma unroll
@@ -880,6 +977,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   attn_mfma2_body<HS, SB, PAD, 1, true>(pp, nqb, aligned_dst, xcd_map);
 }
 // (no head-size-256 form: with the whole register file it still needs 116 .. 196 bytes of scratch per lane — the plan refuses head sizes above 128)
+// the F8 instantiations (ns_hip_attn_prefill_paged_f8): the PAGED forms over pools of E4M3 codes, the same register budget
+template <int HS, bool SB, bool PAD>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2), target("no-packed-fp32-ops"))) void attn_mfma2_paged8_kernel(const AttnPrefillPagedParams pp, const int nqb, const int aligned_dst,
+                                                                                                     const int xcd_map) {
+  attn_mfma2_body<HS, SB, PAD, 1, true, true>(pp, nqb, aligned_dst, xcd_map);
+}
 
 // ---- launch of a plan (ns_attn_plan.cpp): pl.hs_pad, pl.sb and pl.pad are the template arguments -----------------------------------------
 hipError_t launch_attn_rows(const AttnPlan& pl, hipStream_t st) {
@@ -911,6 +1014,19 @@ hipError_t launch_attn_prefill_paged(const AttnPrefillPagedPlan& pl, hipStream_t
     constexpr bool SB = decltype(sb_c)::value, PAD = decltype(pad_c)::value;
     if (pl.hs_pad != 64 && pl.hs_pad != 128) return hipErrorInvalidValue;  // (no plan names another)
     return pl.hs_pad == 64 ? go(kernel_c<attn_mfma2_paged_kernel<64, SB, PAD>>{}) : go(kernel_c<attn_mfma2_paged_kernel<128, SB, PAD>>{});
+  };
+  if (pl.sb) return pl.pad ? by_hs(std::true_type{}, std::true_type{}) : by_hs(std::true_type{}, std::false_type{});
+  return pl.pad ? by_hs(std::false_type{}, std::true_type{}) : by_hs(std::false_type{}, std::false_type{});
+}
+hipError_t launch_attn_prefill_paged_f8(const AttnPrefillPagedPlan& pl, hipStream_t st) {
+  if (!pl.ok || !pl.f8) return hipErrorInvalidValue;
+  auto go = [&](auto kern_c) {
+    return launch_lds<decltype(kern_c)::value>(int(pl.lds), pl.grid, pl.block, pl.lds, st, pl.pp, pl.nqb, pl.aligned, pl.xcd_map);
+  };
+  auto by_hs = [&](auto sb_c, auto pad_c) {
+    constexpr bool SB = decltype(sb_c)::value, PAD = decltype(pad_c)::value;
+    if (pl.hs_pad != 64 && pl.hs_pad != 128) return hipErrorInvalidValue;  // (no plan names another)
+    return pl.hs_pad == 64 ? go(kernel_c<attn_mfma2_paged8_kernel<64, SB, PAD>>{}) : go(kernel_c<attn_mfma2_paged8_kernel<128, SB, PAD>>{});
   };
   if (pl.sb) return pl.pad ? by_hs(std::true_type{}, std::true_type{}) : by_hs(std::true_type{}, std::false_type{});
   return pl.pad ? by_hs(std::false_type{}, std::true_type{}) : by_hs(std::false_type{}, std::false_type{});
