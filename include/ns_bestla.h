@@ -789,6 +789,35 @@ size_t ns_hip_attn_block_paged_workspace_size(int batch, int head_num, int heads
 /* Process-wide counts of ns_hip_attn_block_paged: [0] launches of the head-size-64 kernel, [1] of the head-size-128 kernel, [2] merge launches,
  * [3] refused calls. */
 void ns_hip_attn_block_paged_stats(unsigned long long out[4]);
+/* ns_hip_attn_decode_paged_shared: SHARED-PREFIX (cascade) DECODE over the fp16 pools — one query row per request, as ns_hip_attn_decode_paged, for a
+ * step in which the caller names groups of requests whose first keys are the same cells (a common system prompt).  K / V of a group's prefix are read
+ * once per 64 (member, query head) slots and context range on the matrix cores, not once per request; each member's own keys behind the prefix are read
+ * through its own table row; one merge sums both.  The argument block is ns_hip_attn_decode_paged's: sl_q = 1, batch_size = the requests, sl_kv = the
+ * capacity = table_stride * block_keys, Q / dst / dst16 addressed per request as there.  dGroupStart (groups + 1 ints), dPrefixKeys (groups ints),
+ * dKvLens (batch_size ints) and the table are DEVICE arrays read inside the launches:
+ *   group g holds requests dGroupStart[g] .. + n_g - 1, n_g = clamp(dGroupStart[g + 1] - dGroupStart[g], 0, max_group), max_group >= 1 the host's bound;
+ *   its first request is its LEADER.  A member index outside [0, batch_size) is skipped and never becomes an address (a leader outside it: the group
+ *   is empty).  P_g = floor(clamp(dPrefixKeys[g], 0, sl_kv) / block_keys) * block_keys,  len_b = clamp(dKvLens[b] + kv_len_bias, 0, sl_kv).
+ *   Member b attends over keys [0, min(P_g, len_b)) read through the LEADER's table row and over keys [P_g, len_b) through its own; its own entries
+ *   below P_g / block_keys are never read.
+ * The result is what ns_hip_attn_decode_paged gives on a table in which every member's first P_g / block_keys entries are copies of the leader's (up to
+ * the rounding of another kernel family).  len_b = 0: the row is written as zeros.  A request no group names is not touched; a request two groups name
+ * gets an unspecified row.  A group of one request with prefix 0 is plain paged decode.  Table entries as in the paged entries: an id outside
+ * [0, pool_blocks) reads as zeros and never becomes an address; no byte behind min(P_g, len_b) of the prefix or behind len_b reaches a result.
+ * Three launches (prefix ranges, suffix ranges, merge) one behind the other on the stream; capturable once and moved by the contents of the four
+ * device arrays.  Workspace: `tmp`, when given, is DEVICE memory of ns_hip_attn_decode_paged_shared_workspace_size(..) bytes; otherwise the stream's
+ * scratch, which a first use on a capturing stream cannot allocate.
+ * Refused (-1, ns_hip_last_error set, nothing written): what ns_hip_attn_block_paged refuses of the cache's description, a null dGroupStart /
+ * dPrefixKeys / dKvLens, groups < 1, max_group < 1, sl_q != 1, a head size other than 64 / 128, ALiBi or the tanh cap, a grid dimension above 65535
+ * (batch_size, groups, groups * max_group, heads_kv * ceil(max_group * (head_num / heads_kv) / 64)). */
+int ns_hip_attn_decode_paged_shared(const attn_fp32_fp16_fp16_fp32_fwd_args_t* dparams, const int* dGroupStart, int groups, int max_group,
+                                    const int* dPrefixKeys, const int* dKvLens, int kv_len_bias, const int* dBlockTable, int table_stride, int block_keys,
+                                    int pool_blocks, long long block_step, void* dst16, void* stream);
+/* bytes of its partials, a function of the shape alone (no device needed; 0: a shape the entry refuses) */
+size_t ns_hip_attn_decode_paged_shared_workspace_size(int batch, int head_num, int heads_kv, int head_size, int max_group, int capacity);
+/* Process-wide counts of ns_hip_attn_decode_paged_shared: [0] prefix / suffix range launches of the head-size-64 kernel (two per call), [1] of the
+ * head-size-128 kernel, [2] merge launches, [3] refused calls. */
+void ns_hip_attn_decode_paged_shared_stats(unsigned long long out[4]);
 /* ---- ragged query blocks over an FP8 (E4M3) paged cache: with these two an FP8 pool takes prompt chunks, drafted tokens and mixed steps itself ----
  * ns_hip_attn_block_paged_f8: ns_hip_attn_block_paged's signature and, word for word, its contract (packed Q / dst / dst16 through dQStart, dKvLens +
  * bias, max_q, the causal rule, zero rows, idle requests, the table-entry rules, tmp of ns_hip_attn_block_paged_workspace_size bytes or the stream's

@@ -290,6 +290,11 @@ def lib():
         L.ns_hip_attn_block_paged_f8_stats.argtypes = [vp]
         L.ns_hip_rope_qkv_append_paged_seq_f8.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, vp, i, i, i, f, f, f, f, vp, i, vp, i, i, i, C.c_longlong,
                                                           C.c_longlong, C.c_longlong, f, f, vp]
+        L.ns_hip_attn_decode_paged_shared.argtypes = [vp, vp, i, i, vp, vp, i, vp, i, i, i, C.c_longlong, vp, vp]
+        L.ns_hip_attn_decode_paged_shared_workspace_size.restype = sz
+        L.ns_hip_attn_decode_paged_shared_workspace_size.argtypes = [i, i, i, i, i, i]
+        L.ns_hip_attn_decode_paged_shared_stats.restype = None
+        L.ns_hip_attn_decode_paged_shared_stats.argtypes = [vp]
         L.ns_hip_attn_prefill_paged.argtypes = [vp, vp, vp, i, vp, i, i, i, C.c_longlong, vp, vp]
         L.ns_hip_attn_prefill_paged_stats.restype = None
         L.ns_hip_attn_prefill_paged_stats.argtypes = [vp]

@@ -194,6 +194,58 @@ __host__ __device__ __forceinline__ int attn_block_q_len(const int* q_start, int
   return n < 0 ? 0 : (n > max_q ? max_q : int(n));
 }
 
+// ---- shared-prefix decode over a paged cache (ns_hip_attn_decode_paged_shared; attn_shared_kernel and its merge, ns_attn_shared.hip) ---------------
+// One query row per request; the caller names GROUPS of consecutive requests whose first `prefix` keys are the same cells.  a: as the paged decode
+// entry reads it (a.sl_q = 1, a.sl_kv = a request's capacity, a.k / a.v the pool bases, Q / dst / dst16 stepped per request by step_q_bs /
+// step_dst_bs).  group_start[groups + 1], prefix_keys[groups], kv_lens[requests] and the table are DEVICE arrays read inside the launches.
+// Two kinds of range workgroup write partial (m, l, acc) records, one merge reads them:
+//   prefix ranges  nsp ranges of kps_p keys laid out over the capacity; live: attn_block_live(P_g, nsp, kps_p, min_keys); range i is keys
+//                  [i * kps, min((i + 1) * kps, P_g)) through the LEADER's table row, for the 64 (member, query head) slots of a slot block.
+//   suffix ranges  nss ranges of kps_s keys; live: attn_block_live(len_b - P_g, nss, kps_s, min_keys); range i is keys
+//                  [P_g + i * kps, min(P_g + (i + 1) * kps, len_b)) through the member's own row.
+// P_g is a multiple of block_keys >= 16 and kps a multiple of 64, so every range — and with it every 16-key score tile of its 64-key blocks — starts
+// at a multiple of 16: a tile lies in ONE page, as in the block kernel, although a suffix block no longer starts at a multiple of 64.
+// Partials: ws[request][head][rec_stride][2 + head_size]; prefix range i is record i, suffix range i record suf_off + i.  rec_stride and suf_off are
+// those of ONE group (the most ranges any number of groups gives: the rule's workgroups per range grow with the groups), so the workspace is a
+// function of the shape alone.
+struct AttnSharedParams {
+  AttnParams a;
+  AttnPage pg;
+  float* ws;
+  const int* group_start;
+  const int* prefix_keys;
+  const int* kv_lens;
+  int kdelta;             // added to kv_lens' entries
+  int requests;           // batch_size
+  int groups, max_group;  // max_group: the host's bound on the requests of one group
+  int g_full;             // query heads per kv head
+  int nsp, kps_p, nss, kps_s;
+  int min_keys;           // the block rule's least keys per range, applied to the live lengths (0: ranges as laid out)
+  int rec_stride, suf_off;
+};
+// Group g as every workgroup and the merge read it: its leader `first`, its n members first .. first + n - 1, its shared keys `prefix`.  A leader
+// outside [0, requests) makes the group empty; the members are cut at the last request, so no member index ever leaves [0, requests).
+struct AttnSharedGroup {
+  int first, n, prefix;
+};
+__host__ __device__ __forceinline__ AttnSharedGroup attn_shared_group(const int* group_start, const int* prefix_keys, int g, int max_group, int requests,
+                                                                      int cap, int block_shift) {
+  const int first = group_start[g];
+  if (first < 0 || first >= requests) return {first, 0, 0};
+  const long long n = (long long)group_start[g + 1] - first;
+  const int most = min(max_group, requests - first);
+  const int pk = prefix_keys[g];
+  return {first, n < 0 ? 0 : (n > most ? most : int(n)), (pk < 0 ? 0 : (pk > cap ? cap : pk)) >> block_shift << block_shift};
+}
+__host__ __device__ __forceinline__ AttnSharedGroup attn_shared_group(const AttnSharedParams& sp, int g) {
+  return attn_shared_group(sp.group_start, sp.prefix_keys, g, sp.max_group, sp.requests, sp.a.sl_kv, sp.pg.block_shift);
+}
+// live keys of request b: attn_live_kv<true>'s clamp
+__host__ __device__ __forceinline__ int attn_shared_len(const AttnSharedParams& sp, int b) {
+  const long long len = (long long)sp.kv_lens[b] + sp.kdelta;
+  return len < 0 ? 0 : (len > sp.a.sl_kv ? sp.a.sl_kv : int(len));
+}
+
 // ---- prompt-sized query blocks over a paged cache (ns_hip_attn_prefill_paged; attn_mfma2_body's PAGED instantiations, ns_attn_prefill.hip) --------
 // Argument block: a as the 128-row kernel reads it, with a.sl_q = max_q, a.sl_kv = a request's capacity, a.k / a.v the pool bases and no batch step
 // (Q, dst and dst16 are packed through q_start, as above); kv_lens[b] + kdelta, clamped to [0, capacity], are request b's live keys.
@@ -319,6 +371,25 @@ AttnBlockPagedPlan attn_block_paged_f8_plan(const attn_fp32_fp16_fp16_fp32_fwd_a
 // what ns_hip_attn_block_paged_workspace_size answers: the plan's partial_bytes, from the shape alone (0: no plan of that shape)
 size_t attn_block_paged_ws_bytes(const AttnKnobs& knobs, int batch, int head_num, int heads_kv, int head_size, int max_q, int capacity);
 
+// The plan of ns_hip_attn_decode_paged_shared: a pure function like attn_block_paged_plan (tests/test_attn_shared_paged_plan.py).  a.sl_q is 1, a.sl_kv
+// the capacity.  Both kinds of range follow the block rule of AP_BLOCK_SPLIT (kn.block_target / kn.block_min_keys) over the capacity: the prefix
+// ranges with heads_kv * ceil(max_group * g_full / 64) * groups workgroups per range, the suffix ranges with heads_kv * ceil(g_full / 64) *
+// (groups * max_group); kn.dyn_ranges: the workgroups apply the rule's least keys to P_g and to len_b - P_g.  !ok: *why says what is wrong with the
+// call.  sp.ws is null: the launcher's scratch.
+struct AttnSharedPagedPlan {
+  bool ok = false;
+  int hs_pad = 0;
+  AttnSharedParams sp;
+  dim3 grid_prefix, grid_suffix, block, merge_grid;  // (slot blocks of max_group * g_full slots * kv heads, nsp, groups) x 256; (slot blocks of g_full
+                                                     // slots * kv heads, nss, groups * max_group) x 256; (heads, requests) x 128
+  size_t partial_bytes = 0;
+};
+AttnSharedPagedPlan attn_shared_paged_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst16, const AttnKnobs& knobs, const AttnPage& page,
+                                           const int* group_start, int groups, int max_group, const int* prefix_keys, const int* kv_lens, int kv_len_bias,
+                                           std::string* why);
+// what ns_hip_attn_decode_paged_shared_workspace_size answers: the plan's partial_bytes, from the shape alone (0: no plan of that shape)
+size_t attn_shared_paged_ws_bytes(const AttnKnobs& knobs, int batch, int head_num, int heads_kv, int head_size, int max_group, int capacity);
+
 // The plan of ns_hip_attn_prefill_paged: a pure function like attn_block_paged_plan (tests/test_attn_prefill_paged_plan.py).  a.sl_q is max_q, a.sl_kv
 // the capacity.  One launch of attn_mfma2_body<hs_pad, sb, pad, 1, PAGED>: ceil(max_q / 128) query blocks x heads x requests workgroups; the query
 // blocks a request does not have leave at once.  No partials, no scratch.  !ok: *why says what is wrong with the call.
@@ -347,6 +418,7 @@ hipError_t launch_attn_block_split(const AttnPlan& pl, float* ws, hipStream_t st
 hipError_t launch_attn_block_paged(const AttnBlockPagedPlan& pl, float* ws, hipStream_t st);     // ns_attn_block.hip: the PAGED instantiation + its merge
 hipError_t launch_attn_block_paged_merge(const AttnBlockPagedParams& pp, dim3 merge_grid, hipStream_t st);  // ns_attn_block.hip: attn_block_paged_merge_kernel over pp.sp.ws
 hipError_t launch_attn_block_paged_f8(const AttnBlockPagedPlan& pl, float* ws, hipStream_t st);  // ns_attn_block_f8.hip: a plan with f8 set + that merge
+hipError_t launch_attn_shared_paged(const AttnSharedPagedPlan& pl, float* ws, hipStream_t st);   // ns_attn_shared.hip: prefix ranges, suffix ranges, merge
 hipError_t launch_attn_prefill_paged(const AttnPrefillPagedPlan& pl, hipStream_t st);             // ns_attn_prefill.hip: the PAGED instantiations of the 128-row kernel
 hipError_t launch_attn_prefill_paged_f8(const AttnPrefillPagedPlan& pl, hipStream_t st);          // ns_attn_prefill.hip: a plan with f8 set
 hipError_t launch_attn_merge(const AttnSplitParams& sp, unsigned batch, hipStream_t st, bool rows = false);  // ns_attn_decode.hip: attn_merge_kernel over sp.ws

@@ -367,6 +367,95 @@ AttnBlockPagedPlan attn_block_paged_plan(const attn_fp32_fp16_fp16_fp32_fwd_args
   return pl;
 }
 
+// ---- shared-prefix decode over a paged cache (ns_hip_attn_decode_paged_shared) -----------------------------------------------------------------------
+// Both kinds of range go through block_paged_ranges: the prefix ranges as `groups` requests of max_group rows (the slots of a group are its members'
+// query heads), the suffix ranges as groups * max_group requests of one row.
+static const char* shared_paged_shape_refusal(int requests, int head_num, int heads_kv, int head_size, int max_group, int cap) {
+  if (requests < 1 || requests > 65535) return "attention, shared-prefix decode: batch_size (the requests) must be 1 .. 65535";
+  if (head_size != 64 && head_size != 128) return "attention, shared-prefix decode: head_size must be 64 or 128";
+  if (heads_kv < 1 || head_num < 1 || head_num % heads_kv != 0 || head_num > 65535)
+    return "attention, shared-prefix decode: head_num must be a multiple of heads_kv (at most 65535)";
+  if (max_group < 1 || max_group > 65535) return "attention, shared-prefix decode: max_group, the most requests of one group, must be 1 .. 65535";
+  if (cap < 1) return "attention, shared-prefix decode: sl_kv is the capacity of a request (at least 1 key)";
+  if (size_t(heads_kv) * ((size_t(max_group) * (head_num / heads_kv) + 63) / 64) > 65535)
+    return "attention, shared-prefix decode: heads_kv * ceil(max_group * (head_num / heads_kv) / 64) above the grid limit of 65535";
+  return nullptr;
+}
+// the records of a (request, head): the ranges of ONE group — the most any number of groups gives
+static void shared_paged_records(const AttnKnobs& kn, int heads_kv, int g_full, int max_group, int cap, int* prefix_records, int* suffix_records) {
+  size_t slot_blocks;
+  int kps;
+  block_paged_ranges(kn, 1, heads_kv, g_full, max_group, cap, &slot_blocks, prefix_records, &kps);
+  block_paged_ranges(kn, max_group, heads_kv, g_full, 1, cap, &slot_blocks, suffix_records, &kps);
+}
+size_t attn_shared_paged_ws_bytes(const AttnKnobs& kn, int batch, int head_num, int heads_kv, int head_size, int max_group, int capacity) {
+  if (shared_paged_shape_refusal(batch, head_num, heads_kv, head_size, max_group, capacity)) return 0;
+  int rp, rs;
+  shared_paged_records(kn, heads_kv, head_num / heads_kv, max_group, capacity, &rp, &rs);
+  return size_t(batch) * head_num * (rp + rs) * (2 + head_size) * 4;
+}
+AttnSharedPagedPlan attn_shared_paged_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst16, const AttnKnobs& kn, const AttnPage& page,
+                                           const int* group_start, int groups, int max_group, const int* prefix_keys, const int* kv_lens, int kv_len_bias,
+                                           std::string* why) {
+  AttnSharedPagedPlan pl;
+  memset(&pl.sp, 0, sizeof(pl.sp));
+  auto refuse = [&](const char* text) {
+    *why = text;
+    return pl;
+  };
+  if (a.Q_layout != ATTN_FWD_LAYOUT_PLAIN || a.K_layout != ATTN_FWD_LAYOUT_PLAIN || a.V_layout != ATTN_FWD_LAYOUT_PLAIN ||
+      a.dst_layout != ATTN_FWD_LAYOUT_PLAIN)
+    return refuse("attention: only ATTN_FWD_LAYOUT_PLAIN tensors are supported");
+  if (!group_start) return refuse("attention, shared-prefix decode: dGroupStart is null");
+  if (!prefix_keys) return refuse("attention, shared-prefix decode: dPrefixKeys is null");
+  if (!kv_lens) return refuse("attention, shared-prefix decode: dKvLens is null");
+  if (a.sl_q != 1) return refuse("attention, shared-prefix decode: one query row per request (sl_q must be 1)");
+  if (groups < 1 || groups > 65535) return refuse("attention, shared-prefix decode: groups must be 1 .. 65535");
+  if (const char* text = shared_paged_shape_refusal(a.batch_size, a.head_num, a.heads_kv, a.head_size, max_group, a.sl_kv)) return refuse(text);
+  if ((long long)groups * max_group > 65535) return refuse("attention, shared-prefix decode: groups * max_group above the grid limit of 65535");
+  if (a.attn_flags & (NS_ATTN_FLAG_IS_ALIBI8 | NS_ATTN_FLAG_IS_TANH30)) return refuse("attention, shared-prefix decode: ALiBi and the tanh cap are not served");
+  if (const char* text = attn_page_refusal(a, page)) return refuse(text);
+  if (a.step_k_head_size != 1 || a.step_v_head_size != 1 || a.step_k_sl % 8 != 0 || a.step_v_sl % 8 != 0 || a.step_k_head_num % 8 != 0 ||
+      a.step_v_head_num % 8 != 0 || (reinterpret_cast<uintptr_t>(a.K) & 15) != 0 || (reinterpret_cast<uintptr_t>(a.V) & 15) != 0)
+    return refuse("attention, shared-prefix decode: K / V rows must be contiguous in the head dimension and 16-byte aligned");
+  AttnSharedParams& sp = pl.sp;
+  AttnParams& p = sp.a;
+  p.q = a.Q;
+  p.k = reinterpret_cast<const _Float16*>(a.K);
+  p.v = reinterpret_cast<const _Float16*>(a.V);
+  p.dst = a.dst;
+  p.dst16 = static_cast<_Float16*>(const_cast<void*>(dst16));
+  p.qk_scale = a.QK_scale * a.Q_sc * a.K_sc;
+  p.out_scale = a.V_sc / a.dst_sc;
+  p.flags = a.attn_flags;  // (one query row that sees all its live keys: the causal flag changes nothing)
+  p.head_num = a.head_num, p.heads_kv = a.heads_kv, p.head_size = a.head_size, p.sl_q = 1, p.sl_kv = a.sl_kv;
+  p.step_q_bs = a.step_q_bs, p.step_q_head_num = a.step_q_head_num, p.step_q_sl = a.step_q_sl;
+  p.step_k_head_num = a.step_k_head_num, p.step_k_sl = a.step_k_sl, p.step_k_head_size = 1;  // (the pools: no batch step of K or V)
+  p.step_v_head_num = a.step_v_head_num, p.step_v_sl = a.step_v_sl, p.step_v_head_size = 1;
+  p.step_dst_bs = a.step_dst_bs, p.step_dst_head_num = a.step_dst_head_num, p.step_dst_sl = a.step_dst_sl;
+  p.hs_pad = a.head_size;
+  sp.pg = page;
+  sp.group_start = group_start, sp.prefix_keys = prefix_keys, sp.kv_lens = kv_lens, sp.kdelta = kv_len_bias;
+  sp.requests = a.batch_size, sp.groups = groups, sp.max_group = max_group;
+  sp.g_full = a.head_num / a.heads_kv;
+  size_t sb_prefix, sb_suffix;
+  block_paged_ranges(kn, groups, a.heads_kv, sp.g_full, max_group, a.sl_kv, &sb_prefix, &sp.nsp, &sp.kps_p);
+  block_paged_ranges(kn, groups * max_group, a.heads_kv, sp.g_full, 1, a.sl_kv, &sb_suffix, &sp.nss, &sp.kps_s);
+  sp.min_keys = kn.dyn_ranges ? std::max(1, kn.block_min_keys) : 0;
+  int rp, rs;
+  shared_paged_records(kn, a.heads_kv, sp.g_full, max_group, a.sl_kv, &rp, &rs);
+  if (sp.nsp > rp || sp.nss > rs) return refuse("attention, shared-prefix decode: more ranges than one group's (the range rule is not monotonic)");
+  sp.suf_off = rp, sp.rec_stride = rp + rs;
+  pl.hs_pad = p.hs_pad;
+  pl.grid_prefix = dim3(unsigned(sb_prefix * a.heads_kv), unsigned(sp.nsp), unsigned(groups));
+  pl.grid_suffix = dim3(unsigned(sb_suffix * a.heads_kv), unsigned(sp.nss), unsigned(groups * max_group));
+  pl.block = dim3(256);
+  pl.merge_grid = dim3(unsigned(a.head_num), unsigned(a.batch_size));
+  pl.partial_bytes = size_t(a.batch_size) * a.head_num * sp.rec_stride * (2 + a.head_size) * 4;
+  pl.ok = true;
+  return pl;
+}
+
 // ---- prompt-sized query blocks over a paged cache (ns_hip_attn_prefill_paged) ------------------------------------------------------------------------
 // One launch of the 128-row kernel's PAGED instantiation for every call the entry serves: there is no other kernel to give a call to, so one row is a
 // plan like any other.  The instantiation: the padded head size, SB for a biased call and for a score scale that is not positive (SB scales the

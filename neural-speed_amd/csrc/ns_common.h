@@ -399,6 +399,7 @@ bool attn_prepare_moving(hipStream_t st, int batch, int heads, int heads_kv, int
 void touch_gemm_module();
 void touch_gemv_module();
 void touch_attn_module();
+void touch_attn_shared_module();  // ns_attn_shared.hip (a code object of its own)
 void touch_quant_module();
 extern thread_local Affine g_affine;
 // ... and the device-layout attention may be asked for an fp16 copy of its output row beside the fp32 one (the carried norm of the route's
