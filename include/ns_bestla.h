@@ -832,6 +832,23 @@ void ns_hip_attn_decode_paged_shared_stats(unsigned long long out[4]);
 int ns_hip_attn_block_paged_f8(const attn_fp32_fp16_fp16_fp32_fwd_args_t* dparams, const int* dQStart, const int* dKvLens, int kv_len_bias,
                                const int* dBlockTable, int table_stride, int block_keys, int pool_blocks, long long block_step, void* dst16, void* stream);
 void ns_hip_attn_block_paged_f8_stats(unsigned long long out[4]);
+/* ns_hip_attn_decode_paged_shared_f8: SHARED-PREFIX DECODE over an FP8 (E4M3) paged cache — ns_hip_attn_decode_paged_shared's signature and, word for
+ * word, its contract (the groups and their leaders, n_g, P_g rounded down to a block, len_b, idle members written as zeros, requests no group names
+ * left untouched, the table-entry rules, tmp or the stream's scratch, three launches, capturable once, dst16) over THE FP8 POOL described above: K / V
+ * of the block are the pool bases, every stride counts bytes, K_sc / V_sc are the pools' scales, folded as ever (qk_scale = QK_scale * Q_sc * K_sc,
+ * out_scale = V_sc / dst_sc).  The plan (grids, ranges, partials, merge) is the fp16 entry's for the same shape; the partial records are fp32 and laid
+ * out as there, so ns_hip_attn_decode_paged_shared_workspace_size answers for both entries.  The codes are decoded exactly to fp16 and multiplied as
+ * fp16 matrix-core operands, Q is not quantised: the output is what ns_hip_attn_decode_paged_shared gives over fp16 pools holding the same values, up
+ * to the order of fp32 sums.  No byte behind min(P_g, len_b) of the prefix or behind len_b reaches a result.
+ * Refused (-1, ns_hip_last_error set, nothing written): what ns_hip_attn_decode_paged_shared refuses, and in front of it what the FP8 pool adds
+ * (head_size, the row stride, the head stride or block_step not a multiple of 16, a pool base that is not 16-byte aligned, a scale that is not positive
+ * and finite).
+ * ns_hip_attn_decode_paged_shared_f8_stats: [0] prefix / suffix range launches of the head-size-64 kernel (two per call), [1] of the head-size-128
+ * kernel, [2] merge launches, [3] refused calls; the fp16 entry's counters do not move. */
+int ns_hip_attn_decode_paged_shared_f8(const attn_fp32_fp16_fp16_fp32_fwd_args_t* dparams, const int* dGroupStart, int groups, int max_group,
+                                       const int* dPrefixKeys, const int* dKvLens, int kv_len_bias, const int* dBlockTable, int table_stride,
+                                       int block_keys, int pool_blocks, long long block_step, void* dst16, void* stream);
+void ns_hip_attn_decode_paged_shared_f8_stats(unsigned long long out[4]);
 /* ns_hip_rope_qkv_append_paged_seq_f8: ns_hip_rope_qkv_append_paged_seq's arguments plus the two scales, over FP8 pools: the row -> request map and the
  * idle rules of that entry, the rotation and the conversion rule of ns_hip_rope_qkv_append_paged_f8 — a row holds the byte that entry gives it when row
  * r's table row is a copy of request dRowReq[r]'s, and Q holds the same bits.  One launch, capturable; refusals: the seq append's and the FP8 append's. */

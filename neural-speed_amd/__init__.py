@@ -295,6 +295,9 @@ def lib():
         L.ns_hip_attn_decode_paged_shared_workspace_size.argtypes = [i, i, i, i, i, i]
         L.ns_hip_attn_decode_paged_shared_stats.restype = None
         L.ns_hip_attn_decode_paged_shared_stats.argtypes = [vp]
+        L.ns_hip_attn_decode_paged_shared_f8.argtypes = [vp, vp, i, i, vp, vp, i, vp, i, i, i, C.c_longlong, vp, vp]
+        L.ns_hip_attn_decode_paged_shared_f8_stats.restype = None
+        L.ns_hip_attn_decode_paged_shared_f8_stats.argtypes = [vp]
         L.ns_hip_attn_prefill_paged.argtypes = [vp, vp, vp, i, vp, i, i, i, C.c_longlong, vp, vp]
         L.ns_hip_attn_prefill_paged_stats.restype = None
         L.ns_hip_attn_prefill_paged_stats.argtypes = [vp]

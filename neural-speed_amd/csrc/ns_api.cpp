@@ -195,6 +195,7 @@ int ns_hip_warm_up(void) {
       touch_gemv_module();
       touch_attn_module();
       touch_attn_shared_module();
+      touch_attn_shared_f8_module();
       touch_quant_module();
       (void)moe_exp_table();  // the router's exponential table (ns_hip_moe_route): uploaded here, outside any capture
       ns_hip_reset_error();

@@ -195,6 +195,7 @@ __host__ __device__ __forceinline__ int attn_block_q_len(const int* q_start, int
 }
 
 // ---- shared-prefix decode over a paged cache (ns_hip_attn_decode_paged_shared; attn_shared_kernel and its merge, ns_attn_shared.hip) ---------------
+// (and ns_hip_attn_decode_paged_shared_f8 over FP8 pools: attn_shared8_kernel, ns_attn_shared_f8.hip — the same argument block, geometry and records).
 // One query row per request; the caller names GROUPS of consecutive requests whose first `prefix` keys are the same cells.  a: as the paged decode
 // entry reads it (a.sl_q = 1, a.sl_kv = a request's capacity, a.k / a.v the pool bases, Q / dst / dst16 stepped per request by step_q_bs /
 // step_dst_bs).  group_start[groups + 1], prefix_keys[groups], kv_lens[requests] and the table are DEVICE arrays read inside the launches.
@@ -383,10 +384,17 @@ struct AttnSharedPagedPlan {
   dim3 grid_prefix, grid_suffix, block, merge_grid;  // (slot blocks of max_group * g_full slots * kv heads, nsp, groups) x 256; (slot blocks of g_full
                                                      // slots * kv heads, nss, groups * max_group) x 256; (heads, requests) x 128
   size_t partial_bytes = 0;
+  bool f8 = false;  // the pools hold E4M3 codes (attn_shared_paged_f8_plan only: attn_shared8_kernel)
 };
 AttnSharedPagedPlan attn_shared_paged_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst16, const AttnKnobs& knobs, const AttnPage& page,
                                            const int* group_start, int groups, int max_group, const int* prefix_keys, const int* kv_lens, int kv_len_bias,
                                            std::string* why);
+// The plan of ns_hip_attn_decode_paged_shared_f8: the FP8 pool's own refusals (the scales, attn_f8_pool_refusal) first, then the fp16 plan above of the
+// call as it stands, every decision of which is kept (grids, ranges, records, merge grid, partial_bytes), with the kernel family (f8) in place of the
+// fp16 one.  A pure function (tests/test_attn_shared_paged_f8_plan.py).  sp.a.k / .v are the pools' bases: bytes behind the fp16 pointer type.
+AttnSharedPagedPlan attn_shared_paged_f8_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst16, const AttnKnobs& knobs,
+                                              const AttnPage& page, const int* group_start, int groups, int max_group, const int* prefix_keys,
+                                              const int* kv_lens, int kv_len_bias, std::string* why);
 // what ns_hip_attn_decode_paged_shared_workspace_size answers: the plan's partial_bytes, from the shape alone (0: no plan of that shape)
 size_t attn_shared_paged_ws_bytes(const AttnKnobs& knobs, int batch, int head_num, int heads_kv, int head_size, int max_group, int capacity);
 
@@ -419,6 +427,8 @@ hipError_t launch_attn_block_paged(const AttnBlockPagedPlan& pl, float* ws, hipS
 hipError_t launch_attn_block_paged_merge(const AttnBlockPagedParams& pp, dim3 merge_grid, hipStream_t st);  // ns_attn_block.hip: attn_block_paged_merge_kernel over pp.sp.ws
 hipError_t launch_attn_block_paged_f8(const AttnBlockPagedPlan& pl, float* ws, hipStream_t st);  // ns_attn_block_f8.hip: a plan with f8 set + that merge
 hipError_t launch_attn_shared_paged(const AttnSharedPagedPlan& pl, float* ws, hipStream_t st);   // ns_attn_shared.hip: prefix ranges, suffix ranges, merge
+hipError_t launch_attn_shared_merge(const AttnSharedParams& sp, dim3 merge_grid, hipStream_t st);  // ns_attn_shared.hip: attn_shared_merge_kernel over sp.ws
+hipError_t launch_attn_shared_paged_f8(const AttnSharedPagedPlan& pl, float* ws, hipStream_t st);  // ns_attn_shared_f8.hip: a plan with f8 set + that merge
 hipError_t launch_attn_prefill_paged(const AttnPrefillPagedPlan& pl, hipStream_t st);             // ns_attn_prefill.hip: the PAGED instantiations of the 128-row kernel
 hipError_t launch_attn_prefill_paged_f8(const AttnPrefillPagedPlan& pl, hipStream_t st);          // ns_attn_prefill.hip: a plan with f8 set
 hipError_t launch_attn_merge(const AttnSplitParams& sp, unsigned batch, hipStream_t st, bool rows = false);  // ns_attn_decode.hip: attn_merge_kernel over sp.ws

@@ -603,6 +603,29 @@ AttnBlockPagedPlan attn_block_paged_f8_plan(const attn_fp32_fp16_fp16_fp32_fwd_a
   return pl;
 }
 
+// ---- shared-prefix decode over an FP8 paged cache (ns_hip_attn_decode_paged_shared_f8) ---------------------------------------------------------------
+// As above: the FP8 pool's refusals first — so a head size that is a multiple of 8 and not of 16 is refused in the pool's words — and what passes
+// them is a layout the fp16 plan takes as it stands (its alignment rule is implied by the byte rule's multiples of 16; the shared entry has no 32-bit
+// rule to halve).  Everything the fp16 plan decides is kept: the records are fp32 whatever the pools hold.
+AttnSharedPagedPlan attn_shared_paged_f8_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst16, const AttnKnobs& kn, const AttnPage& page,
+                                              const int* group_start, int groups, int max_group, const int* prefix_keys, const int* kv_lens,
+                                              int kv_len_bias, std::string* why) {
+  AttnSharedPagedPlan none;
+  memset(&none.sp, 0, sizeof(none.sp));
+  auto refuse = [&](const char* text) {
+    *why = text;
+    return none;
+  };
+  if (!(a.K_sc > 0.f) || !(a.V_sc > 0.f) || std::isinf(a.K_sc) || std::isinf(a.V_sc))
+    return refuse("attention, FP8 paged cache: K_sc and V_sc, the pools' scales, must be positive and finite");
+  if (a.step_k_head_size != 1 || a.step_v_head_size != 1) return refuse("attention, FP8 paged cache: K / V rows must be contiguous in the head dimension");
+  if (const char* text = attn_f8_pool_refusal(a.head_size, a.step_k_sl, a.step_k_head_num, page.block_step, a.K)) return refuse(text);
+  if (const char* text = attn_f8_pool_refusal(a.head_size, a.step_v_sl, a.step_v_head_num, page.block_step, a.V)) return refuse(text);
+  AttnSharedPagedPlan pl = attn_shared_paged_plan(a, dst16, kn, page, group_start, groups, max_group, prefix_keys, kv_lens, kv_len_bias, why);
+  pl.f8 = pl.ok;
+  return pl;
+}
+
 // ---- prompt-sized query blocks over an FP8 paged cache (ns_hip_attn_prefill_paged_f8) ----------------------------------------------------------------
 // As above: the FP8 pool's refusals first — so a head size that is a multiple of 8 and not of 16 is refused in the pool's words, not the fp16 plan's —
 // and what passes them is a layout the fp16 plan takes as it stands: its alignment rule (row and head strides multiples of 8 elements, 16-byte aligned

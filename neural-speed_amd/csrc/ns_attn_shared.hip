@@ -347,8 +347,11 @@ hipError_t launch_attn_shared_paged(const AttnSharedPagedPlan& pl, float* ws, hi
   else
     hipLaunchKernelGGL((attn_shared_kernel<128, 1>), pl.grid_suffix, pl.block, 0, st, sp);
   e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(attn_shared_merge_kernel, pl.merge_grid, dim3(128), 0, st, sp);
+  return e != hipSuccess ? e : launch_attn_shared_merge(sp, pl.merge_grid, st);
+}
+// the merge alone, over sp.ws: the partials do not know the cache's type (ns_attn_shared_f8.hip launches its own range kernels in front of it)
+hipError_t launch_attn_shared_merge(const AttnSharedParams& sp, dim3 merge_grid, hipStream_t st) {
+  hipLaunchKernelGGL(attn_shared_merge_kernel, merge_grid, dim3(128), 0, st, sp);
   return hipGetLastError();
 }
 void touch_attn_shared_module() { touch_kernel(reinterpret_cast<const void*>(attn_shared_kernel<128, 0>)); }

@@ -400,6 +400,7 @@ void touch_gemm_module();
 void touch_gemv_module();
 void touch_attn_module();
 void touch_attn_shared_module();  // ns_attn_shared.hip (a code object of its own)
+void touch_attn_shared_f8_module();  // ns_attn_shared_f8.hip (likewise)
 void touch_quant_module();
 extern thread_local Affine g_affine;
 // ... and the device-layout attention may be asked for an fp16 copy of its output row beside the fp32 one (the carried norm of the route's
