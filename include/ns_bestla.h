@@ -872,10 +872,11 @@ int ns_hip_rope_qkv_append_paged_seq_f8(float* dQ, const float* dK, const float*
  * Refused (-1, ns_hip_last_error set, nothing written): what ns_hip_attn_decode_paged refuses of the cache's description, a null dQStart or dKvLens,
  * non-PLAIN layouts, batch_size < 1, head_size % 8 != 0 or head_size > 128 (136 .. 256: the 256-wide form of the kernel would spill registers and is
  * not built), head_num % heads_kv != 0, max_q < 1, sl_kv < 1, K / V rows not contiguous in the head dimension or not 16-byte aligned,
- * ceil(max_q / 128) * head_num * batch_size >= 2^31, an ALiBi call whose heads do not fit the head partition. */
+ * ceil(max_q / 128) * head_num * batch_size >= 2^31, an ALiBi call whose heads do not fit the head partition.  Head sizes 136 .. 256 are served by
+ * ns_hip_attn_prefill_paged_wide below. */
 int ns_hip_attn_prefill_paged(const attn_fp32_fp16_fp16_fp32_fwd_args_t* dparams, const int* dQStart, const int* dKvLens, int kv_len_bias,
                               const int* dBlockTable, int table_stride, int block_keys, int pool_blocks, long long block_step, void* dst16, void* stream);
-/* Process-wide counts of ns_hip_attn_prefill_paged: launches by padded head size [0] 64, [1] 128, [2] 256 (none: not built); [3] launches of a
+/* Process-wide counts of ns_hip_attn_prefill_paged: launches by padded head size [0] 64, [1] 128, [2] 256 (none: not built here — ns_hip_attn_prefill_paged_wide); [3] launches of a
  * biased instantiation (score bias or a score scale that is not positive), [4] of a padded one; [5] refused calls. */
 void ns_hip_attn_prefill_paged_stats(unsigned long long out[6]);
 /* ns_hip_attn_prefill_paged_f8: ns_hip_attn_prefill_paged's signature and, word for word, its contract (packed Q / dst / dst16 through dQStart, dKvLens
@@ -894,6 +895,21 @@ void ns_hip_attn_prefill_paged_stats(unsigned long long out[6]);
 int ns_hip_attn_prefill_paged_f8(const attn_fp32_fp16_fp16_fp32_fwd_args_t* dparams, const int* dQStart, const int* dKvLens, int kv_len_bias,
                                  const int* dBlockTable, int table_stride, int block_keys, int pool_blocks, long long block_step, void* dst16, void* stream);
 void ns_hip_attn_prefill_paged_f8_stats(unsigned long long out[6]);
+/* ns_hip_attn_prefill_paged_wide: ns_hip_attn_prefill_paged's signature and, word for word, its contract (packed Q / dst / dst16 through dQStart, dKvLens
+ * + bias, max_q, the causal rule, zero rows, idle requests, the table-entry rules, ONE launch with no `tmp` and no scratch, capturable without a first
+ * eager call) over the fp16 pools at THE HEAD SIZES THAT ENTRY REFUSES: 136, 144, .. 256 (GPT-J, Gemma, 160 / 192-wide models; 136 .. 248 padded to
+ * 256).  A kernel of its own: the 128-row kernel's arithmetic with the 64-key K / V tiles moved pool -> LDS by DMA through one buffer descriptor per
+ * page and wave — a key at or behind kv_len_b, an id outside [0, pool_blocks) and a dim at or past head_size lie outside the descriptor and arrive as
+ * zeros; every cell address is 64-bit.  Unbiased scores only: QK_scale * Q_sc * K_sc must be positive and finite.
+ * Refused (-1, ns_hip_last_error set, nothing written): what ns_hip_attn_prefill_paged refuses of the cache's description, the arrays, the layouts, the
+ * head group, max_q, sl_kv, the K / V rows and the grid; head_size <= 128 (ns_hip_attn_prefill_paged serves those), head_size > 256 or not a multiple
+ * of 8; NS_ATTN_FLAG_IS_ALIBI8, NS_ATTN_FLAG_IS_TANH30 or a score scale that is not positive and finite ("not built at this width"); a block whose
+ * rows of one kv head span 2 GiB or more.
+ * ns_hip_attn_prefill_paged_wide_stats: [0] launches at head size 256, [1] padded launches (136 .. 248), [2] reserved (0), [3] refused calls.  No
+ * other entry's counter moves. */
+int ns_hip_attn_prefill_paged_wide(const attn_fp32_fp16_fp16_fp32_fwd_args_t* dparams, const int* dQStart, const int* dKvLens, int kv_len_bias,
+                                   const int* dBlockTable, int table_stride, int block_keys, int pool_blocks, long long block_step, void* dst16, void* stream);
+void ns_hip_attn_prefill_paged_wide_stats(unsigned long long out[4]);
 
 /* ----------------------------------------------------------------------------------------------
  * Part 4b — mixture-of-experts matmul with the routing on the device.  Device twin of

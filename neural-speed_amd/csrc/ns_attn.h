@@ -293,6 +293,50 @@ __host__ __device__ __forceinline__ long long attn_prefill8_group_base(const Att
   return (long long)blk * pg.block_step + (long long)(first & ((1 << pg.block_shift) - 1)) * step_sl;
 }
 
+// ---- ... at head sizes 136 .. 256 (ns_hip_attn_prefill_paged_wide; attn_wide_paged_kernel, ns_attn_prefill_wide.hip) ------------------------------
+// The argument block is AttnPrefillPagedParams.  A 64-key tile travels pool -> LDS by DMA, 16 bytes per lane and 1 KiB per wave-wide request, through
+// one buffer descriptor per (page, head) and wave: of a tile's keys wave w moves the aligned group 16 w .. 16 w + 15 — inside ONE page, since tiles
+// start at multiples of 64 and a page holds 16 keys or more — in kAwReq requests of K (request u: tile rows 16 w + 2 u, + 1, 512 bytes each) and
+// kAwReq of V (request u: the group's 16 rows x dims 32 u .. 32 u + 31).  THE request rule of that kernel: its issue and
+// tests/tools/attn_prefill_paged_wide_plan_main.cpp both go through the functions below.
+constexpr int kAwReq = 8;                              // requests of K, and of V, per wave and tile
+constexpr int kAwKTile = kA2KB * 512;                  // K image: [64 keys][32 swizzled 16-byte slots]
+constexpr int kAwStage = kAwKTile + 8 * kA2KB * 64;    // + V image: [8 column blocks of 32 dims][64 keys][32 dims]
+constexpr uint32_t kAwNoCell = 0x80000000u;            // a lane offset outside every descriptor (the plan keeps num_records below it): zeros arrive
+// the table slot whose entry serves group g (keys pos0 + 16 g ..) of the tile at pos0: that of the group's first key clamped to the last live one
+__host__ __device__ __forceinline__ int attn_wide_table_slot(const AttnPage& pg, int pos0, int g, int kv_len) {
+  return attn_prefill_tile_key(pos0, 16 * g, kv_len) >> pg.block_shift;
+}
+// The descriptor of wave w's group of the tile at pos0 in physical block id: base = the ELEMENT offset from the pool's base of the group's first row of
+// kv head ihkv, bytes = num_records — through the last live key's last dim and no further; 0 (nothing is addressable) for a group at or behind kv_len
+// and for an id that is no block of the pool.  step_sl / step_head: K's or V's.
+struct AttnWideDesc {
+  long long base;
+  uint32_t bytes;
+};
+__host__ __device__ __forceinline__ AttnWideDesc attn_wide_desc(const AttnPage& pg, int id, int pos0, int w, int kv_len, int ihkv, long long step_sl,
+                                                                long long step_head, int head_size) {
+  const int first = pos0 + 16 * w;
+  const int live = min(max(kv_len - first, 0), 16);
+  if (unsigned(id) >= unsigned(pg.pool_blocks) || live == 0) return {0, 0u};
+  return {(long long)id * pg.block_step + (long long)ihkv * step_head + (long long)(first & ((1 << pg.block_shift) - 1)) * step_sl,
+          uint32_t(((long long)(live - 1) * step_sl + head_size) * 2)};
+}
+// Lane l's byte offset inside that descriptor in request u.  K: the lane writes 16-byte slot l & 31 of the group's row r = 2 u + (l >> 5), which holds
+// the row's chunk slot ^ r (the swizzle of the 128-row kernels at head sizes from 128 on: the row's low four bits).  V: the lane writes piece l & 3 of
+// the 64-byte row l >> 2 of column block u.  A chunk at or past head_size (the padded forms) does not exist: kAwNoCell.
+__host__ __device__ __forceinline__ uint32_t attn_wide_k_offset(int u, int l, long long step_sl, int head_size) {
+  const int r = 2 * u + (l >> 5), chunk = (l & 31) ^ r;
+  return 8 * chunk < head_size ? uint32_t(((long long)r * step_sl + 8 * chunk) * 2) : kAwNoCell;
+}
+__host__ __device__ __forceinline__ uint32_t attn_wide_v_offset(int u, int l, long long step_sl, int head_size) {
+  const int d = 32 * u + 8 * (l & 3);
+  return d < head_size ? uint32_t(((long long)(l >> 2) * step_sl + d) * 2) : kAwNoCell;
+}
+// where request u of wave w lands inside a stage (the DMA then writes lane-linear: + 16 l)
+__host__ __device__ constexpr int attn_wide_k_lds(int w, int u) { return (kAwReq * w + u) * 1024; }
+__host__ __device__ constexpr int attn_wide_v_lds(int w, int u) { return kAwKTile + u * (kA2KB * 64) + w * 1024; }
+
 // ---- the launch decision as a value (ns_attn_plan.cpp) -------------------------------------------------------------------------------------
 // Every tunable the decision reads.  attn_knobs() (ns_attn.cpp) fills it from ns_hip_set_tuning's atomics and the environment.
 struct AttnKnobs {
@@ -417,6 +461,19 @@ AttnPrefillPagedPlan attn_prefill_paged_plan(const attn_fp32_fp16_fp16_fp32_fwd_
 // A pure function (tests/test_attn_prefill_paged_f8_plan.py).  pp.a.k / .v are the pools' bases: bytes behind the fp16 pointer type.
 AttnPrefillPagedPlan attn_prefill_paged_f8_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst16, const AttnKnobs& knobs, const AttnPage& page,
                                                 const int* q_start, const int* kv_lens, int kv_len_bias, std::string* why);
+// The plan of ns_hip_attn_prefill_paged_wide: a pure function like attn_prefill_paged_plan (tests/test_attn_prefill_paged_wide_plan.py), the same
+// reading of a.sl_q / a.sl_kv, the same grid, alignment and XCD rules.  One launch of attn_wide_paged_kernel<pad>; head sizes 136, 144, .. 256 and
+// unbiased scores under a positive finite scale only.  !ok: *why says what is wrong with the call.
+struct AttnPrefillWidePlan {
+  bool ok = false;
+  int pad = 0;  // the template argument: head_size != 256
+  AttnPrefillPagedParams pp;
+  dim3 grid, block;
+  size_t lds = 0;
+  int nqb = 0, aligned = 0, xcd_map = 0;
+};
+AttnPrefillWidePlan attn_prefill_paged_wide_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst16, const AttnKnobs& knobs, const AttnPage& page,
+                                                 const int* q_start, const int* kv_lens, int kv_len_bias, std::string* why);
 
 // ---- launches of a plan ----------------------------------------------------------------------------------------------------------------------
 hipError_t launch_attn_onerow(const AttnPlan& pl, float* ws, uint32_t* tickets, hipStream_t st);  // ns_attn_decode.hip: AP_GENERIC, AP_SPLIT_REGS, AP_RING (+ merge)
@@ -431,6 +488,7 @@ hipError_t launch_attn_shared_merge(const AttnSharedParams& sp, dim3 merge_grid,
 hipError_t launch_attn_shared_paged_f8(const AttnSharedPagedPlan& pl, float* ws, hipStream_t st);  // ns_attn_shared_f8.hip: a plan with f8 set + that merge
 hipError_t launch_attn_prefill_paged(const AttnPrefillPagedPlan& pl, hipStream_t st);             // ns_attn_prefill.hip: the PAGED instantiations of the 128-row kernel
 hipError_t launch_attn_prefill_paged_f8(const AttnPrefillPagedPlan& pl, hipStream_t st);          // ns_attn_prefill.hip: a plan with f8 set
+hipError_t launch_attn_prefill_paged_wide(const AttnPrefillWidePlan& pl, hipStream_t st);          // ns_attn_prefill_wide.hip: attn_wide_paged_kernel
 hipError_t launch_attn_merge(const AttnSplitParams& sp, unsigned batch, hipStream_t st, bool rows = false);  // ns_attn_decode.hip: attn_merge_kernel over sp.ws
 // touch_attn_module (ns_common.h) makes the runtime load every one of these code objects
 inline void touch_kernel(const void* kernel) {

@@ -532,6 +532,76 @@ AttnPrefillPagedPlan attn_prefill_paged_plan(const attn_fp32_fp16_fp16_fp32_fwd_
   return pl;
 }
 
+// ---- ... at head sizes 136 .. 256 (ns_hip_attn_prefill_paged_wide) -----------------------------------------------------------------------------------
+// One launch of attn_wide_paged_kernel<pad> for every call the entry serves.  The refusals of the fp16 entry above come first, in its order and with
+// its texts (the cache, the arrays, the layouts, the head group, the grid), then the width's own: the head sizes of the other entry, the score biases
+// and scales this kernel is not built for, and a page whose rows of one head do not fit one 32-bit buffer descriptor below kAwNoCell.
+AttnPrefillWidePlan attn_prefill_paged_wide_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst16, const AttnKnobs& kn, const AttnPage& page,
+                                                 const int* q_start, const int* kv_lens, int kv_len_bias, std::string* why) {
+  AttnPrefillWidePlan pl;
+  memset(&pl.pp, 0, sizeof(pl.pp));
+  auto refuse = [&](const char* text) {
+    *why = text;
+    return pl;
+  };
+  if (a.Q_layout != ATTN_FWD_LAYOUT_PLAIN || a.K_layout != ATTN_FWD_LAYOUT_PLAIN || a.V_layout != ATTN_FWD_LAYOUT_PLAIN ||
+      a.dst_layout != ATTN_FWD_LAYOUT_PLAIN)
+    return refuse("attention: only ATTN_FWD_LAYOUT_PLAIN tensors are supported");
+  if (!q_start) return refuse("attention, wide prompt blocks over a paged cache: dQStart is null");
+  if (!kv_lens) return refuse("attention, wide prompt blocks over a paged cache: dKvLens is null");
+  if (a.batch_size < 1) return refuse("attention, wide prompt blocks over a paged cache: batch_size (the requests) must be at least 1");
+  if (a.head_size < 8 || a.head_size % 8 != 0 || a.head_size > 256)
+    return refuse("attention, wide prompt blocks over a paged cache: head_size must be a multiple of 8 from 136 to 256");
+  if (a.head_size <= 128)
+    return refuse("attention, wide prompt blocks over a paged cache: head sizes up to 128 are served by ns_hip_attn_prefill_paged");
+  if (a.heads_kv < 1 || a.head_num < 1 || a.head_num % a.heads_kv != 0)
+    return refuse("attention, wide prompt blocks over a paged cache: head_num must be a multiple of heads_kv");
+  if (a.sl_q < 1) return refuse("attention, wide prompt blocks over a paged cache: sl_q is max_q, the most query rows of one request (at least 1)");
+  if (a.sl_kv < 1) return refuse("attention, wide prompt blocks over a paged cache: sl_kv is the capacity of a request (at least 1 key)");
+  if (const char* text = attn_page_refusal(a, page)) return refuse(text);
+  if (a.step_k_head_size != 1 || a.step_v_head_size != 1 || a.step_k_sl % 8 != 0 || a.step_v_sl % 8 != 0 || a.step_k_head_num % 8 != 0 ||
+      a.step_v_head_num % 8 != 0 || (reinterpret_cast<uintptr_t>(a.K) & 15) != 0 || (reinterpret_cast<uintptr_t>(a.V) & 15) != 0)
+    return refuse("attention, wide prompt blocks over a paged cache: K / V rows must be contiguous in the head dimension and 16-byte aligned");
+  const size_t nqb = (size_t(a.sl_q) + 127) / 128, wgs = nqb * size_t(a.head_num) * size_t(a.batch_size);
+  if (wgs >= (size_t(1) << 31))
+    return refuse("attention, wide prompt blocks over a paged cache: ceil(max_q / 128) * head_num * batch_size must stay below 2^31 workgroups");
+  const float qk_scale = a.QK_scale * a.Q_sc * a.K_sc;
+  if (a.attn_flags & (NS_ATTN_FLAG_IS_ALIBI8 | NS_ATTN_FLAG_IS_TANH30))
+    return refuse("attention, wide prompt blocks over a paged cache: ALiBi and the tanh cap are not built at this width");
+  if (!(qk_scale > 0.f) || !std::isfinite(qk_scale))
+    return refuse("attention, wide prompt blocks over a paged cache: a score scale that is not positive and finite is not built at this width");
+  // a page's rows of one head under one descriptor: the last key's last byte, and every lane offset with it, below kAwNoCell
+  const long long last = (1ll << page.block_shift) - 1;
+  if ((last * std::max(a.step_k_sl, a.step_v_sl) + a.head_size) * 2 >= (long long)kAwNoCell)
+    return refuse("attention, wide prompt blocks over a paged cache: a block's rows of one kv head must lie within 2 GiB (one buffer descriptor per page and head)");
+  AttnParams& p = pl.pp.a;
+  p.q = a.Q;
+  p.k = reinterpret_cast<const _Float16*>(a.K);
+  p.v = reinterpret_cast<const _Float16*>(a.V);
+  p.dst = a.dst;
+  p.dst16 = static_cast<_Float16*>(const_cast<void*>(dst16));
+  p.qk_scale = qk_scale;
+  p.out_scale = a.V_sc / a.dst_sc;
+  p.flags = a.attn_flags;
+  p.head_num = a.head_num, p.heads_kv = a.heads_kv, p.head_size = a.head_size, p.sl_q = a.sl_q, p.sl_kv = a.sl_kv;
+  p.step_q_head_num = a.step_q_head_num, p.step_q_sl = a.step_q_sl;  // (packed rows: no batch step of Q or dst; the pools: none of K or V)
+  p.step_k_head_num = a.step_k_head_num, p.step_k_sl = a.step_k_sl, p.step_k_head_size = 1;
+  p.step_v_head_num = a.step_v_head_num, p.step_v_sl = a.step_v_sl, p.step_v_head_size = 1;
+  p.step_dst_head_num = a.step_dst_head_num, p.step_dst_sl = a.step_dst_sl;
+  p.hs_pad = 256;
+  pl.pp.pg = page, pl.pp.q_start = q_start, pl.pp.kv_lens = kv_lens, pl.pp.kdelta = kv_len_bias;
+  pl.pad = a.head_size != 256;
+  pl.nqb = int(nqb);
+  pl.grid = dim3(unsigned(wgs));
+  pl.block = dim3(256);
+  pl.lds = size_t(2) * kAwStage;
+  pl.aligned = (reinterpret_cast<uintptr_t>(a.dst) & 15) == 0 && a.step_dst_sl % 4 == 0 && a.step_dst_head_num % 4 == 0 &&
+               (!dst16 || (reinterpret_cast<uintptr_t>(dst16) & 7) == 0);
+  pl.xcd_map = !kn.no_xcd_map && (size_t(a.heads_kv) * a.batch_size) % 8 == 0;  // (attn_prefill_paged_plan's rule)
+  pl.ok = true;
+  return pl;
+}
+
 // ---- decode over an FP8 paged cache (ns_hip_attn_decode_paged_f8) ------------------------------------------------------------------------------------
 const char* attn_f8_pool_refusal(int head_size, long long step_sl, long long step_head, long long block_step, const void* pool) {
   if (head_size < 16 || head_size % 16 != 0) return "FP8 paged cache: head_size must be a multiple of 16";
