@@ -1,6 +1,7 @@
 """attn_block_paged_f8_plan (neural-speed_amd/csrc/ns_attn_plan.cpp: what ns_hip_attn_block_paged_f8 launches).  A host program
 (tests/tools/attn_block_paged_f8_plan_main.cpp, built with the library's compiler, nothing launched) prints the FP8 plan beside attn_block_paged_plan of
 the same shape over 486 shapes, and the FP8 plan of each refused call."""
+import importlib.util
 import os
 import subprocess
 
@@ -13,19 +14,42 @@ MAIN = os.path.join(ROOT, "tests", "tools", "attn_block_paged_f8_plan_main.cpp")
 
 
 @pytest.fixture(scope="module")
-def lines(tmp_path_factory):
+def exe(tmp_path_factory):
     hipcc = compiler()
     if not hipcc:
         pytest.skip("the library's compiler is not installed")
     exe = str(tmp_path_factory.mktemp("attn_block_paged_f8_plan") / "attn_block_paged_f8_plan")
     subprocess.run([hipcc, "-std=c++20", "-x", "hip", "--offload-arch=gfx950", "--cuda-host-only", "-Wall", "-Werror", "-I", CSRC, MAIN, "-o", exe],
                    check=True, capture_output=True, text=True, timeout=300)
+    return exe
+
+
+def run(exe, *args):
     res = {"plan": [], "refuse": []}
-    for line in subprocess.run([exe], check=True, capture_output=True, text=True, timeout=120).stdout.splitlines():
+    for line in subprocess.run([exe] + [str(x) for x in args], check=True, capture_output=True, text=True, timeout=120).stdout.splitlines():
         kind, rest = line.split(" ", 1)
         parts = rest.split(" | ")
         res[kind].append(({k: num(v) for k, v in (kv.split("=") for kv in parts[0].split())},) + tuple(fields(p) for p in parts[1:]))
     return res
+
+
+@pytest.fixture(scope="module")
+def lines(exe):
+    return run(exe)
+
+
+def test_the_pool_of_the_far_address_test_takes_the_kernel_it_asserts(exe):
+    """tests/test_gpu_attn_block_paged_f8.py asserts attn_block_split8_kernel<128> through ns_hip_attn_block_paged_f8_stats on a pool of 2^20 + 64 blocks
+    of 4096 bytes: accepted as the FP8 family with the caller's pool (no 32-bit rule: 64-bit addresses).  Numbers: tests/tools/attn_far_layout.py."""
+    spec = importlib.util.spec_from_file_location("attn_far_layout", os.path.join(ROOT, "tests", "tools", "attn_far_layout.py"))
+    FL = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(FL)
+    step = FL.block_step(128, 16)
+    assert step == 4096 and FL.F8_BLOCKS * step > 1 << 32
+    (i, o, r), = run(exe, "far", 128, 16, FL.PAGED_CAP[16], len(FL.BLOCK_Q), max(FL.BLOCK_Q), FL.F8_BLOCKS, step, *FL.strides("pm", 128, 16))["plan"]
+    assert i["what"] == "far" and (o["ok"], o["f8"], o["why"], o["hs_pad"]) == (1, 1, "", 128), o
+    assert (o["blocks"], o["bstep"], o["ksl"], o["khead"], o["vsl"], o["vhead"]) == (FL.F8_BLOCKS, step, 256, 128, 256, 128), o
+    assert {k: (o[k], r[k]) for k in o if k != "f8" and o[k] != r[k]} == {}
 
 
 def test_the_f8_plan_is_the_fp16_block_plan_but_for_the_family(lines):

@@ -3,6 +3,7 @@ kernel moves K / V tiles pool -> LDS by DMA, one buffer descriptor per page and 
 attn_wide_v_offset, attn_wide_k_lds / attn_wide_v_lds, ns_attn.h).  A host program (tests/tools/attn_prefill_paged_wide_plan_main.cpp, built with the
 library's compiler, nothing launched) prints the plans of a grid of calls, the refusals, and — for a few tables with junk behind the live blocks and
 bad ids inside them — every (tile, wave, request, lane) with its descriptor, lane offset and LDS slot; the rules are written out again here."""
+import importlib.util
 import os
 import subprocess
 
@@ -16,15 +17,18 @@ KB, STAGE, NO_CELL = 64, 65536, 1 << 31  # keys per tile, bytes per stage (K 32 
 
 
 @pytest.fixture(scope="module")
-def lines(tmp_path_factory):
+def exe(tmp_path_factory):
     hipcc = compiler()
     if not hipcc:
         pytest.skip("the library's compiler is not installed")
     exe = str(tmp_path_factory.mktemp("attn_prefill_paged_wide_plan") / "attn_prefill_paged_wide_plan")
     subprocess.run([hipcc, "-std=c++20", "-x", "hip", "--offload-arch=gfx950", "--cuda-host-only", "-Wall", "-Werror", "-I", CSRC, MAIN, "-o", exe],
                    check=True, capture_output=True, text=True, timeout=300)
-    out = subprocess.run([exe], check=True, capture_output=True, text=True, timeout=120).stdout
-    res = {"plan": [], "refuse": [], "walk": []}
+    return exe
+
+
+def parse(out):
+    res = {"plan": [], "refuse": [], "walk": [], "far": []}
     for line in out.splitlines():
         kind, rest = line.split(" ", 1)
         head, tail = rest.split(" |", 1)
@@ -36,6 +40,18 @@ def lines(tmp_path_factory):
             o["why"] = why.strip()
             res[kind].append((kv(head), o))
     return res
+
+
+@pytest.fixture(scope="module")
+def lines(exe):
+    return parse(subprocess.run([exe], check=True, capture_output=True, text=True, timeout=120).stdout)
+
+
+def far_layout():
+    spec = importlib.util.spec_from_file_location("attn_far_layout", os.path.join(ROOT, "tests", "tools", "attn_far_layout.py"))
+    FL = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(FL)
+    return FL
 
 
 def test_the_plan_fields_follow_the_rule(lines):
@@ -128,3 +144,62 @@ def test_the_walk_requests_every_live_cell_once_and_nothing_else(lines):
         for (pos0, which), got in slots.items():
             assert sorted(got) == list(range(which * KB * 512, (which + 1) * KB * 512, 16)), (h, pos0, which)
     assert bad_inside > 0 and padded > 0
+
+
+def far_call(exe, FL, hs, blocks, block_step, step_sl, step_head, bs=3, max_q=130, cap=None):
+    args = ["far", hs, FL.WIDE_BK, cap or FL.WIDE_CAP, bs, max_q, blocks, block_step, step_sl, step_head]
+    (i, o), = parse(subprocess.run([exe] + [str(x) for x in args], check=True, capture_output=True, text=True, timeout=60).stdout)["far"]
+    assert (i["hs"], i["blocks"], i["step"], i["stepsl"], i["stephead"]) == (hs, blocks, block_step, step_sl, step_head)
+    return o
+
+
+def test_the_pools_of_the_far_address_tests_take_the_kernels_they_assert(exe):
+    """tests/test_gpu_attn_far_addresses.py asserts these instantiations through ns_hip_attn_prefill_paged_wide_stats on pools of 1.4 * 2^31 elements,
+    position-major and head-major, and at the boundary of the descriptor rule: row step s is accepted, s + 8 refused.  If the rule moves, this fails
+    first, with the reason; the numbers are those of tests/tools/attn_far_layout.py."""
+    FL = far_layout()
+    live = [ceil_div(n, FL.WIDE_BK) for n in FL.WIDE_KV]
+    for hs in FL.WIDE_HS:
+        for layout in ("pm", "hm"):
+            g = FL.paged_layout("over", hs, FL.WIDE_BK, live, layout)
+            o = far_call(exe, FL, hs, g["pool_blocks"], g["block_step"], g["step_sl"], g["step_head"])
+            assert (o["ok"], o["pad"], o["why"]) == (1, int(hs != 256), ""), (hs, layout, o)
+    s, t = FL.wide_edge_steps(256)
+    assert (15 * s + 256) * 2 < NO_CELL <= (15 * t + 256) * 2  # the plan's rule restated: last = 15 at blocks of 16
+    for step_sl, ok in ((s, 1), (t, 0)):
+        g = FL.wide_edge_layout(256, step_sl)
+        o = far_call(exe, FL, 256, g["pool_blocks"], g["block_step"], g["step_sl"], g["step_head"], bs=2, max_q=max(FL.EDGE_Q), cap=2 * FL.EDGE_BK)
+        assert o["ok"] == ok and o["pad"] == 0, (step_sl, o)
+        assert o["why"] == "" if ok else "a block's rows of one kv head must lie within 2 GiB" in o["why"], (step_sl, o)
+
+
+def test_the_walk_at_the_descriptor_boundary_addresses_every_live_key_in_64_bits(exe):
+    """the boundary pools' two requests, both kv heads: for every lane whose 16 bytes lie inside num_records, descriptor base + lane offset is
+    attn_page_at of that lane's key (+ the head, + the chunk) — block 2's beyond 2^31 elements, the last rows' offsets just below 2^31 bytes"""
+    FL = far_layout()
+    g = FL.wide_edge_layout(256)
+    s, hs, top = g["step_sl"], 256, 0
+    for table, n in zip(FL.EDGE_TABLE, FL.EDGE_KV):
+        for ihkv in range(FL.HKV):
+            args = ["walk", hs, FL.EDGE_BK, n, g["pool_blocks"], g["block_step"], s, g["step_head"], ihkv] + table
+            (h, cells), = parse(subprocess.run([exe] + [str(x) for x in args], check=True, capture_output=True, text=True, timeout=60).stdout)["walk"]
+            assert (h["step"], h["stepsl"], h["stephead"]) == (g["block_step"], s, g["step_head"]) and len(cells) == 4 * 2 * 8 * 64
+            seen = set()
+            for pos0, w, which, u, l, slot, ident, base, nbytes, offset, lds in cells:
+                if offset + 16 > nbytes:
+                    assert offset >= nbytes  # wholly outside: zeros
+                    continue
+                if which == 0:
+                    row, chunk = lds // 512, (lds % 512 // 16) ^ (lds // 512 & 15)
+                else:
+                    v = lds - KB * 512
+                    row, chunk = v % 4096 // 64, 4 * (v // 4096) + v % 64 // 16
+                key = pos0 + row
+                assert key < n and ident == table[key // 16] and offset < NO_CELL and nbytes < NO_CELL
+                page_at = ident * g["block_step"] + (key % 16) * s  # attn_page_at (ns_attn.h)
+                assert 2 * base + offset == 2 * (page_at + ihkv * g["step_head"] + 8 * chunk), (key, ihkv, chunk)
+                assert any(o <= base + offset // 2 and base + offset // 2 + 8 <= o + m for o, m in g["extents"] if o // g["block_step"] == ident)
+                seen.add((which, key, chunk))
+                top = max(top, offset)
+            assert seen == {(which, key, c) for which in (0, 1) for key in range(n) for c in range(hs // 8)}
+    assert top == (15 * s + hs) * 2 - 16 and top < NO_CELL  # the last offset the rule allows is asked for

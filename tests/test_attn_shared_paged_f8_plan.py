@@ -1,5 +1,6 @@
 """attn_shared_paged_f8_plan (ns_attn_plan.cpp: what ns_hip_attn_decode_paged_shared_f8 launches).  tests/tools/attn_shared_paged_f8_plan_main.cpp, a
 host program, prints the FP8 plan beside attn_shared_paged_plan of the same call: ten accepted calls, then every refusal."""
+import importlib.util
 import subprocess
 
 import pytest
@@ -16,15 +17,39 @@ FP16 = {"head_size_80": "head_size must be 64 or 128", "alibi_tanh": "ALiBi and 
 
 
 @pytest.fixture(scope="module")
-def lines(tmp_path_factory):
+def exe(tmp_path_factory):
     hipcc = compiler()
     if not hipcc:
         pytest.skip("the library's compiler is not installed")
     exe = str(tmp_path_factory.mktemp("attn_shared_paged_f8_plan") / "attn_shared_paged_f8_plan")
     subprocess.run([hipcc, "-std=c++20", "-x", "hip", "--offload-arch=gfx950", "--cuda-host-only", "-Wall", "-Werror", "-I", CSRC, MAIN, "-o", exe],
                    check=True, capture_output=True, text=True, timeout=300)
-    out = subprocess.run([exe], check=True, capture_output=True, text=True, timeout=120).stdout.splitlines()
+    return exe
+
+
+def run(exe, *args):
+    out = subprocess.run([exe] + [str(x) for x in args], check=True, capture_output=True, text=True, timeout=120).stdout.splitlines()
     return [(what, fields(o), fields(r)) for what, o, r in (line.split(" | ") for line in out)]
+
+
+@pytest.fixture(scope="module")
+def lines(exe):
+    return run(exe)
+
+
+def test_the_pool_of_the_far_address_test_takes_the_kernel_it_asserts(exe):
+    """tests/test_gpu_attn_shared_paged_f8.py asserts attn_shared8_kernel<128> through ns_hip_attn_decode_paged_shared_f8_stats on a pool of 2^20 + 64
+    blocks of 4096 bytes: accepted as the FP8 family with the caller's pool (no 32-bit rule: 64-bit addresses).  Numbers: tests/tools/attn_far_layout.py."""
+    spec = importlib.util.spec_from_file_location("attn_far_layout", ROOT + "/tests/tools/attn_far_layout.py")
+    FL = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(FL)
+    step = FL.block_step(128, FL.SHARED_BK)
+    assert step == 4096 and FL.F8_BLOCKS * step > 1 << 32
+    (what, o, r), = run(exe, "far", 128, FL.SHARED_BK, FL.SHARED_CAP, len(FL.SHARED_LENS), len(FL.SHARED_PREFIX), FL.SHARED_MAX_GROUP, FL.F8_BLOCKS, step,
+                        *FL.strides("pm", 128, FL.SHARED_BK))
+    assert what == "far" and (o["ok"], o["f8"], o["why"], o["hspad"]) == (1, 1, "", 128), o
+    assert (o["blocks"], o["bstep"], o["ksl"], o["khead"], o["vsl"], o["vhead"]) == (FL.F8_BLOCKS, step, 256, 128, 256, 128), o
+    assert {k: (o[k], r[k]) for k in o if k != "f8" and o[k] != r[k]} == {}
 
 
 def test_the_f8_plan_is_the_fp16_shared_plan_but_for_the_family(lines):

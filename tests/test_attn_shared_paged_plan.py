@@ -3,6 +3,7 @@ workgroups and its merge run (attn_block_live, ns_attn.h), printed by a host pro
 rules are written out again here.  Both kinds of range follow the block-split kernel's rule: ceil(512 / workgroups per range) ranges, 128 keys or more
 each, 64 at the most, whole 64-key blocks; workgroups per range: prefix kv heads * ceil(max_group * g / 64) * groups, suffix kv heads * ceil(g / 64) *
 (groups * max_group).  The records of a (request, head) are laid out for ONE group, so the workspace is a function of the shape alone."""
+import importlib.util
 import os
 import subprocess
 
@@ -19,15 +20,24 @@ def ceil_div(a, b):
 
 
 @pytest.fixture(scope="module")
-def lines(tmp_path_factory):
+def exe(tmp_path_factory):
     hipcc = compiler()
     if not hipcc:
         pytest.skip("the library's compiler is not installed")
     exe = str(tmp_path_factory.mktemp("attn_shared_paged_plan") / "attn_shared_paged_plan")
     subprocess.run([hipcc, "-std=c++20", "-x", "hip", "--offload-arch=gfx950", "--cuda-host-only", "-Wall", "-Werror", "-I", CSRC, MAIN, "-o", exe],
                    check=True, capture_output=True, text=True, timeout=300)
-    res = {"plan": [], "refuse": [], "live": []}
-    for line in subprocess.run([exe], check=True, capture_output=True, text=True, timeout=120).stdout.splitlines():
+    return exe
+
+
+@pytest.fixture(scope="module")
+def lines(exe):
+    return parse(subprocess.run([exe], check=True, capture_output=True, text=True, timeout=120).stdout)
+
+
+def parse(out):
+    res = {"plan": [], "refuse": [], "live": [], "far": []}
+    for line in out.splitlines():
         kind, rest = line.split(" ", 1)
         head, tail = rest.split(" |", 1)
         body, _, why = tail.partition(" why=")
@@ -69,6 +79,26 @@ def test_each_refusal_names_its_reason(lines):
             "alibi": "ALiBi and the tanh cap are not served", "grid_limit_members": "groups * max_group above the grid limit",
             "capacity": "must equal table_stride * block_keys"}
     assert set(got) == set(want) and all(text in got[what]["why"] for what, text in want.items()), got
+
+
+def test_the_pools_of_the_far_address_tests_take_the_kernels_they_assert(exe):
+    """tests/test_gpu_attn_far_addresses.py asserts attn_shared_kernel<64 / 128> through ns_hip_attn_decode_paged_shared_stats on pools of 1.4 * 2^31
+    elements — position-major, and head-major with a gap behind every block: both are accepted as they are (the plan has no 32-bit rule: the kernels
+    read through 64-bit pointers), with the caller's block_step and strides.  The numbers are those of tests/tools/attn_far_layout.py."""
+    spec = importlib.util.spec_from_file_location("attn_far_layout", os.path.join(ROOT, "tests", "tools", "attn_far_layout.py"))
+    FL = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(FL)
+    live = [ceil_div(n, FL.SHARED_BK) for n in FL.SHARED_LENS]
+    for hs in FL.SHARED_HS:
+        for layout, gap in (("pm", False), ("hm", True)):
+            g = FL.paged_layout("over", hs, FL.SHARED_BK, live, layout, gap)
+            assert not FL.page_in32(g["pool_blocks"], g["block_step"]) and (g["block_step"] > g["cells"]) == gap
+            args = ["far", hs, FL.SHARED_BK, FL.SHARED_CAP, len(FL.SHARED_LENS), len(FL.SHARED_PREFIX), FL.SHARED_MAX_GROUP, g["pool_blocks"], g["block_step"],
+                    g["step_sl"], g["step_head"]]
+            (i, o), = parse(subprocess.run([exe] + [str(x) for x in args], check=True, capture_output=True, text=True, timeout=60).stdout)["far"]
+            assert (o["ok"], o["why"], o["hspad"]) == (1, "", hs) and i["blocks"] == g["pool_blocks"], (hs, layout, o)
+            assert (o["bstep"], o["ksl"], o["khead"]) == (g["block_step"], g["step_sl"], g["step_head"]), (hs, layout, o)
+            assert o["pgrid"][2] == 1 and o["sgrid"][2] == FL.SHARED_MAX_GROUP  # one group, three member slots
 
 
 def test_the_live_ranges_tile_the_prefix_and_the_suffix(lines):

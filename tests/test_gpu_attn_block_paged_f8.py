@@ -260,3 +260,63 @@ def test_chunked_prefill_on_an_f8_pool(L, pkg, nso):
     ref, model = nso.attn_ref(qr, kb, vb, scale, CAUSAL), rounding_model(qr, kb, vb, scale, CAUSAL)
     for lo, hi in ((0, 64), (64, 128), (128, 150)):
         check(nso, "chunk rows %d..%d of the prompt on an FP8 pool" % (lo, hi - 1), out[:, lo:hi], ref[:, lo:hi], model[:, lo:hi])
+
+
+# ---- 5. a pool just over 2^32 bytes ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mode,n_dims", [(0, 128), (2, 64)])
+def test_far_pool_is_bit_equal_to_the_compact_twin(L, pkg, nso, mode, n_dims):
+    """The ragged step of tests/test_gpu_attn_far_addresses.py (q lens 1 / 5 / 40 over kv lens 70 / 200 / 120, 4 / 2 heads of 128, blocks of 16 = 4096
+    bytes, partials in the caller's workspace) on FarPools8 of tests/test_gpu_attn_paged_f8.py: an untouched pool of 2^20 + 64 blocks, every live block
+    but block 2 above 2^32 bytes.  Request 0's last key is written by ns_hip_rope_qkv_append_paged_seq_f8 in both twins (mode 0; NeoX pairs over half
+    the head).  The compact twin meets the reference over the pool's decoded contents and the fp16 entry; the far run holds its bits — the output,
+    the rotated Q and every live block — consumes no 0x7f byte and changes none."""
+    import torch
+    from test_gpu_attn_far_addresses import FL, need, release, same_bits
+    from test_gpu_attn_paged_f8 import FarPools8
+    hs, bk, (qs, ks, vs, ds) = 128, 16, (1.0, 0.125, 0.125, 1.0)
+    c = Rag8(nso, FL.HN, FL.HKV, hs, FL.PAGED_CAP[bk], FL.BLOCK_Q, FL.BLOCK_KV[bk])
+    live, n0 = [-(-n // bk) for n in c.kvlens], c.kvlens[0]
+    rng = np.random.default_rng(500 + mode)
+    q1, k1, v1 = (torch.from_numpy(rng.standard_normal((1, h, hs)).astype(np.float32)).cuda() for h in (c.hn, c.hkv, c.hkv))
+    dpos, dreq = torch.tensor([n0 - 1], dtype=torch.int32, device="cuda"), torch.zeros(1, dtype=torch.int32, device="cuda")
+    ws = L.ns_hip_attn_block_paged_workspace_size(c.bs, c.hn, c.hkv, hs, max(c.qlens), c.cap)
+    assert ws > 0
+    need(2 * FL.F8_BLOCKS * FL.block_step(hs, bk))
+    got, p, tmp = [], None, None
+    try:
+        tmp = torch.empty(ws, dtype=torch.uint8, device="cuda")
+        for blocks in (FL.pool_blocks("near", FL.block_step(hs, bk), sum(live)) + 128, FL.F8_BLOCKS):
+            p = FarPools8(blocks, c, bk, live)
+            assert blocks < 1 << 20 or all(i == 2 or i * p.block_step >= 1 << 32 for i in p.ids.values())
+            for b, n in enumerate(c.kvlens):
+                p.put(b, c.kc[b, :n - (b == 0)], c.vc[b, :n - (b == 0)])
+            dq = q1.clone()
+            pkg.check(L.ns_hip_rope_qkv_append_paged_seq_f8(dq.data_ptr(), k1.data_ptr(), v1.data_ptr(), p.kp, p.vp, 1, c.hn, c.hkv, hs, dpos.data_ptr(), c.cap, n_dims,
+                                                            mode, 10000.0, 0.75, 0.0, 1.1, dreq.data_ptr(), c.bs, *p.table_args(), p.step_sl, p.step_head, ks, vs,
+                                                            stream_ptr()))
+            s0 = block8_stats(L)
+            out = run_block8(L, pkg, c, p, tmp=tmp)[0]
+            assert delta(s0, block8_stats(L)) == [0, 1, 1, 0], blocks
+            cells, clean = p.live()
+            assert clean and np.all(np.isfinite(out)), blocks
+            got.append((out, dq.cpu().numpy(), cells))
+            p = None
+            release()
+        (on, qn, cn), (of, qf, cf) = got
+        # the near twin against the reference and the fp16 entry: the step with request 0's last key as the pool holds it
+        last = [x.reshape(bk, c.hkv, hs)[(n0 - 1) % bk] for x in cn[(0, (n0 - 1) // bk)]]
+        assert all(NAN8 not in x for x in last)
+        kc, vc = c.kc.copy(), c.vc.copy()
+        kc[0, n0 - 1], vc[0, n0 - 1] = last
+        c2 = Rag8(nso, FL.HN, FL.HKV, hs, FL.PAGED_CAP[bk], FL.BLOCK_Q, FL.BLOCK_KV[bk], codes=lambda shape: (kc, vc))
+        assert np.array_equal(c2.q, c.q)
+        check_rag(nso, "far addresses, near twin: block_paged_f8 after append_paged_seq_f8 mode %d" % mode, c2, on)
+        half = run_block(L, pkg, c2, pools_pair(c2, bk, PM)[1])[0]
+        rows = slice(c.start[0], c.start[-1])
+        e = nso.rel_l2(on[rows], half[rows])
+        assert e < 2e-4, e
+        assert same_bits(on, of) and same_bits(qn, qf) and not same_bits(qn, q1.cpu().numpy())
+        assert all(same_bits(cn[key][x], cf[key][x]) for key in cn for x in (0, 1))
+    finally:
+        p = tmp = None
+        release()

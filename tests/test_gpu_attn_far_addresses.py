@@ -11,6 +11,11 @@ Alias traps: 0x7f bytes (an fp16 NaN) lie where a truncated address would land â
 (tests/tools/attn_far_layout.py, aliases) â€” and directly before and after every live block or slab; the layout asserts on the host that no trap
 touches live data.  A read of a trap shows as NaN in the output, a write as a changed trap.
 
+The shared-prefix step and the wide prompt blocks (head sizes 136 .. 256, with the boundary of their own descriptor rule) have their far twins here; the
+FP8 shared step and the FP8 ragged blocks with their append have theirs in tests/test_gpu_attn_shared_paged_f8.py and
+tests/test_gpu_attn_block_paged_f8.py, beside the FP8 pools they use.  tests/test_attn_far_layout.py shows on the host which address mistakes the
+traps of these layouts catch.
+
 Not pinned, and why: the prefill calls past the slab rule run attn_mfma2_kernel, which only the environment variable NS_ATTN_PIPE selects for a
 compact buffer â€” those far runs have no bit twin and are held to check() against the reference alone."""
 import contextlib
@@ -25,7 +30,9 @@ import pytest
 from test_gpu_attention_paths import check, rounding_model
 from test_gpu_attn_block_paged import Rag, block_stats, check_rag, run_block
 from test_gpu_attn_paged import delta, family, paged_stats, run_paged
+from test_gpu_attn_prefill_paged_wide import run_wide, wide_stats
 from test_gpu_attn_rows import CAUSAL, Case, attn_stats, check_case, rows_stats, stream_ptr
+from test_gpu_attn_shared_paged import Step, check_step, run_shared, shared_stats
 
 pytestmark = pytest.mark.gpu
 _spec = importlib.util.spec_from_file_location("attn_far_layout", os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools", "attn_far_layout.py"))
@@ -109,21 +116,21 @@ class Pages:
     blocks start as NaN (0xFFFF); traps around them, at their aliases and in block 0, which the table entries behind a live length name.  Has the
     attributes run_paged / run_block (tests/test_gpu_attn_paged.py, test_gpu_attn_block_paged.py) read of their Pools."""
 
-    def __init__(self, size, hs, bk, live):
+    def __init__(self, size, hs, bk, live, layout="pm", gap=False):
+        """layout "hm": head-major blocks [kv head][key][dim]; gap: block_step is a block's cells + 8 * hs, the gap cells traps (FL.paged_layout)"""
         import torch
+        g = FL.paged_layout(size, hs, bk, live, layout, gap)
         self.hs, self.bk, self.ts = hs, bk, FL.PAGED_CAP[bk] // bk
-        self.block_step = step = FL.block_step(hs, bk)
-        self.step_sl, self.step_head = HKV * hs, hs
-        self.pool_blocks = FL.pool_blocks(size, step, sum(live))
-        self.table, self.ids = FL.place(live, self.ts, self.pool_blocks)
+        self.block_step = step = g["block_step"]
+        self.step_sl, self.step_head = g["step_sl"], g["step_head"]
+        self.pool_blocks, self.table, self.ids = g["pool_blocks"], g["table"].copy(), g["ids"]
         high = [i for i in self.ids.values() if i != 2]
         assert size != "under" or all(E31 <= 2 * i * step < E32 for i in high)  # byte offsets a signed or wrapped 32-bit value cannot hold
         assert size != "over" or all(i * step > E31 for i in high)
-        total = self.pool_blocks * step
+        total, extents = g["total"], g["extents"]
         if size != "near":
             need(4 * total)
-        extents = [(i * step, step) for i in self.ids.values()]
-        self.k, self.v = (Far(total, extents, step, dead=[(0, step)], traps=size != "near") for _ in range(2))
+        self.k, self.v = (Far(total, extents, g["strip"], dead=g["dead"], traps=size != "near") for _ in range(2))
         for x in (self.k, self.v):
             for off, n in extents:
                 x.buf[off:off + n].fill_(s16(NAN16))
@@ -138,13 +145,23 @@ class Pages:
         for b, n in enumerate(lens):
             for j in range(-(-n // self.bk)):
                 cnt, off = min(self.bk, n - j * self.bk), self.ids[(b, j)] * self.block_step
-                self.k.put(off, (self.step_sl, self.hs, 1), k[b, j * self.bk:j * self.bk + cnt])
-                self.v.put(off, (self.step_sl, self.hs, 1), v[b, j * self.bk:j * self.bk + cnt])
+                self.k.put(off, (self.step_sl, self.step_head, 1), k[b, j * self.bk:j * self.bk + cnt])
+                self.v.put(off, (self.step_sl, self.step_head, 1), v[b, j * self.bk:j * self.bk + cnt])
+        return self
+
+    def share_prefix(self, members):
+        """the shared-prefix tables: {request: (leader, prefix keys)} â€” a member's entries below its prefix name the leader's blocks; its own blocks
+        there, which no entry names any more, stay NaN (fill_keys is given lens that leave them out)"""
+        import torch
+        for b, (leader, P) in members.items():
+            if b != leader:
+                self.table[b, :P // self.bk] = self.table[leader, :P // self.bk]
+        self.dt = torch.from_numpy(self.table).cuda()
         return self
 
     def blocks(self):
         """{(request, logical block): (K block, V block)} as uint16 [bk][HKV][hs]"""
-        shape, strides = (self.bk, HKV, self.hs), (self.step_sl, self.hs, 1)
+        shape, strides = (self.bk, HKV, self.hs), (self.step_sl, self.step_head, 1)
         return {key: (self.k.get(i * self.block_step, shape, strides), self.v.get(i * self.block_step, shape, strides)) for key, i in self.ids.items()}
 
     def keys(self, b, n):
@@ -240,6 +257,156 @@ def test_block_paged(L, pkg, nso, size, hs, bk):
         assert far.traps_intact()
     finally:
         near = far = tmp = None
+        release()
+
+
+# ---- the shared-prefix step -----------------------------------------------------------------------------------------------------------------------------
+SHARED_FORMS = {"position_major": ("pm", False), "head_major_gapped_blocks": ("hm", True)}
+
+
+@pytest.mark.parametrize("form", list(SHARED_FORMS))
+@pytest.mark.parametrize("hs", FL.SHARED_HS)
+def test_decode_paged_shared(L, pkg, nso, hs, form):
+    """ns_hip_attn_decode_paged_shared (attn_shared_kernel<hs, prefix / suffix> and attn_shared_merge_kernel): one group of three requests over a
+    prefix of 64 keys â€” the leader ends inside a block, one member beside the capacity, one at the prefix (an empty suffix) â€” and a request of no
+    group.  The members' prefix entries name the leader's blocks, all but block 2 beyond 2^31 elements; their own blocks there are NaN.  Once on
+    head-major blocks with a gap of 8 * hs cells behind each: block_step is more than a block's cells."""
+    layout, gap = SHARED_FORMS[form]
+    bk = FL.SHARED_BK
+    if ("shared", hs) not in _cases:
+        _cases[("shared", hs)] = Step(nso, HN, HKV, hs, FL.SHARED_CAP, bk, FL.SHARED_START, FL.SHARED_PREFIX, FL.SHARED_LENS, FL.SHARED_MAX_GROUP)
+    c = _cases[("shared", hs)]
+    assert c.members == {0: (0, 64), 1: (0, 64), 2: (0, 64)}
+    k, v = c.k.copy(), c.v.copy()
+    for b, (leader, P) in c.members.items():
+        if b != leader:
+            k[b, :P].view(np.uint16)[...] = NAN16  # (a member's own prefix blocks: no entry names them)
+            v[b, :P].view(np.uint16)[...] = NAN16
+    near = far = None
+    try:
+        near = Pages("near", hs, bk, live_blocks(c.lens, bk), layout, gap).fill_keys(k, v, c.lens).share_prefix(c.members)
+        far = Pages("over", hs, bk, live_blocks(c.lens, bk), layout, gap).fill_keys(k, v, c.lens).share_prefix(c.members)
+        assert all(far.table[b, j] == far.ids[(0, j)] for b in (1, 2) for j in range(4)) and sum(far.ids[(0, j)] * far.block_step > E31 for j in range(4)) == 3
+        s0 = shared_stats(L)
+        out_n = run_shared(L, pkg, c, near)[0]
+        s1 = shared_stats(L)
+        out_f = run_shared(L, pkg, c, far)[0]
+        dn, df = delta(s0, s1), delta(s1, shared_stats(L))
+        assert dn == df == ([2, 0, 1, 0] if hs == 64 else [0, 2, 1, 0]), (dn, df)
+        check_step(nso, "far addresses, near twin: decode_paged_shared hs %d %s" % (hs, form), c, out_n)
+        assert np.all(np.isfinite(out_f)), "a trap or a dead cell was consumed"
+        assert same_bits(out_f, out_n)
+        assert far.traps_intact()
+    finally:
+        near = far = None
+        release()
+
+
+# ---- prompt blocks at head sizes 136 .. 256 ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("layout", ["pm", "hm"], ids=["position_major", "head_major"])
+@pytest.mark.parametrize("hs", FL.WIDE_HS)
+def test_prefill_paged_wide(L, pkg, nso, hs, layout):
+    """ns_hip_attn_prefill_paged_wide (attn_wide_paged_kernel<PAD>: hs 256 exact, hs 160 padded): the one paged kernel that addresses K / V through
+    32-bit buffer descriptors, one per (page, head, wave), built from a 64-bit base.  q lens [1, 130, 40] over kv lens [70, 200, 120], the live blocks
+    but block 2 beyond 2^31 elements."""
+    bk = FL.WIDE_BK
+    if ("wide", hs) not in _rags:
+        _rags[("wide", hs)] = Rag(nso, HN, HKV, hs, FL.WIDE_CAP, FL.WIDE_Q, FL.WIDE_KV, seed=31)
+    c = _rags[("wide", hs)]
+    near = far = None
+    try:
+        near = Pages("near", hs, bk, live_blocks(c.kvlens, bk), layout).fill_keys(c.k, c.v, c.kvlens)
+        far = Pages("over", hs, bk, live_blocks(c.kvlens, bk), layout).fill_keys(c.k, c.v, c.kvlens)
+        s0 = wide_stats(L)
+        out_n = run_wide(L, pkg, c, near)[0]
+        s1 = wide_stats(L)
+        out_f = run_wide(L, pkg, c, far)[0]
+        dn, df = delta(s0, s1), delta(s1, wide_stats(L))
+        assert dn == df == ([1, 0, 0, 0] if hs == 256 else [0, 1, 0, 0]), (dn, df)
+        check_rag(nso, "far addresses, near twin: prefill_paged_wide hs %d %s" % (hs, layout), c, out_n)
+        assert np.all(np.isfinite(out_f)), "a trap or a dead cell was consumed"
+        assert same_bits(out_f, out_n)
+        assert far.traps_intact()
+    finally:
+        near = far = None
+        release()
+
+
+class EdgePools:
+    """The wide kernel's descriptor boundary (FL.wide_edge_layout): three blocks of 16 rows `step_sl` apart, kv head 1 hs + 8 cells behind kv head 0;
+    block 0 traps, blocks 1 and 2 live in all 16 rows, so a wave's lanes reach the last offset its descriptor may hold.  Traps: block 0's rows, the 8
+    cells in front of and behind every live row of a head, every alias of one.  near: the same rows 2 * hs apart in a compact pool."""
+
+    def __init__(self, hs, k, v, far):
+        import torch
+        if far:
+            g = FL.wide_edge_layout(hs)
+            need(4 * g["total"])
+        else:
+            g = dict(block_step=FL.EDGE_BK * 2 * hs, step_sl=2 * hs, step_head=hs, total=FL.EDGE_BLOCKS * FL.EDGE_BK * 2 * hs, extents=[], strip=8, dead=[])
+        self.block_step, self.step_sl, self.step_head, self.pool_blocks, self.bk, self.ts = g["block_step"], g["step_sl"], g["step_head"], FL.EDGE_BLOCKS, FL.EDGE_BK, 2
+        self.k, self.v = (Far(g["total"], g["extents"], g["strip"], dead=g["dead"], traps=far) for _ in range(2))
+        for x, rows in ((self.k, k), (self.v, v)):  # request 0's keys 0 .. 15 are block 1, its positions 16 .. 31 block 2 (EDGE_TABLE)
+            x.put(1 * self.block_step, (self.step_sl, self.step_head, 1), rows[0, :16])
+            x.put(2 * self.block_step, (self.step_sl, self.step_head, 1), rows[0, 16:32])
+        self.dt = torch.tensor(FL.EDGE_TABLE, dtype=torch.int32, device="cuda")
+        self.kp, self.vp = self.k.ptr, self.v.ptr
+
+    def table_args(self):
+        return C.c_void_p(self.dt.data_ptr()), self.ts, self.bk, self.pool_blocks, self.block_step
+
+    def traps_intact(self):
+        return self.k.traps_intact() and self.v.traps_intact()
+
+
+def edge_step(nso, hs):
+    """q lens [20, 1] over kv lens [20, 17] on the two live blocks: request 1's keys 0 .. 15 are request 0's positions 16 .. 31, its key 16 is request
+    0's key 0 (two requests may name the same block)"""
+    if ("edge", hs) not in _rags:
+        c = Rag(None, HN, HKV, hs, 2 * FL.EDGE_BK, FL.EDGE_Q, FL.EDGE_KV, seed=77)
+        k, v = c.k.copy(), c.v.copy()
+        for x in (k, v):
+            x[1, :16], x[1, 16:] = x[0, 16:], x[0, :16]
+            x.setflags(write=False)
+        c.k, c.v = k, v
+        for b in range(c.bs):
+            see, end = c.seeing(b), c.start[b] + c.qlens[b]
+            qb, kb, vb = c.q[end - see:end][None], c.k[b:b + 1, :c.kvlens[b]], c.v[b:b + 1, :c.kvlens[b]]
+            c.ref[b], c.model[b] = nso.attn_ref(qb, kb, vb, c.scale, c.flags, scales=c.scales), rounding_model(qb, kb, vb, c.scale, c.flags, c.scales)
+        _rags[("edge", hs)] = c
+    return _rags[("edge", hs)]
+
+
+def test_prefill_paged_wide_descriptor_boundary(L, pkg, nso):
+    """Rows as far apart as the plan's rule lets a descriptor span them â€” (15 s + 256) * 2 bytes just below kAwNoCell = 2^31, lane offsets up to
+    2^31 - 112 â€” in pools of 6.9 GB, block 2 beyond 2^32 bytes: the bits of the same keys 512 elements apart.  One step of 8 further the entry refuses
+    ("a block's rows of one kv head must lie within 2 GiB"), counts the refusal and writes nothing."""
+    hs = 256
+    below, above = FL.wide_edge_steps(hs)
+    c = edge_step(nso, hs)
+    near = far = None
+    try:
+        near, far = EdgePools(hs, c.k, c.v, False), EdgePools(hs, c.k, c.v, True)
+        assert far.step_sl == below and 2 * far.block_step * 2 >= E32
+        s0 = wide_stats(L)
+        out_n = run_wide(L, pkg, c, near)[0]
+        s1 = wide_stats(L)
+        out_f = run_wide(L, pkg, c, far)[0]
+        dn, df = delta(s0, s1), delta(s1, wide_stats(L))
+        assert dn == df == [1, 0, 0, 0], (dn, df)
+        check_rag(nso, "far addresses, near twin: prefill_paged_wide at the descriptor boundary", c, out_n)
+        assert np.all(np.isfinite(out_f)), "a trap was consumed"
+        assert same_bits(out_f, out_n)
+        assert far.traps_intact()
+        far.step_sl, far.block_step = above, FL.EDGE_BK * above  # (nothing is launched: the pools are not read)
+        L.ns_hip_reset_error()
+        s0 = wide_stats(L)
+        whole = run_wide(L, pkg, c, far, expect=-1)[2]
+        assert "a block's rows of one kv head must lie within 2 GiB" in pkg.last_error(), pkg.last_error()
+        assert delta(s0, wide_stats(L)) == [0, 0, 0, 1] and np.all(whole == 7.0)
+        L.ns_hip_reset_error()
+    finally:
+        near = far = None
         release()
 
 

@@ -105,3 +105,49 @@ def test_table_entries(L, pkg, nso, edit):
     out = run_shared(Entry(L, c), pkg, c, p)[0]
     same = list(range(c.bs)) if edit == "junk_member_entries" else [0, 6, 7, 8, 9, 10]
     assert np.all(np.isfinite(out)) and np.array_equal(out[same].view(np.uint32), good[same].view(np.uint32)) and p.guards_intact()
+
+
+def test_far_pool_is_bit_equal_to_the_compact_twin(L, pkg, nso):
+    """The far step of tests/test_gpu_attn_far_addresses.py (one group of three over a prefix of 64 keys, lens 70 / 200 / 64, a request of no group;
+    4 / 2 heads of 128, blocks of 16 = 4096 bytes) on FarPools8 of tests/test_gpu_attn_paged_f8.py: an untouched pool of 2^20 + 64 blocks, every live
+    block but block 2 — the leader's prefix blocks the members' entries name among them — above 2^32 bytes; 0x7f in the first and the last 64 blocks,
+    the members' own prefix blocks included.  The compact twin meets the reference and the fp16 entry; the far run holds its bits, consumes no 0x7f
+    byte and changes none."""
+    import torch
+    from test_gpu_attn_far_addresses import FL, need, release, same_bits
+    from test_gpu_attn_paged_f8 import FarPools8
+    bk = FL.SHARED_BK
+    c = Step8(nso, hn=FL.HN, hkv=FL.HKV, hs=128, cap=FL.SHARED_CAP, bk=bk, start=FL.SHARED_START, prefix=FL.SHARED_PREFIX, lens=FL.SHARED_LENS,
+              max_group=FL.SHARED_MAX_GROUP)
+    live = [-(-n // bk) for n in c.lens]
+    need(2 * FL.F8_BLOCKS * FL.block_step(128, bk))
+    got, p = [], None
+    try:
+        for blocks in (FL.pool_blocks("near", FL.block_step(128, bk), sum(live)) + 128, FL.F8_BLOCKS):
+            p = FarPools8(blocks, c, bk, live)
+            assert blocks < 1 << 20 or all(i == 2 or i * p.block_step >= 1 << 32 for i in p.ids.values())
+            for b, n in enumerate(c.lens):
+                kc, vc = c.kc[b, :n].copy(), c.vc[b, :n].copy()
+                if b in c.members and c.members[b][0] != b:
+                    P = c.members[b][1]
+                    kc[:P], vc[:P] = NAN8, NAN8  # (the member's own prefix blocks, which no entry names)
+                    p.table[b, :P // bk] = p.table[c.members[b][0], :P // bk]
+                p.put(b, kc, vc)
+            p.dt = torch.from_numpy(p.table).cuda()
+            s0 = shared8_stats(L)
+            out = run_shared(Entry(L, c), pkg, c, p)[0]
+            assert delta(s0, shared8_stats(L)) == [0, 2, 1, 0], blocks
+            cells, clean = p.live()
+            assert clean and np.all(np.isfinite(out)), blocks
+            got.append((out, cells))
+            p = None
+            release()
+        (on, cn), (of, cf) = got
+        check_step(nso, "far addresses, near twin: decode_paged_shared_f8", c, on)
+        half = run_shared(Entry(L, c, f8=False), pkg, c, c.pools(f8=False))[0]
+        e = nso.rel_l2(on[sorted(c.members)], half[sorted(c.members)])
+        assert e < 2e-4, e
+        assert same_bits(on, of) and all(same_bits(cn[key][x], cf[key][x]) for key in cn for x in (0, 1))
+    finally:
+        p = None
+        release()

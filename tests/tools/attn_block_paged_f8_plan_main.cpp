@@ -3,6 +3,7 @@
 //   plan   <the call> | <the fields of the FP8 plan> | <the fields of the fp16 plan>
 //   refuse what=.. | <the fields of the FP8 plan>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <initializer_list>
 #include <limits>
@@ -19,6 +20,7 @@ struct Case {
   uintptr_t vbase = 0x200000;
   float k_sc = 0.25f, v_sc = 2.f;
   bool null_table = false;
+  int pool_blocks = 0;  // 0: the table's blocks + 4
 };
 static const int g_lens[64] = {0}, g_start[65] = {0};
 static const int g_table[1] = {0};  // (only its address is used by a plan)
@@ -44,7 +46,7 @@ static AttnBlockPagedPlan plan(const Case& c, bool f8, std::string* why) {
   pg.table = c.null_table ? nullptr : g_table;
   pg.block_shift = attn_block_shift(c.bk);
   pg.table_stride = c.cap / c.bk;
-  pg.pool_blocks = pg.table_stride * c.bs + 4;
+  pg.pool_blocks = c.pool_blocks ? c.pool_blocks : pg.table_stride * c.bs + 4;
   pg.block_step = c.block_step ? c.block_step : (long long)c.bk * c.hkv * c.hs;
   return f8 ? attn_block_paged_f8_plan(a, nullptr, AttnKnobs(), pg, g_start, g_lens, 1, why)
             : attn_block_paged_plan(a, nullptr, AttnKnobs(), pg, g_start, g_lens, 1, why);
@@ -74,7 +76,17 @@ static void run(const char* kind, const char* what, const Case& c, bool both) {
   printf("\n");
 }
 
-int main() {
+int main(int argc, char** argv) {
+  // far hs bk cap requests max_q pool_blocks block_step step_sl step_head: the pool of the far-address test (4 / 2 heads), whose numbers
+  // (tests/tools/attn_far_layout.py) the caller passes -> a plan line with what=far
+  if (argc == 11 && std::string(argv[1]) == "far") {
+    const auto at = [&](int i) { return atoll(argv[i]); };
+    Case c;
+    c.hn = 4, c.hkv = 2, c.hs = int(at(2)), c.bk = int(at(3)), c.cap = int(at(4)), c.bs = int(at(5)), c.max_q = int(at(6)), c.pool_blocks = int(at(7));
+    c.block_step = at(8), c.step_sl = at(9), c.step_head = at(10);
+    run("plan", "far", c, true);
+    return 0;
+  }
   const int groups[][2] = {{8, 8}, {8, 2}, {8, 1}};
   int n = 0;
   for (int bk : {16, 64, 256})

@@ -1,6 +1,7 @@
 """Where tests/test_gpu_attn_far_addresses.py puts its K / V rows: pool sizes, strides, physical block ids, and the places a truncated address would
-land (the alias traps).  Host arithmetic only — the CPU plan tests (tests/test_attn_plan.py, tests/test_attn_paged_plan.py) run the plan on the same
-numbers, so a 32-bit rule that moves fails there with the reason, not on the GPU with a changed path.
+land (the alias traps).  Host arithmetic only — the CPU plan tests (tests/test_attn_plan.py, tests/test_attn_paged_plan.py, the shared, FP8-block and
+wide plan tests) run the plan on the same numbers, so a 32-bit rule that moves fails there with the reason, not on the GPU with a changed path;
+tests/test_attn_far_layout.py restates the wide kernel's address with three mistakes in it and looks for the traps they reach.
 
 Offsets are fp16 ELEMENTS from a tensor's base unless a name says bytes."""
 import numpy as np
@@ -20,6 +21,68 @@ BLOCK_KV = {16: [70, 200, 120], 128: [200, 300, 150]}
 def block_step(hs, bk):
     """elements of a position-major block [key][kv head][dim]"""
     return bk * HKV * hs
+
+
+# ---- the shared-prefix, FP8-block and wide cases ------------------------------------------------------------------------------------------------------
+SHARED_HS, SHARED_BK, SHARED_CAP = [64, 128], 16, 256
+SHARED_START, SHARED_PREFIX, SHARED_MAX_GROUP = [0, 3], [64], 3  # one group: requests 0 .. 2, the leader's first 64 keys
+SHARED_LENS = [70, 200, 64, 33]  # the leader ends inside a block, a member beside the capacity, a member with an empty suffix; request 3 is in no group
+WIDE_HS, WIDE_BK, WIDE_CAP = [256, 160], 16, 256  # the exact instantiation and a padded one
+WIDE_Q, WIDE_KV = [1, 130, 40], BLOCK_KV[16]
+F8_BLOCKS = (1 << 20) + 64  # FarPools8 (tests/test_gpu_attn_paged_f8.py): blocks of 4096 bytes; up to 25 high blocks, every second one, all above 2^32 bytes
+GAP_ROWS = 8                # a gapped block: GAP_ROWS * hs cells behind a block's own, traps
+WIDE_NO_CELL = 1 << 31      # kAwNoCell (ns_attn.h): the wide kernel's lane offsets and num_records stay below it
+EDGE_BLOCKS, EDGE_BK, EDGE_Q, EDGE_KV = 3, 16, [20, 1], [20, 17]  # the wide descriptor boundary: block 0 traps, live blocks 1 and 2
+EDGE_TABLE = [[1, 2], [2, 1]]  # request 0: keys 0 .. 15 in block 1, 16 .. 19 in rows 0 .. 3 of block 2; request 1: keys 0 .. 15 in block 2, key 16 in row 0 of block 1
+
+
+def strides(layout, hs, bk):
+    """(step_sl, step_head) of a block: "pm" [key][kv head][dim], "hm" [kv head][key][dim]"""
+    assert layout in ("pm", "hm")
+    return (HKV * hs, hs) if layout == "pm" else (hs, bk * hs)
+
+
+def gapped_step(hs, bk):
+    """block_step of a block with GAP_ROWS * hs cells of gap behind its own"""
+    return block_step(hs, bk) + GAP_ROWS * hs
+
+
+def paged_layout(size, hs, bk, live, layout="pm", gap=False):
+    """everything tests/test_gpu_attn_far_addresses.py's Pages is made of: strides, pool size, table, ids, the live blocks' extents (a block's own
+    cells: a gap is no part of one) and the arguments traps_of gets — a whole block step as the strip, so a gap lies inside it, and block 0 dead"""
+    cells, step = block_step(hs, bk), gapped_step(hs, bk) if gap else block_step(hs, bk)
+    step_sl, step_head = strides(layout, hs, bk)
+    assert (bk - 1) * step_sl + (HKV - 1) * step_head + hs <= cells
+    n = pool_blocks(size, step, sum(live))
+    table, ids = place(live, PAGED_CAP[bk] // bk, n)
+    extents = [(i * step, cells) for i in ids.values()]
+    gaps = [(i * step + cells, step - cells) for i in ids.values()] if gap else []  # (by name: the last block's strip would end behind the pool)
+    return dict(cells=cells, block_step=step, step_sl=step_sl, step_head=step_head, pool_blocks=n, table=table, ids=ids, total=n * step, extents=extents,
+                strip=step, dead=[(0, step)] + gaps)
+
+
+def wide_rule(bk, step_sl, hs):
+    """attn_prefill_paged_wide_plan's rule restated: the last key's last byte, and every lane offset with it, below kAwNoCell"""
+    return ((bk - 1) * step_sl + hs) * 2 < WIDE_NO_CELL
+
+
+def wide_edge_steps(hs):
+    """(the largest row step, a multiple of 8, that keeps the 16 rows of a block of one kv head inside a descriptor below kAwNoCell; the next one)"""
+    s = ((WIDE_NO_CELL // 2 - 1 - hs) // (EDGE_BK - 1)) // 8 * 8
+    assert (15 * s + hs) * 2 < E31 <= (15 * (s + 8) + hs) * 2
+    assert wide_rule(EDGE_BK, s, hs) and not wide_rule(EDGE_BK, s + 8, hs)
+    return s, s + 8
+
+
+def wide_edge_layout(hs, step_sl=None):
+    """the boundary pools: EDGE_BLOCKS blocks of 16 rows step_sl apart, kv head 1 hs + 8 cells behind kv head 0, so the 8 cells behind every live row
+    of a head are no head's; extents: every (row, kv head) of blocks 1 and 2; dead: those of block 0, where a dropped id lands"""
+    step_sl = wide_edge_steps(hs)[0] if step_sl is None else step_sl
+    step_head, step = hs + 8, EDGE_BK * step_sl
+    assert (EDGE_BK - 1) * step_sl + (HKV - 1) * step_head + hs <= step
+    cell = lambda blk: [(blk * step + r * step_sl + h * step_head, hs) for r in range(EDGE_BK) for h in range(HKV)]
+    return dict(block_step=step, step_sl=step_sl, step_head=step_head, pool_blocks=EDGE_BLOCKS, total=EDGE_BLOCKS * step, extents=cell(1) + cell(2),
+                strip=8, dead=cell(0))
 
 
 def page_in32(pool_blocks, step):

@@ -9,6 +9,7 @@
 // Host code only: no HIP call is made, no tensor exists — the pointers are made-up addresses.
 #include <algorithm>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -29,6 +30,7 @@ struct Case {
   int dst_off = 0, d16 = 0, dst_sl_add = 0;
   bool no_xcd = false;
   int layout = ATTN_FWD_LAYOUT_PLAIN;
+  long long step_sl = 0, step_head = 0;  // 0: by the layout
 };
 
 static const int g_ints[64] = {0};  // (only its address is used by a plan)
@@ -58,6 +60,7 @@ static AttnPrefillWidePlan plan_of(const Case& c, std::string* why) {
     a.step_k_sl = a.step_v_sl = (long long)c.hkv * c.hs;
     a.step_k_head_num = a.step_v_head_num = c.hs;
   }
+  if (c.step_sl) a.step_k_sl = a.step_v_sl = c.step_sl, a.step_k_head_num = a.step_v_head_num = c.step_head;
   a.step_k_sl += c.k_sl_add;
   AttnPage pg;
   pg.table = c.null_table ? nullptr : g_ints;
@@ -89,11 +92,12 @@ static void run_refusal(const char* what, const Case& c) {
 }
 
 // every request of every wave of every tile, as attn_wide_paged_kernel's issue() makes it; two kv heads, the walk is kv head ihkv's
-static void run_walk(int index, int hs, int bk, int kv_len, int pool_blocks, int head_major, int ihkv, const std::vector<int>& table) {
+static void run_walk(int index, int hs, int bk, int kv_len, int pool_blocks, int head_major, int ihkv, const std::vector<int>& table, long long sl = 0,
+                     long long head = 0, long long block_step = 0) {
   AttnPage pg;
   pg.table = table.data(), pg.table_stride = int(table.size()), pg.block_shift = attn_block_shift(bk), pg.pool_blocks = pool_blocks;
-  const long long step_sl = head_major ? hs : 2 * hs, step_head = head_major ? (long long)bk * hs : hs;
-  pg.block_step = (long long)bk * 2 * hs;
+  const long long step_sl = sl ? sl : (head_major ? hs : 2 * hs), step_head = sl ? head : (head_major ? (long long)bk * hs : hs);
+  pg.block_step = block_step ? block_step : (long long)bk * 2 * hs;
   printf("walk case=%d hs=%d bk=%d kvlen=%d blocks=%d step=%lld stepsl=%lld stephead=%lld ihkv=%d table=", index, hs, bk, kv_len, pool_blocks, pg.block_step,
          step_sl, step_head, ihkv);
   for (size_t i = 0; i < table.size(); i++) printf("%s%d", i ? "," : "", table[i]);
@@ -111,7 +115,33 @@ static void run_walk(int index, int hs, int bk, int kv_len, int pool_blocks, int
   printf("\n");
 }
 
-int main() {
+// the pools of the far-address tests, whose numbers (tests/tools/attn_far_layout.py) the caller passes:
+//   far  hs bk cap requests max_q pool_blocks block_step step_sl step_head   -> far <the call> | ok=.. pad=.. why=..
+//   walk hs bk kv_len pool_blocks block_step step_sl step_head ihkv id id ..   -> one walk line (case -1)
+static int from_arguments(int argc, char** argv) {
+  const auto at = [&](int i) { return atoll(argv[i]); };
+  if (std::string(argv[1]) == "far" && argc == 11) {
+    Case c;
+    c.hn = 4, c.hkv = 2, c.hs = int(at(2)), c.bk = int(at(3)), c.cap = int(at(4)), c.bs = int(at(5)), c.max_q = int(at(6)), c.pool_blocks = int(at(7));
+    c.block_step = at(8), c.step_sl = at(9), c.step_head = at(10);
+    std::string why;
+    const AttnPrefillWidePlan pl = plan_of(c, &why);
+    printf("far hs=%d bk=%d blocks=%d step=%lld stepsl=%lld stephead=%lld | ok=%d pad=%d why=%s\n", c.hs, c.bk, c.pool_blocks, c.block_step, c.step_sl, c.step_head,
+           int(pl.ok), pl.pad, why.c_str());
+    return 0;
+  }
+  if (std::string(argv[1]) == "walk" && argc > 10) {
+    std::vector<int> table;
+    for (int i = 10; i < argc; i++) table.push_back(int(at(i)));
+    run_walk(-1, int(at(2)), int(at(3)), int(at(4)), int(at(5)), 0, int(at(9)), table, at(7), at(8), at(6));
+    return 0;
+  }
+  fprintf(stderr, "usage: far .. | walk ..\n");
+  return 2;
+}
+
+int main(int argc, char** argv) {
+  if (argc > 1) return from_arguments(argc, argv);
   const int groups[][2] = {{8, 8}, {8, 1}, {16, 16}};
   int n = 0;
   for (int bk : {16, 64, 256})

@@ -1,5 +1,6 @@
 // Program of tests/test_attn_shared_paged_f8_plan.py (host code only, made-up addresses).  Lines: `<what> | <the FP8 plan's fields> | <the fp16 plan's>`.
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <limits>
 #include <string>
@@ -14,6 +15,7 @@ struct Case {
   uintptr_t vbase = 0x200000;
   float k_sc = 0.25f, v_sc = 2.f;
   unsigned flags = NS_ATTN_FLAG_IS_CAUSAL;
+  int pool_blocks = 0;  // 0: the table's blocks + 4
 };
 static const int g_ints[64] = {0};  // (only its address is used by a plan)
 
@@ -27,7 +29,7 @@ static void print_plan(const Case& c, bool f8) {
   a.Q_layout = a.K_layout = a.V_layout = a.dst_layout = ATTN_FWD_LAYOUT_PLAIN;
   a.step_q_bs = a.step_dst_bs = a.step_q_sl = a.step_dst_sl = c.hn * c.hs, a.step_q_head_num = a.step_dst_head_num = c.hs;
   a.step_k_head_size = a.step_v_head_size = 1, a.step_k_sl = a.step_v_sl = c.step_sl, a.step_k_head_num = a.step_v_head_num = c.step_head;
-  const AttnPage pg = {g_ints, c.cap / c.bk, attn_block_shift(c.bk), c.cap / c.bk * c.bs + 4, c.block_step};
+  const AttnPage pg = {g_ints, c.cap / c.bk, attn_block_shift(c.bk), c.pool_blocks ? c.pool_blocks : c.cap / c.bk * c.bs + 4, c.block_step};
   std::string why;
   const AttnSharedPagedPlan pl = f8 ? attn_shared_paged_f8_plan(a, nullptr, AttnKnobs(), pg, g_ints, c.groups, c.max_group, g_ints, g_ints, 1, &why)
                                     : attn_shared_paged_plan(a, nullptr, AttnKnobs(), pg, g_ints, c.groups, c.max_group, g_ints, g_ints, 1, &why);
@@ -43,8 +45,18 @@ static void print_plan(const Case& c, bool f8) {
          (long long)sp.a.step_dst_bs, sp.a.qk_scale, sp.a.out_scale, why.c_str());
 }
 
-int main() {
+int main(int argc, char** argv) {
   const auto run = [](const char* what, const Case& c) { printf("%s", what), print_plan(c, true), print_plan(c, false), printf("\n"); };
+  // far hs bk cap requests groups max_group pool_blocks block_step step_sl step_head: the pool of the far-address test (4 / 2 heads), whose numbers
+  // (tests/tools/attn_far_layout.py) the caller passes
+  if (argc == 12 && std::string(argv[1]) == "far") {
+    const auto at = [&](int i) { return atoll(argv[i]); };
+    Case c;
+    c.hn = 4, c.hkv = 2, c.hs = int(at(2)), c.bk = int(at(3)), c.cap = int(at(4)), c.bs = int(at(5)), c.groups = int(at(6)), c.max_group = int(at(7));
+    c.pool_blocks = int(at(8)), c.block_step = at(9), c.step_sl = at(10), c.step_head = at(11);
+    run("far", c);
+    return 0;
+  }
   const int shapes[][6] = {{8, 8, 8, 2, 4, 2048}, {32, 8, 32, 1, 32, 4096}, {32, 32, 32, 4, 8, 4096}, {8, 1, 9, 3, 5, 256}, {71, 1, 1, 1, 1, 1024}};
   for (const auto& s : shapes)  // (hn, hkv, requests, groups, max_group, capacity): head size 128 position-major, then 64 head-major
     for (int hs : {128, 64}) {

@@ -3,6 +3,7 @@
 // `refuse what=.. | ok=.. why=..`, `live dyn=.. bk=.. P=.. len=.. | <the plan's ranges> prefix=<kps:live> suffix=<kps:live>`.
 // Host code only: no HIP call is made, no tensor exists — the pointers are made-up addresses.
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 
@@ -15,6 +16,8 @@ struct Case {
   int hs = 128, cap = 2048, hn = 8, hkv = 8, bs = 8, bk = 16, groups = 2, max_group = 4, sl_q = 1, table_stride = 0, null_arg = -1;
   unsigned flags = NS_ATTN_FLAG_IS_CAUSAL;
   bool dyn = true;
+  long long step_sl = 0, step_head = 0, block_step = 0;  // 0: position-major blocks of their own size
+  int pool_blocks = 0;
 };
 static const int g_ints[64] = {0};  // (only its address is used by a plan)
 
@@ -28,8 +31,10 @@ static AttnSharedPagedPlan plan_of(const Case& c, std::string* why) {
   a.Q_layout = a.K_layout = a.V_layout = a.dst_layout = ATTN_FWD_LAYOUT_PLAIN;
   a.step_q_bs = a.step_dst_bs = a.step_q_sl = a.step_dst_sl = c.hn * c.hs, a.step_q_head_num = a.step_dst_head_num = c.hs;
   a.step_k_head_size = a.step_v_head_size = 1, a.step_k_sl = a.step_v_sl = c.hkv * c.hs, a.step_k_head_num = a.step_v_head_num = c.hs;
+  if (c.step_sl) a.step_k_sl = a.step_v_sl = c.step_sl, a.step_k_head_num = a.step_v_head_num = c.step_head;
   const int ts = c.table_stride ? c.table_stride : c.cap / c.bk;
-  const AttnPage pg = {g_ints, ts, attn_block_shift(c.bk), ts * c.bs + 4, (long long)c.bk * c.hkv * c.hs};
+  const AttnPage pg = {g_ints, ts, attn_block_shift(c.bk), c.pool_blocks ? c.pool_blocks : ts * c.bs + 4,
+                       c.block_step ? c.block_step : (long long)c.bk * c.hkv * c.hs};
   AttnKnobs kn;
   kn.dyn_ranges = c.dyn;
   why->clear();
@@ -37,7 +42,23 @@ static AttnSharedPagedPlan plan_of(const Case& c, std::string* why) {
                                 c.null_arg == 2 ? nullptr : g_ints, 1, why);
 }
 
-int main() {
+// far hs bk cap requests groups max_group pool_blocks block_step step_sl step_head: a pool of the far-address tests, whose numbers
+// (tests/tools/attn_far_layout.py) the caller passes; 4 / 2 heads -> far hs=.. blocks=.. step=.. | ok=.. hspad=.. pgrid=.. sgrid=.. why=..
+static int far_call(char** argv) {
+  const auto at = [&](int i) { return atoll(argv[i]); };
+  Case c;
+  c.hn = 4, c.hkv = 2, c.hs = int(at(2)), c.bk = int(at(3)), c.cap = int(at(4)), c.bs = int(at(5)), c.groups = int(at(6)), c.max_group = int(at(7));
+  c.pool_blocks = int(at(8)), c.block_step = at(9), c.step_sl = at(10), c.step_head = at(11);
+  std::string why;
+  const AttnSharedPagedPlan pl = plan_of(c, &why);
+  printf("far hs=%d blocks=%d step=%lld | ok=%d hspad=%d pgrid=%u,%u,%u sgrid=%u,%u,%u bstep=%lld ksl=%lld khead=%lld why=%s\n", c.hs, pl.sp.pg.pool_blocks, c.block_step,
+         int(pl.ok), pl.hs_pad, pl.grid_prefix.x, pl.grid_prefix.y, pl.grid_prefix.z, pl.grid_suffix.x, pl.grid_suffix.y, pl.grid_suffix.z, pl.sp.pg.block_step,
+         (long long)pl.sp.a.step_k_sl, (long long)pl.sp.a.step_k_head_num, why.c_str());
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc == 12 && std::string(argv[1]) == "far") return far_call(argv);
   std::string why;
   const int heads[][2] = {{8, 8}, {32, 32}, {32, 8}, {8, 1}, {71, 1}};
   const int shapes[][3] = {{1, 1, 1}, {32, 1, 32}, {32, 4, 8}, {32, 32, 1}, {9, 3, 5}};  // (requests, groups, max_group)
