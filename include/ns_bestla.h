@@ -910,6 +910,24 @@ void ns_hip_attn_prefill_paged_f8_stats(unsigned long long out[6]);
 int ns_hip_attn_prefill_paged_wide(const attn_fp32_fp16_fp16_fp32_fwd_args_t* dparams, const int* dQStart, const int* dKvLens, int kv_len_bias,
                                    const int* dBlockTable, int table_stride, int block_keys, int pool_blocks, long long block_step, void* dst16, void* stream);
 void ns_hip_attn_prefill_paged_wide_stats(unsigned long long out[4]);
+/* ns_hip_attn_prefill_paged_wide_f8: ns_hip_attn_prefill_paged_wide's signature and, word for word, its contract (packed Q / dst / dst16 through dQStart,
+ * dKvLens + bias, max_q, the causal rule, zero rows, idle requests, the table-entry rules, ONE launch with no `tmp` and no scratch, capturable without
+ * a first eager call, unbiased scores only: QK_scale * Q_sc * K_sc positive and finite) over THE FP8 POOL of ns_hip_attn_decode_paged_f8: K / V of the
+ * block are the pool bases of E4M3 codes, every stride counts bytes, K_sc / V_sc are the pools' scales, folded as ever.  Head sizes: the multiples of
+ * 16 from 144 to 256 (144 .. 240 padded to 256).  A kernel of its own way from the pool to LDS: the codes of a 64-key tile are loaded through one
+ * buffer descriptor per page and wave into registers, decoded exactly to fp16 once per workgroup and stored into the LDS image the fp16 kernel keeps;
+ * everything behind that image is the fp16 kernel's, so the output holds THE BITS ns_hip_attn_prefill_paged_wide gives over fp16 pools holding the
+ * codes' values under the same argument block.  A key at or behind kv_len_b, an id outside [0, pool_blocks) and a dim at or past head_size lie outside
+ * the descriptor and arrive as zero bytes, which decode to +0.0: no byte behind kv_len_b reaches a result.  Every cell address is 64-bit.
+ * Refused (-1, ns_hip_last_error set, nothing written), in this order: a scale that is not positive and finite; what the FP8 pool asks (head_size, the
+ * row stride, the head stride or block_step not a multiple of 16, a pool base that is not 16-byte aligned); what ns_hip_attn_prefill_paged_wide
+ * refuses, with head_size <= 128 naming ns_hip_attn_prefill_paged_f8 and the 2 GiB span of a block's rows of one kv head counted in bytes.
+ * ns_hip_attn_prefill_paged_wide_f8_stats: [0] launches at head size 256, [1] padded launches (144 .. 240), [2] reserved (0), [3] refused calls.  No
+ * other entry's counter moves. */
+int ns_hip_attn_prefill_paged_wide_f8(const attn_fp32_fp16_fp16_fp32_fwd_args_t* dparams, const int* dQStart, const int* dKvLens, int kv_len_bias,
+                                      const int* dBlockTable, int table_stride, int block_keys, int pool_blocks, long long block_step, void* dst16,
+                                      void* stream);
+void ns_hip_attn_prefill_paged_wide_f8_stats(unsigned long long out[4]);
 
 /* ----------------------------------------------------------------------------------------------
  * Part 4b — mixture-of-experts matmul with the routing on the device.  Device twin of

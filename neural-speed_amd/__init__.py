@@ -305,6 +305,10 @@ def lib():
         L.ns_hip_attn_prefill_paged_wide.argtypes = [vp, vp, vp, i, vp, i, i, i, C.c_longlong, vp, vp]
         L.ns_hip_attn_prefill_paged_wide_stats.restype = None
         L.ns_hip_attn_prefill_paged_wide_stats.argtypes = [vp]
+        L.ns_hip_attn_prefill_paged_wide_f8.restype = C.c_int
+        L.ns_hip_attn_prefill_paged_wide_f8.argtypes = [vp, vp, vp, i, vp, i, i, i, C.c_longlong, vp, vp]
+        L.ns_hip_attn_prefill_paged_wide_f8_stats.restype = None
+        L.ns_hip_attn_prefill_paged_wide_f8_stats.argtypes = [vp]
         L.ns_hip_attn_prefill_paged_f8.restype = C.c_int
         L.ns_hip_attn_prefill_paged_f8.argtypes = [vp, vp, vp, i, vp, i, i, i, C.c_longlong, vp, vp]
         L.ns_hip_attn_prefill_paged_f8_stats.restype = None

@@ -336,6 +336,17 @@ static hipError_t launch_attn_prefill_paged_wide_call(const attn_fp32_fp16_fp16_
   return e;
 }
 
+// ns_hip_attn_prefill_paged_wide_f8: the same over FP8 pools — attn_prefill_paged_wide_f8_plan and ONE launch of attn_wide_paged8_kernel
+static std::atomic<uint64_t> g_attn_prefill_wide_f8[4];  // ns_hip_attn_prefill_paged_wide_f8_stats
+static hipError_t launch_attn_prefill_paged_wide_f8_call(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const int* q_start, const int* lens, int bias,
+                                                         const AttnPage& page, hipStream_t st, std::string* why, void* dst16) {
+  const AttnPrefillWidePlan pl = attn_prefill_paged_wide_f8_plan(a, dst16, attn_knobs(), page, q_start, lens, bias, why);
+  if (!pl.ok) return hipErrorInvalidValue;
+  const hipError_t e = launch_attn_prefill_paged_wide_f8(pl, st);
+  if (e == hipSuccess) g_attn_prefill_wide_f8[pl.pad ? 1 : 0].fetch_add(1, std::memory_order_relaxed);
+  return e;
+}
+
 // scratch a moving-length decode launch needs (partials for the longest context, the merge tickets): allocated BEFORE the route's capture
 bool attn_prepare_moving(hipStream_t st, int batch, int heads, int heads_kv, int head_size, int cap) {
   const size_t b = attn_ws_bytes(attn_knobs(), batch, heads, heads_kv, head_size, 1, cap);
@@ -579,6 +590,25 @@ int ns_hip_attn_prefill_paged_wide(const attn_fp32_fp16_fp16_fp32_fwd_args_t* a,
 
 void ns_hip_attn_prefill_paged_wide_stats(unsigned long long out[4]) {
   for (int i = 0; i < 4; i++) out[i] = g_attn_prefill_wide[i].load(std::memory_order_relaxed);
+}
+
+int ns_hip_attn_prefill_paged_wide_f8(const attn_fp32_fp16_fp16_fp32_fwd_args_t* a, const int* dQStart, const int* dKvLens, int kv_len_bias,
+                                      const int* dBlockTable, int table_stride, int block_keys, int pool_blocks, long long block_step, void* dst16,
+                                      void* stream) {
+  std::string why;
+  const AttnPage page = {dBlockTable, table_stride, attn_block_shift(block_keys), pool_blocks, block_step};
+  const hipError_t e =
+      a ? launch_attn_prefill_paged_wide_f8_call(*a, dQStart, dKvLens, kv_len_bias, page, static_cast<hipStream_t>(stream), &why, dst16) : hipErrorInvalidValue;
+  if (e != hipSuccess) {
+    g_attn_prefill_wide_f8[3].fetch_add(1, std::memory_order_relaxed);
+    set_error(why.empty() ? std::string("attention launch (wide prompt blocks over an FP8 paged cache): ") + (a ? hipGetErrorString(e) : "null arguments") : why);
+    return -1;
+  }
+  return 0;
+}
+
+void ns_hip_attn_prefill_paged_wide_f8_stats(unsigned long long out[4]) {
+  for (int i = 0; i < 4; i++) out[i] = g_attn_prefill_wide_f8[i].load(std::memory_order_relaxed);
 }
 
 size_t ns_hip_attn_block_paged_workspace_size(int batch, int head_num, int heads_kv, int head_size, int max_q, int capacity) {

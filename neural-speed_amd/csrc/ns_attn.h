@@ -337,6 +337,49 @@ __host__ __device__ __forceinline__ uint32_t attn_wide_v_offset(int u, int l, lo
 __host__ __device__ constexpr int attn_wide_k_lds(int w, int u) { return (kAwReq * w + u) * 1024; }
 __host__ __device__ constexpr int attn_wide_v_lds(int w, int u) { return kAwKTile + u * (kA2KB * 64) + w * 1024; }
 
+// ---- ... over an FP8 paged cache (ns_hip_attn_prefill_paged_wide_f8; attn_wide_paged8_kernel, ns_attn_prefill_wide_f8.hip) --------------------------
+// The same argument block, table slot (attn_wide_table_slot) and split — wave w moves keys 16 w .. 16 w + 15 of a tile through one descriptor pair —
+// over pools of CODES: every stride counts bytes, a lane's 16 bytes are 16 dims of one key row, and a wave's share is kAw8Req requests of K and as
+// many of V.  The codes travel through registers (buffer_load_dwordx4), are decoded there and stored to the stage with two 16-byte LDS writes per
+// request: the stage is byte for byte the fp16 kernel's image over the decoded values.  THE request rule of that kernel: its issue, its commit and
+// tests/tools/attn_prefill_paged_wide_f8_plan_main.cpp all go through the functions below.
+constexpr int kAw8Req = 4;  // requests of K, and of V, per wave and tile
+// attn_wide_desc in bytes: base = the BYTE offset from the pool's base, bytes = num_records = (live - 1) * step_sl + head_size
+__host__ __device__ __forceinline__ AttnWideDesc attn_wide8_desc(const AttnPage& pg, int id, int pos0, int w, int kv_len, int ihkv, long long step_sl,
+                                                                 long long step_head, int head_size) {
+  const int first = pos0 + 16 * w;
+  const int live = min(max(kv_len - first, 0), 16);
+  if (unsigned(id) >= unsigned(pg.pool_blocks) || live == 0) return {0, 0u};
+  return {(long long)id * pg.block_step + (long long)ihkv * step_head + (long long)(first & ((1 << pg.block_shift) - 1)) * step_sl,
+          uint32_t((long long)(live - 1) * step_sl + head_size)};
+}
+// Lane l's (row of the wave's group, 16-dim column) in request u.  K: four whole rows of codes per request, a row's 16 columns in neighbouring lanes
+// (256 contiguous bytes).  V: the group's 16 rows x columns 4 u .. 4 u + 3 (64 contiguous bytes per row); 16 neighbouring lanes are 4 rows x 4
+// columns, so the 16-byte pieces they store with one LDS write fall at eight different places of the banks' 256 bytes, where the 16 columns of one
+// row would fall at two.
+__host__ __device__ constexpr int attn_wide8_k_row(int u, int l) { return 4 * u + (l >> 4); }
+__host__ __device__ constexpr int attn_wide8_k_col(int, int l) { return l & 15; }
+__host__ __device__ constexpr int attn_wide8_v_row(int, int l) { return 4 * (l >> 4) + ((l >> 2) & 3); }
+__host__ __device__ constexpr int attn_wide8_v_col(int u, int l) { return 4 * u + (l & 3); }
+// ... and its byte offset inside the descriptor; a column at or past head_size (the padded forms) does not exist: kAwNoCell
+__host__ __device__ __forceinline__ uint32_t attn_wide8_offset(int row, int col, long long step_sl, int head_size) {
+  return 16 * col < head_size ? uint32_t((long long)row * step_sl + 16 * col) : kAwNoCell;
+}
+__host__ __device__ __forceinline__ uint32_t attn_wide8_k_offset(int u, int l, long long step_sl, int head_size) {
+  return attn_wide8_offset(attn_wide8_k_row(u, l), attn_wide8_k_col(u, l), step_sl, head_size);
+}
+__host__ __device__ __forceinline__ uint32_t attn_wide8_v_offset(int u, int l, long long step_sl, int head_size) {
+  return attn_wide8_offset(attn_wide8_v_row(u, l), attn_wide8_v_col(u, l), step_sl, head_size);
+}
+// Where the lane's decoded 32 bytes go inside a stage.  K: its 16 dims are the fp16 chunks c = 2 col and c + 1 of tile row 16 w + row: slot
+// (c + half) ^ (row & 15) of that row, half = 0 / 1.  V: 32 contiguous bytes of its key's 64-byte row in column block col / 2.
+__host__ __device__ constexpr int attn_wide8_k_lds(int w, int u, int l, int half) {
+  return (16 * w + attn_wide8_k_row(u, l)) * 512 + (((2 * attn_wide8_k_col(u, l) + half) ^ (attn_wide8_k_row(u, l) & 15)) << 4);
+}
+__host__ __device__ constexpr int attn_wide8_v_lds(int w, int u, int l) {
+  return kAwKTile + (attn_wide8_v_col(u, l) >> 1) * (kA2KB * 64) + (16 * w + attn_wide8_v_row(u, l)) * 64 + (attn_wide8_v_col(u, l) & 1) * 32;
+}
+
 // ---- the launch decision as a value (ns_attn_plan.cpp) -------------------------------------------------------------------------------------
 // Every tunable the decision reads.  attn_knobs() (ns_attn.cpp) fills it from ns_hip_set_tuning's atomics and the environment.
 struct AttnKnobs {
@@ -471,9 +514,16 @@ struct AttnPrefillWidePlan {
   dim3 grid, block;
   size_t lds = 0;
   int nqb = 0, aligned = 0, xcd_map = 0;
+  bool f8 = false;  // the pools hold E4M3 codes (attn_prefill_paged_wide_f8_plan only: attn_wide_paged8_kernel)
 };
 AttnPrefillWidePlan attn_prefill_paged_wide_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst16, const AttnKnobs& knobs, const AttnPage& page,
                                                  const int* q_start, const int* kv_lens, int kv_len_bias, std::string* why);
+// The plan of ns_hip_attn_prefill_paged_wide_f8: the FP8 pool's own refusals (the scales, attn_f8_pool_refusal) first, then the plan above of the call
+// as it stands with a cell of one byte in the descriptor rule; grid, nqb, pad, aligned and xcd_map are kept, f8 is set, lds is the kernel's own (the
+// two stages: the codes travel through registers).  Head sizes 144, 160, .. 256.  A pure function (tests/test_attn_prefill_paged_wide_f8_plan.py).
+// pp.a.k / .v are the pools' bases: bytes behind the fp16 pointer type.
+AttnPrefillWidePlan attn_prefill_paged_wide_f8_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst16, const AttnKnobs& knobs,
+                                                    const AttnPage& page, const int* q_start, const int* kv_lens, int kv_len_bias, std::string* why);
 
 // ---- launches of a plan ----------------------------------------------------------------------------------------------------------------------
 hipError_t launch_attn_onerow(const AttnPlan& pl, float* ws, uint32_t* tickets, hipStream_t st);  // ns_attn_decode.hip: AP_GENERIC, AP_SPLIT_REGS, AP_RING (+ merge)
@@ -489,6 +539,7 @@ hipError_t launch_attn_shared_paged_f8(const AttnSharedPagedPlan& pl, float* ws,
 hipError_t launch_attn_prefill_paged(const AttnPrefillPagedPlan& pl, hipStream_t st);             // ns_attn_prefill.hip: the PAGED instantiations of the 128-row kernel
 hipError_t launch_attn_prefill_paged_f8(const AttnPrefillPagedPlan& pl, hipStream_t st);          // ns_attn_prefill.hip: a plan with f8 set
 hipError_t launch_attn_prefill_paged_wide(const AttnPrefillWidePlan& pl, hipStream_t st);          // ns_attn_prefill_wide.hip: attn_wide_paged_kernel
+hipError_t launch_attn_prefill_paged_wide_f8(const AttnPrefillWidePlan& pl, hipStream_t st);       // ns_attn_prefill_wide_f8.hip: a plan with f8 set
 hipError_t launch_attn_merge(const AttnSplitParams& sp, unsigned batch, hipStream_t st, bool rows = false);  // ns_attn_decode.hip: attn_merge_kernel over sp.ws
 // touch_attn_module (ns_common.h) makes the runtime load every one of these code objects
 inline void touch_kernel(const void* kernel) {

@@ -536,8 +536,9 @@ AttnPrefillPagedPlan attn_prefill_paged_plan(const attn_fp32_fp16_fp16_fp32_fwd_
 // One launch of attn_wide_paged_kernel<pad> for every call the entry serves.  The refusals of the fp16 entry above come first, in its order and with
 // its texts (the cache, the arrays, the layouts, the head group, the grid), then the width's own: the head sizes of the other entry, the score biases
 // and scales this kernel is not built for, and a page whose rows of one head do not fit one 32-bit buffer descriptor below kAwNoCell.
-AttnPrefillWidePlan attn_prefill_paged_wide_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst16, const AttnKnobs& kn, const AttnPage& page,
-                                                 const int* q_start, const int* kv_lens, int kv_len_bias, std::string* why) {
+// (cell_bytes: what one element of the pools is — 2, or 1 for the FP8 entry below, whose strides count bytes)
+static AttnPrefillWidePlan wide_plan_of(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst16, const AttnKnobs& kn, const AttnPage& page,
+                                        const int* q_start, const int* kv_lens, int kv_len_bias, int cell_bytes, std::string* why) {
   AttnPrefillWidePlan pl;
   memset(&pl.pp, 0, sizeof(pl.pp));
   auto refuse = [&](const char* text) {
@@ -553,7 +554,8 @@ AttnPrefillWidePlan attn_prefill_paged_wide_plan(const attn_fp32_fp16_fp16_fp32_
   if (a.head_size < 8 || a.head_size % 8 != 0 || a.head_size > 256)
     return refuse("attention, wide prompt blocks over a paged cache: head_size must be a multiple of 8 from 136 to 256");
   if (a.head_size <= 128)
-    return refuse("attention, wide prompt blocks over a paged cache: head sizes up to 128 are served by ns_hip_attn_prefill_paged");
+    return refuse(cell_bytes == 1 ? "attention, wide prompt blocks over a paged cache: head sizes up to 128 are served by ns_hip_attn_prefill_paged_f8"
+                                  : "attention, wide prompt blocks over a paged cache: head sizes up to 128 are served by ns_hip_attn_prefill_paged");
   if (a.heads_kv < 1 || a.head_num < 1 || a.head_num % a.heads_kv != 0)
     return refuse("attention, wide prompt blocks over a paged cache: head_num must be a multiple of heads_kv");
   if (a.sl_q < 1) return refuse("attention, wide prompt blocks over a paged cache: sl_q is max_q, the most query rows of one request (at least 1)");
@@ -572,7 +574,7 @@ AttnPrefillWidePlan attn_prefill_paged_wide_plan(const attn_fp32_fp16_fp16_fp32_
     return refuse("attention, wide prompt blocks over a paged cache: a score scale that is not positive and finite is not built at this width");
   // a page's rows of one head under one descriptor: the last key's last byte, and every lane offset with it, below kAwNoCell
   const long long last = (1ll << page.block_shift) - 1;
-  if ((last * std::max(a.step_k_sl, a.step_v_sl) + a.head_size) * 2 >= (long long)kAwNoCell)
+  if ((last * std::max(a.step_k_sl, a.step_v_sl) + a.head_size) * cell_bytes >= (long long)kAwNoCell)
     return refuse("attention, wide prompt blocks over a paged cache: a block's rows of one kv head must lie within 2 GiB (one buffer descriptor per page and head)");
   AttnParams& p = pl.pp.a;
   p.q = a.Q;
@@ -600,6 +602,10 @@ AttnPrefillWidePlan attn_prefill_paged_wide_plan(const attn_fp32_fp16_fp16_fp32_
   pl.xcd_map = !kn.no_xcd_map && (size_t(a.heads_kv) * a.batch_size) % 8 == 0;  // (attn_prefill_paged_plan's rule)
   pl.ok = true;
   return pl;
+}
+AttnPrefillWidePlan attn_prefill_paged_wide_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst16, const AttnKnobs& kn, const AttnPage& page,
+                                                 const int* q_start, const int* kv_lens, int kv_len_bias, std::string* why) {
+  return wide_plan_of(a, dst16, kn, page, q_start, kv_lens, kv_len_bias, 2, why);
 }
 
 // ---- decode over an FP8 paged cache (ns_hip_attn_decode_paged_f8) ------------------------------------------------------------------------------------
@@ -715,6 +721,31 @@ AttnPrefillPagedPlan attn_prefill_paged_f8_plan(const attn_fp32_fp16_fp16_fp32_f
   if (const char* text = attn_f8_pool_refusal(a.head_size, a.step_v_sl, a.step_v_head_num, page.block_step, a.V)) return refuse(text);
   AttnPrefillPagedPlan pl = attn_prefill_paged_plan(a, dst16, kn, page, q_start, kv_lens, kv_len_bias, why);
   pl.f8 = pl.ok;
+  return pl;
+}
+
+// ---- ... at head sizes 144 .. 256 (ns_hip_attn_prefill_paged_wide_f8) -------------------------------------------------------------------------------
+// As above: the FP8 pool's refusals first — so head sizes 136 and 152 are refused in the pool's words — and what passes them is a layout the wide plan
+// takes as it stands: its alignment rule (row and head strides multiples of 8 elements, 16-byte aligned bases) is implied by the byte rule's multiples
+// of 16, so no legal byte layout is refused.  The one rule that counts bytes, the descriptor's span, is asked with a cell of one byte.  A head size up
+// to 128 is sent to the FP8 entry that serves it.  Every decision is kept; lds is this kernel's own: the two stages of the fp16 image and nothing
+// beside them, since the codes travel through registers.
+AttnPrefillWidePlan attn_prefill_paged_wide_f8_plan(const attn_fp32_fp16_fp16_fp32_fwd_args_t& a, const void* dst16, const AttnKnobs& kn,
+                                                    const AttnPage& page, const int* q_start, const int* kv_lens, int kv_len_bias, std::string* why) {
+  AttnPrefillWidePlan none;
+  memset(&none.pp, 0, sizeof(none.pp));
+  auto refuse = [&](const char* text) {
+    *why = text;
+    return none;
+  };
+  if (!(a.K_sc > 0.f) || !(a.V_sc > 0.f) || std::isinf(a.K_sc) || std::isinf(a.V_sc))
+    return refuse("attention, FP8 paged cache: K_sc and V_sc, the pools' scales, must be positive and finite");
+  if (a.step_k_head_size != 1 || a.step_v_head_size != 1) return refuse("attention, FP8 paged cache: K / V rows must be contiguous in the head dimension");
+  if (const char* text = attn_f8_pool_refusal(a.head_size, a.step_k_sl, a.step_k_head_num, page.block_step, a.K)) return refuse(text);
+  if (const char* text = attn_f8_pool_refusal(a.head_size, a.step_v_sl, a.step_v_head_num, page.block_step, a.V)) return refuse(text);
+  AttnPrefillWidePlan pl = wide_plan_of(a, dst16, kn, page, q_start, kv_lens, kv_len_bias, 1, why);
+  pl.f8 = pl.ok;
+  if (pl.ok) pl.lds = size_t(2) * kAwStage;
   return pl;
 }
 
